@@ -6,9 +6,16 @@ torch.distributed.run, one rank per GPU over RCCL.  One "step" = one optimizer s
 CIFAR-10 recipe network (BASELINE.json configs[1]: uncond two-decoder UNet, 216 M params, fp32,
 128 images per GPU, ddm_const schedule, dropout 0.1): q_sample -> UNet forward -> weighted loss ->
 backward -> [bucketed gradient all-reduce] -> clip 1.0 + AdamW + EMA.  Weak scaling: per-GPU batch
-is fixed.  After the timed steps rank 0 also times `sample(batch_size=128)` (10 NFE), measures the
-implicit-GEMM kernel's average duration with HIP events (roofline object) and times the CPU oracle
-on a bounded sample (cpu_baseline object).  Prints ONE JSON line.
+is fixed.  Prints ONE JSON line; `value` and `ms_per_step` come from the K timed steps.
+
+A plain run only sets up, warms up, times the K steps (and writes their outputs with --dump-outputs).
+With --full it then also times `sample(batch_size=128)` (10 NFE), measures every GEMM-shaped kernel's
+duration with HIP events in one more step (roofline object), the gradient-accumulation-2 and bf16-mode
+side lines (also_measured) and times the CPU oracle on a bounded sample (cpu_baseline object).
+
+--dump-outputs DIR writes what the last timed step computed, for comparing two builds output for
+output: loss.npy (float64), and params.npy / grads.npy (float32): the updated parameters and the
+step's gradient at a fixed, seeded sample of 2^22 parameter positions (32 MiB in all).
 """
 import argparse
 import json
@@ -48,6 +55,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=128, help="images per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements: sampling, the profiled step (roofline), "
+                         "the all-reduce exposure, grad-accum-2 + bf16 mode and the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and a fixed sample of its updated parameters and gradient as DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sample", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the grad-accum-2 and bf16-mode side measurements of the headline line")
@@ -67,7 +79,39 @@ def parse():
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
                     help="contraction precision of conv/Linear: f32 = BASELINE configs[1] (default, exact fp32 MFMA); "
                          "bf16 = configs[2] mode (bf16 MFMA operands, fp32 accumulate/storage)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_SAMPLE = 1 << 22       # parameter positions written by --dump-outputs (params + grads: 32 MiB of float32)
+
+
+def dump_outputs(out_dir, loss, flat):
+    """The last timed step's results: its loss, and the updated parameters and the gradient at a fixed, seeded sample of
+    parameter positions (the alignment padding of the flat buffers is never sampled)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sizes = torch.tensor([p.numel() for p in flat.params], dtype=torch.int64)
+    ends = torch.cumsum(sizes, 0)
+    total = int(ends[-1])
+    if total <= DUMP_SAMPLE:
+        pos = torch.arange(total, dtype=torch.int64)
+    else:
+        pos = torch.unique(torch.randint(total, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)))
+    k = torch.searchsorted(ends, pos, right=True)          # parameter holding each position
+    idx = torch.tensor(flat.offsets, dtype=torch.int64)[k] + pos - (ends[k] - sizes[k])
+    idx = idx.to(flat.flat.device)
+    arrays = {"loss": np.array([float(loss.detach())], dtype=np.float64),
+              "params": flat.flat[idx].cpu().numpy().astype(np.float32),
+              "grads": flat.grad[idx].cpu().numpy().astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    log(f"outputs of the last timed step -> {out_dir}: " + ", ".join(f"{n}{list(a.shape)}" for n, a in arrays.items()))
+    bad = [n for n, a in arrays.items() if not np.isfinite(a).all()]
+    if bad:
+        log(f"WARNING: non-finite values in the dumped {', '.join(bad)}")
 
 
 def build_sr_model(dev, small=False):
@@ -251,6 +295,8 @@ def main():
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, flat)
     if args.profile_only:
         if use_dist:
             dist.destroy_process_group()
@@ -268,19 +314,20 @@ def main():
     # on rank 0 alone would wait for its peers forever); only rank 0 records and reports.
     # The profiled step runs on ONE stream (the weight gradients' side stream is off under PROFILE; the second decoder's
     # stream is switched off here): a kernel that shares the CUs with a kernel of another stream reads longer than it is.
-    if rank == 0:
-        ops.PROFILE = []
-    branch, ops.BRANCH_STREAM = ops.BRANCH_STREAM, False
-    train_step(args.warmup + args.steps)
-    ops.BRANCH_STREAM = branch
-    barrier()
-    if reducer.active:        # two more untimed steps that measure how much of the all-reduce is NOT hidden under backward
+    if args.full:
+        if rank == 0:
+            ops.PROFILE = []
+        branch, ops.BRANCH_STREAM = ops.BRANCH_STREAM, False
+        train_step(args.warmup + args.steps)
+        ops.BRANCH_STREAM = branch
+        barrier()
+    if args.full and reducer.active:        # two more untimed steps that measure how much of the all-reduce is NOT hidden under backward
         reducer.measure = True
         for i in range(2):
             train_step(args.warmup + args.steps + 1 + i)
         barrier()
         reducer.measure = False
-    if rank == 0:
+    if args.full and rank == 0:
         recs, ops.PROFILE = ops.PROFILE, None
         log(f"profiled step: {len(recs)} GEMM-shaped launches")
         by = {}
@@ -417,7 +464,7 @@ def main():
                                          "pass) / time.  The multi-pass kernels read x (and dy) twice on the large maps: "
                                          "`traffic` is the PMC bytes per kernel launch (several launches per call)"}
     # ---- 10-step sampling, every rank samples its own batch, no collectives ----
-    if not args.no_sample:
+    if args.full and not args.no_sample:
         dpm.eval()
         skw = {"cond": batches[0]["cond"]} if args.config == "sr" else {}
         dpm.sample(batch_size=min(B, 16), **({"cond": [c[:min(B, 16)] for c in skw["cond"]]} if skw else {}))
@@ -440,7 +487,7 @@ def main():
     #  * the opt-in bf16 contraction mode (BASELINE configs[2]'s per-GPU share): same model object, conv / Linear operands rounded to
     #    bf16, everything else as in the headline.  Never part of `value`.
     extras = None
-    if world == 1 and args.config == "cifar" and args.dtype == "f32" and not args.no_extras and not args.profile_only:
+    if args.full and world == 1 and args.config == "cifar" and args.dtype == "f32" and not args.no_extras and not args.profile_only:
         dpm.train()
 
         def accum2_step(it):
@@ -510,7 +557,7 @@ def main():
                                 "backward's own kernels had drained (0 when the reducer is inactive)"}}
         if extras is not None:
             out["also_measured"] = extras
-        if not args.no_cpu_baseline and world == 1 and args.config == "cifar":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.config == "cifar":
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if use_dist:

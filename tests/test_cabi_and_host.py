@@ -261,3 +261,34 @@ def test_selection_context_and_use_counts_host_logic():
     q = torch.nn.Parameter(torch.zeros(4))           # not a direct-gradient parameter: never counted
     ops._mark_uses(Ctx, (1, q))
     assert not hasattr(q, "_adm_uses")
+
+
+def test_bench_dump_outputs_samples_real_parameter_positions(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the sampled positions are fixed by a seed, never fall into the alignment padding of the flat
+    buffers, and map to the right entries of params / grads; the files are float32 / float64."""
+    import bench
+    from adm_amd.optim import FlatParams
+    m = torch.nn.Sequential(torch.nn.Linear(7, 5), torch.nn.Linear(5, 3), torch.nn.Conv2d(3, 2, 3))
+    flat = FlatParams(m)
+    n = 0
+    for p, o in zip(flat.params, flat.offsets):          # position i of the concatenated parameters holds i + 1, padding 0
+        flat.flat[o:o + p.numel()] = torch.arange(n + 1, n + 1 + p.numel(), dtype=torch.float32)
+        n += p.numel()
+    assert flat.numel > n                                  # the layout has padding to stay out of
+    flat.grad.copy_(-flat.flat)
+    loss = torch.tensor(1.25)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", n // 2)
+    outs = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), loss, flat)
+        outs.append({k: np.load(str(tmp_path / d / f"{k}.npy")) for k in ("loss", "params", "grads")})
+    a, b = outs
+    assert a["loss"].dtype == np.float64 and a["loss"].tolist() == [1.25]
+    assert a["params"].dtype == np.float32 and a["grads"].dtype == np.float32
+    np.testing.assert_array_equal(a["params"], b["params"])
+    pos = a["params"].astype(np.int64) - 1
+    assert pos.min() >= 0 and pos.max() < n and np.all(np.diff(pos) > 0)         # real positions only, sorted, no repeats
+    np.testing.assert_array_equal(a["grads"], -a["params"])
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 10 * n)                              # a small model is written whole
+    bench.dump_outputs(str(tmp_path / "c"), loss, flat)
+    np.testing.assert_array_equal(np.load(str(tmp_path / "c" / "params.npy")), np.arange(1, n + 1, dtype=np.float32))

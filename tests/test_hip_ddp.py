@@ -177,7 +177,7 @@ def test_bench_two_ranks_prints_one_whole_job_line(tmp_path):
     import json
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
-    r = _torchrun(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--small", "--batch", "8"], tmp_path)
+    r = _torchrun(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--small", "--batch", "8", "--full"], tmp_path)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, lines
@@ -223,7 +223,7 @@ def test_bench_runs_over_a_one_rank_rccl_communicator():
     env = dict(os.environ, ADM_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1",
                LOCAL_RANK="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--small", "--steps", "3", "--warmup", "1", "--batch", "16",
-                        "--no-cpu-baseline", "--no-sample"], capture_output=True, text=True, env=env, timeout=900)
+                        "--full", "--no-cpu-baseline", "--no-sample"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     out = json.loads(line)
@@ -232,3 +232,37 @@ def test_bench_runs_over_a_one_rank_rccl_communicator():
     assert d["allreduce_exposed_ms_per_step"] >= 0.0
     assert out["value"] > 0 and out["config"]["valid"] is False       # --small is a debug configuration
     assert 0 < out["roofline"]["frac"] <= 1.0 and 0 < out["roofline"]["step"]["frac"] <= 1.0
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times only its steps: the headline keys are there, the side measurements are not;
+    --dump-outputs writes the last timed step's loss and a sample of its parameters and gradient."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--small", "--steps", "3", "--warmup", "1",
+                        "--batch", "16", "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["steps"] == 3 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert abs(out["value"] - 16 / (out["ms_per_step"] / 1e3)) <= 0.01 * out["value"]
+    assert out["roofline"] is None and out["sample_images_per_sec"] is None
+    assert "cpu_baseline" not in out and "also_measured" not in out
+    loss = np.load(str(out_dir / "loss.npy"))
+    assert loss.dtype == np.float64 and abs(float(loss[0]) - out["final_loss"]) <= 1e-3 * max(1.0, abs(out["final_loss"]))
+    total = 0
+    for name in ("params", "grads"):
+        a = np.load(str(out_dir / f"{name}.npy"))
+        assert a.dtype == np.float32 and a.ndim == 1 and a.size > 0
+        total += a.nbytes
+    assert total <= 64 << 20
