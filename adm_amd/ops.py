@@ -69,7 +69,8 @@ def _chk(t: torch.Tensor, name: str) -> torch.Tensor:
 # packed-weight cache
 # ------------------------------------------------------------------------------------------------
 class _Packed:
-    __slots__ = ("key", "fwd", "bwd", "bias", "fwd16", "bwd16", "wf", "wb", "w2f", "w2b", "w2f6", "w2b6", "w2fh", "w2bh", "g6f", "g6b", "g6fh", "g6bh", "src")
+    __slots__ = ("key", "fwd", "bwd", "bias", "fwd16", "bwd16", "wf", "wb", "w2f", "w2b", "w2f6", "w2b6", "w2fh", "w2bh", "g6f", "g6b", "g6fh", "g6bh", "src",
+                 "h3_off")
 
 
 # Contraction precision of the conv / Linear kernels: "f32" (default: exact fp32 MFMA) or "bf16" (BASELINE
@@ -94,8 +95,11 @@ BF16X6 = os.environ.get("ADM_BF16X6", "1") != "0"
 # ... or, where the activation operand comes with an upper bound of its magnitude (a GroupNorm output: the GroupNorm kernel writes
 # max |y| next to it), on THREE fp16 MFMAs per product: two-term round-to-nearest split after a power-of-two scaling (conv_wino2d_x6.hip,
 # X6Fmt<1>).  Same error against fp64 as the six-bf16 form (tools/fp16x3_accuracy.py, tests/test_hip_ops.py::test_conv_h3_*), half its
-# matrix, LDS and split work.  Weights use one fixed power-of-two scale: a scaled weight leaving the fp16 range raises a device flag
-# that repack_all() reads every 64 steps and that switches the format off (never observed: it takes a Winograd-domain weight >= 32).
+# matrix, LDS and split work.  Weights use one fixed power-of-two scale (H3_WSCALE = 2^11): a Winograd-domain 3x3 weight or a 1x1 weight
+# >= 32 leaves the fp16 range.  Each fp16 weight image is checked when it is built (first use, and again after load_state_dict or any
+# other change of the parameter made a new packed entry: one 4-byte read-back per build, _h3_weight_image): a layer whose image
+# overflows keeps running on the bf16 format.  Weights that only GROW past the limit during training (the images are then rewritten
+# in place by repack_all()) raise a device flag that repack_all() reads every 64 steps and that switches the format off everywhere.
 # ADM_FP16X3=0 keeps every split kernel on the bf16 format.
 FP16X3 = os.environ.get("ADM_FP16X3", "1") != "0"
 H3_WGRAD = os.environ.get("ADM_FP16X3_WGRAD", "1") != "0"      # ... also for the weight gradients
@@ -115,7 +119,8 @@ def _amax_slot(like: torch.Tensor) -> torch.Tensor:
     """A zeroed BOUND VECTOR (include/adm_hip.h: 64 floats, one cache line apart; the bound is their maximum) for a kernel to raise to
     max |output| -- every wave raises its own slot: one address for all of them serialised the atomics of a launch (185 us for
     a 22 us add3).  Vectors come from a pool that is zero-filled once per 4096 vectors (no per-call fill launch); a vector lives as
-    long as a tensor refers to it."""
+    long as a tensor refers to it.  The pool is filled on whichever stream asks for the vector that needs a new pool (the main, the
+    second decoder's or the weight-gradient side stream): _bound_use() orders every other stream that touches it after that fill."""
     global _amax_pool, _amax_next, _amax_pool_captured, _amax_pool_size
     # Under HIP-graph capture (the sampler's replayed forward) the pool is allocated INSIDE the capture, so that its zero fill is part
     # of the graph and every replay starts from zeroed vectors: bounds never carry over from an earlier replay (a larger stale bound
@@ -126,9 +131,52 @@ def _amax_slot(like: torch.Tensor) -> torch.Tensor:
         _amax_pool_size = 1024 if capturing else _AMAX_POOL
         _amax_pool, _amax_next = torch.zeros(_amax_pool_size * AMAX_FLOATS, device=like.device, dtype=_f32), 0
         _amax_pool_captured = capturing
+        if like.is_cuda:
+            cur = torch.cuda.current_stream(like.device)
+            _amax_pool._adm_users = {cur.cuda_stream}      # streams ordered after the fill and holding a lifetime mark
+            if not capturing:
+                _amax_pool._adm_fill = torch.cuda.Event()
+                _amax_pool._adm_fill.record(cur)
     s = _amax_pool[_amax_next * AMAX_FLOATS:(_amax_next + 1) * AMAX_FLOATS]
     _amax_next += 1
-    return s
+    return _bound_use(s)
+
+
+def _bound_use(v):
+    """A kernel on the current stream is about to raise or read the bound vector v.  The first time a stream touches a pool, it waits
+    for the pool's zero fill (an event on the stream that filled it) and marks the pool as used by it (record_stream), so that the
+    allocator does not hand the pool's memory out again while that stream may still read or raise a bound in it: the side stream's
+    weight gradients read the bounds of x and dy, the second decoder's stream raises and reads bounds of pools another stream filled.
+    Once per pool and stream."""
+    if v is None or not v.is_cuda:
+        return v
+    pool = v if v._base is None else v._base
+    users = getattr(pool, "_adm_users", None)
+    if users is None:                 # a vector made outside the pools (amax_vector): its lifetime is all that needs a mark
+        users = pool._adm_users = set()
+    s = torch.cuda.current_stream(v.device)
+    if s.cuda_stream not in users:
+        if torch.cuda.is_current_stream_capturing():
+            return v
+        fill = getattr(pool, "_adm_fill", None)
+        if fill is not None:
+            s.wait_event(fill)
+        pool.record_stream(s)
+        users.add(s.cuda_stream)
+    return v
+
+
+def _bptr(v):
+    """ptr() of a bound vector that a kernel on the current stream reads (see _bound_use)."""
+    return ptr(_bound_use(v))
+
+
+def _check_bound(t: torch.Tensor, v, what: str):
+    """AMAX_CHECK: the bound vector v must be >= max |t| (one host read each: tests only)."""
+    if AMAX_CHECK and v is not None:
+        got, bound = float(t.detach().abs().max()), float(v.max())
+        if not got <= bound:
+            raise RuntimeError(f"adm_amd: the bound {bound} of {what} is below its maximum {got}")
 
 
 def new_amax_pool():
@@ -147,7 +195,9 @@ def amax_vector(t: torch.Tensor, loose: float = 1.0) -> torch.Tensor:
 # Bounds of GRADIENT tensors travel by address: autograd hands a backward node new Python objects for its incoming gradients, so an
 # attribute set by the producing node does not arrive.  The producing node registers (address -> slot, numel, pass id); the consuming
 # conv looks its dy up; every allocation through _new() / _like() forgets the address it returns (a recycled address must not meet
-# the bound of its previous tenant), and entries of an earlier backward pass are ignored.
+# the bound of its previous tenant), and entries of an earlier backward pass are ignored.  Each entry also keeps the tensor's version:
+# a gradient that was modified after it was registered (autograd sums the gradients of a tensor with two consumers IN PLACE into the
+# first one's buffer unless ops.fanout() does the sum) is no longer covered by that bound, and the lookup then finds none.
 _grad_amax = {}
 
 
@@ -157,16 +207,13 @@ def _reg_amax(t: torch.Tensor, slot):
         if len(_grad_amax) > 8192:       # forget the entries of earlier backward passes (never this pass's: their consumers are still to come)
             for k in [k for k, e in _grad_amax.items() if e[2] != tid]:
                 del _grad_amax[k]
-        _grad_amax[t.data_ptr()] = (slot, t.numel(), tid)
+        _grad_amax[t.data_ptr()] = (slot, t.numel(), tid, t._version)
 
 
 def _get_amax(t: torch.Tensor):
     e = _grad_amax.get(t.data_ptr())
-    if e is not None and e[1] == t.numel() and e[2] == _graph_task_id() and e[2] >= 0:
-        if AMAX_CHECK:
-            got, bound = float(t.abs().max()), float(e[0].max())
-            if not got <= bound:
-                raise RuntimeError(f"adm_amd: registered bound {bound} of a gradient tensor is below its maximum {got}")
+    if e is not None and e[1] == t.numel() and e[2] == _graph_task_id() and e[2] >= 0 and e[3] == t._version:
+        _check_bound(t, e[0], "a gradient tensor (registered)")
         return e[0]
     return None
 
@@ -188,12 +235,28 @@ def _h3_flag_tensor(like):
     return _h3_flag
 
 
+def _h3_weight_image(ent: "_Packed", split) -> bool:
+    """Runs split(flag) -- a weight split kernel that raises the int32 device flag it is given when a scaled weight leaves the fp16
+    range -- on a fresh flag and reads it back: False (and the entry is marked to stay on the bf16 format) when the image overflowed."""
+    flag = torch.zeros(1, device=ent.fwd.device, dtype=torch.int32)
+    split(flag)
+    if torch.cuda.is_current_stream_capturing():     # (no read-back inside a capture: the sampler packs in its eager warm-up first)
+        return True
+    if int(flag) != 0:
+        ent.h3_off = True
+        return False
+    return True
+
+
 def _h3_operands(weight: torch.Tensor, ent: "_Packed", which: int):
     """fp16-format image of a 2-D Winograd operand (which = 0: forward, 1: data gradient), built on first use from the f32 planes and
     afterwards refreshed by repack_all() with the rest.  Only the direction that is asked for is built and kept current: most layers
-    never need the other format's image of the same direction (a third of the repack table's bytes)."""
+    never need the other format's image of the same direction (a third of the repack table's bytes).  None when the layer's weights
+    do not fit the fp16 image (the caller runs the bf16 format)."""
     global _pack_table
     name = "w2bh" if which else "w2fh"
+    if ent.h3_off:
+        return None
     if getattr(ent, name) is None:
         co, ci = weight.shape[0], weight.shape[1]
         cop, cip = ceil32(co), ceil32(ci)
@@ -202,7 +265,9 @@ def _h3_operands(weight: torch.Tensor, ent: "_Packed", which: int):
         call("adm_pack_weight_wino2d", ptr(w), ptr(w2f), ptr(w2b), co, ci, cop, cip)
         rows, cols = (cip, cop) if which else (cop, cip)
         img = torch.empty((16, 2, rows, cols), device=w.device, dtype=torch.float16)
-        call("adm_split2_f16", ptr(w2b if which else w2f), ptr(img), rows, cols, H3_WSCALE, ptr(_h3_flag_tensor(w)))
+        if not _h3_weight_image(ent, lambda flag: call("adm_split2_f16", ptr(w2b if which else w2f), ptr(img), rows, cols, H3_WSCALE,
+                                                       ptr(flag))):
+            return None
         setattr(ent, name, img)
         _pack_table = None           # the one-launch repack table must learn the new destination
     return getattr(ent, name)
@@ -350,13 +415,17 @@ def _gemm_x6_operand(ent: "_Packed", which: int):
 
 def _gemm_h3_operand(ent: "_Packed", which: int):
     """[K/16][2][rows][16] fp16 image (scale H3_WSCALE) of a packed 1x1 operand: which = 0 forward (rows = couts), 1 data gradient (rows =
-    cins); built on first use, refreshed by repack_all() afterwards."""
+    cins); built on first use, refreshed by repack_all() afterwards; None when the weights do not fit it (see _h3_weight_image)."""
     global _pack_table
     name = "g6bh" if which else "g6fh"
+    if ent.h3_off:
+        return None
     if getattr(ent, name) is None:
         src = ent.bwd if which else ent.fwd
         img = torch.empty((2,) + tuple(src.shape), device=src.device, dtype=torch.float16)
-        call("adm_split2_rows_f16", ptr(src), ptr(img), src.shape[0], src.shape[1], src.shape[1], H3_WSCALE, ptr(_h3_flag_tensor(src)))
+        if not _h3_weight_image(ent, lambda flag: call("adm_split2_rows_f16", ptr(src), ptr(img), src.shape[0], src.shape[1], src.shape[1],
+                                                       H3_WSCALE, ptr(flag))):
+            return None
         setattr(ent, name, img)
         _pack_table = None           # the one-launch repack table must learn the new destination
     return getattr(ent, name)
@@ -387,6 +456,7 @@ def packed(weight: torch.Tensor, bias: Optional[torch.Tensor], ks: int, qkv: boo
     ent.w2fh = ent.w2bh = None
     ent.g6f = ent.g6b = None
     ent.g6fh = ent.g6bh = None
+    ent.h3_off = False
     ent.src = (co, ci, ks, qkv)
     ent.fwd = _new((cop, ks * ks * cip), w)
     ent.bwd = _new((cip, ks * ks * cop), w)
@@ -856,11 +926,12 @@ class _Conv(torch.autograd.Function):
             raise RuntimeError("a bf16-stored activation reached a conv that does not run in the bf16 mode")
         wino = not use_bf16 and _use_wino(B, Ho, Wo, ks, up, tile) and not qkv
         wino2 = wino and _use_wino2d(B, Ho, Wo, ks, up, tile)
-        h3 = wino2 and BF16X6 and FP16X3 and amax is not None       # fp16 format: the operand came with its max |x|
+        h3 = (wino2 and BF16X6 and FP16X3 and amax is not None       # fp16 format: the operand came with its max |x| ...
+              and _h3_operands(weight, pk, 0) is not None)           # ... and the weights fit their fp16 image
         wq2 = _wino2_operands(weight, pk, 0) if (wino2 and not h3) else None
         wq = _wino_operands(weight, pk)[0] if (wino and not wino2) else None
         g6 = not use_bf16 and _use_gemm_x6(_sel_batch(B) * Ho * Wo, ks, up, cop, cip)
-        g6h = g6 and FP16X3 and H3_GEMM and amax is not None
+        g6h = g6 and FP16X3 and H3_GEMM and amax is not None and _gemm_h3_operand(pk, 0) is not None
         # the bound of a 1x1 conv's OUTPUT (qkv -> attention -> proj; proj + residual -> the next block's skip conv): written by the epilogue
         global _conv_amax_out
         _conv_amax_out = None
@@ -874,11 +945,11 @@ class _Conv(torch.autograd.Function):
                 sk = 1 if _SELECT_BATCH is not None else hip.lib().adm_wino2d_x6_splitk(B, Ho, Wo, cip, cop)
                 wsk = _new((sk * B * Ho * Wo * cop,), x) if sk > 1 else None
                 call("adm_conv_fwd_wino2d_h3", ptr(x), ptr(_h3_operands(weight, pk, 0)), ptr(pk.bias), ptr(res), ptr(y), ptr(wsk),
-                     0 if wsk is None else wsk.numel(), B, Ho, Wo, cip, cip, cop, cop, cop, cop, ptr(amax), H3_WSCALE, int(up))
+                     0 if wsk is None else wsk.numel(), B, Ho, Wo, cip, cip, cop, cop, cop, cop, _bptr(amax), H3_WSCALE, int(up))
             elif g6h:
                 _conv_amax_out = _amax_slot(x) if want_out else None
                 call("adm_gemm_x6_h3", ptr(x), ptr(_gemm_h3_operand(pk, 0)), ptr(pk.bias), ptr(res), ptr(y), B * Ho * Wo, cip, cip, cop,
-                     cop, cop, cop, ptr(amax), H3_WSCALE, ptr(_conv_amax_out))
+                     cop, cop, cop, _bptr(amax), H3_WSCALE, ptr(_conv_amax_out))
             elif g6 and want_out:
                 _conv_amax_out = _amax_slot(x)
                 call("adm_gemm_x6_amax", ptr(x), ptr(_gemm_x6_operand(pk, 0)), ptr(pk.bias), ptr(res), ptr(y), B * Ho * Wo, cip, cip, cop,
@@ -977,6 +1048,8 @@ class _Conv(torch.autograd.Function):
                 if amax_x is not None and (x6_w or g6_w) and not bf16 and H3_WGRAD:
                     amax_dy = _get_amax(dy)
                 h3_w = amax_dy is not None          # fp16 format (conv_wgrad_x6.hip FMT 1): both operands came with their bounds
+                if h3_w:
+                    _check_bound(x, amax_x, "a conv input (weight gradient)")
                 kind = "wgrad_wino2h3" if (h3_w and x6_w) else "wgrad_gemmh3" if h3_w else "wgrad_wino2x6" if x6_w else "wgrad_gemmx6" if g6_w else "wgrad_wino2" if wino2_w else "wgrad_wino" if wino_w else "wgrad"
                 with _Prof(kind, 2.0 * B * Ho * Wo * co * ci * ks * ks,
                            f"{kind.replace('_', '-')} P={B * Ho * Wo} Co={cop} Ci={cip} ks={ks}"):
@@ -989,10 +1062,10 @@ class _Conv(torch.autograd.Function):
                              Wo, cip, cip, cop, cop, ks, int(up), auto)
                     elif h3_w and x6_w:
                         call("adm_conv_wgrad_x6_h3", ptr(x), ptr(dy), ptr(dwp), ptr(bws if det else dbp), B, Ho, Wo, cip, cip, cop, cop,
-                             splits if det else auto, int(up), int(det), ptr(amax_x), ptr(amax_dy))
+                             splits if det else auto, int(up), int(det), _bptr(amax_x), _bptr(amax_dy))
                     elif h3_w:
                         call("adm_gemm_wgrad_x6_h3", ptr(x), ptr(dy), ptr(dwp), ptr(bws if det else dbp), B * Ho * Wo, cip, cip, cop, cop,
-                             splits if det else auto, int(det), ptr(amax_x), ptr(amax_dy))
+                             splits if det else auto, int(det), _bptr(amax_x), _bptr(amax_dy))
                     elif det and g6_w:
                         call("adm_gemm_wgrad_x6_ws", ptr(x), ptr(dy), ptr(dwp), ptr(bws), B * Ho * Wo, cip, cip, cop, cop, splits)
                     elif g6_w:
@@ -1066,12 +1139,12 @@ class _Conv(torch.autograd.Function):
             wino = not use_bf16 and _use_wino(B, Ho, Wo, ks, False, -1) and not qkv
             wino2 = wino and _use_wino2d(B, Ho, Wo, ks, False, -1)
             amax_dy = _get_amax(dy) if (wino2 and BF16X6 and FP16X3) else None
-            h3 = amax_dy is not None
+            h3 = amax_dy is not None and _h3_operands(weight, pk, 1) is not None
             wq2 = _wino2_operands(weight, pk, 1) if (wino2 and not h3) else None
             wq = _wino_operands(weight, pk)[1] if (wino and not wino2) else None
             g6 = not use_bf16 and _use_gemm_x6(B * Ho * Wo, ks, up, cip, cop)
             amax_g = _get_amax(dy) if (g6 and FP16X3 and H3_GEMM) else None
-            g6h = amax_g is not None
+            g6h = amax_g is not None and _gemm_h3_operand(pk, 1) is not None
             kind = ("wino2h3" if h3 else "wino2x6" if BF16X6 else "wino2") if wino2 else "wino" if wq is not None else ("gemmh3" if g6h else "gemmx6") if g6 else "igemm"
             with _Prof(kind, 2.0 * B * Ho * Wo * co * ci * ks * ks,
                        f"dgrad{'-' + kind if kind != 'igemm' else ''} M={B * Ho * Wo} N={cip} K={ks * ks * cop}"):
@@ -1079,11 +1152,11 @@ class _Conv(torch.autograd.Function):
                     sk = hip.lib().adm_wino2d_x6_splitk(B, Ho, Wo, cop, cip)
                     wsk = _new((sk * B * Ho * Wo * cip,), dy) if sk > 1 else None
                     call("adm_conv_fwd_wino2d_h3", ptr(dy), ptr(_h3_operands(weight, pk, 1)), None, None, ptr(dxf), ptr(wsk),
-                         0 if wsk is None else wsk.numel(), B, Ho, Wo, cop, cop, cip, cip, cip, cip, ptr(amax_dy), H3_WSCALE, 0)
+                         0 if wsk is None else wsk.numel(), B, Ho, Wo, cop, cop, cip, cip, cip, cip, _bptr(amax_dy), H3_WSCALE, 0)
                 elif g6h:       # (the epilogue leaves max |dx|: the attention backward behind a proj conv runs on the fp16 format)
                     slot_dx = _amax_slot(dy)
                     call("adm_gemm_x6_h3", ptr(dy), ptr(_gemm_h3_operand(pk, 1)), None, None, ptr(dxf), B * Ho * Wo, cop, cop, cip, cip,
-                         cip, cip, ptr(amax_g), H3_WSCALE, ptr(slot_dx))
+                         cip, cip, _bptr(amax_g), H3_WSCALE, ptr(slot_dx))
                     _reg_amax(dxf, slot_dx)
                 elif g6:
                     call("adm_gemm_x6", ptr(dy), ptr(_gemm_x6_operand(pk, 1)), None, None, ptr(dxf), B * Ho * Wo, cop, cop, cip, cip,
@@ -1500,7 +1573,8 @@ class _Attention(torch.autograd.Function):
         h3 = amax is not None and ATTN_H3 and FP16X3 and COMPUTE == "f32" and (L in (32, 64, 128, 256) or (L % 256 == 0 and L <= 16384))
         with _Prof("attnh3" if h3 else "attn", 4.0 * L * L * 64 * B * heads):
             if h3:
-                call("adm_attn_fwd_h3", ptr(qkv), ptr(out), ptr(lse), ptr(amax), B, L, heads)
+                _check_bound(qkv, amax, "qkv (attention forward)")
+                call("adm_attn_fwd_h3", ptr(qkv), ptr(out), ptr(lse), _bptr(amax), B, L, heads)
             else:
                 call("adm_attn_fwd", ptr(qkv), ptr(out), ptr(lse), B, L, heads)
         ctx.save_for_backward(qkv, out, lse)
@@ -1519,7 +1593,8 @@ class _Attention(torch.autograd.Function):
         amax_g = _get_amax(dout) if (ctx.amax_qkv is not None and ATTN_H3_BWD) else None
         with _Prof("attnh3" if amax_g is not None else "attn", 10.0 * (H * W) ** 2 * 64 * B * ctx.heads):
             if amax_g is not None:      # both bounds at hand: the fp16 split format (attention_h3.hip)
-                call("adm_attn_bwd_h3", ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), ptr(delta), ptr(ctx.amax_qkv), ptr(amax_g),
+                _check_bound(qkv, ctx.amax_qkv, "qkv (attention backward)")
+                call("adm_attn_bwd_h3", ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), ptr(delta), _bptr(ctx.amax_qkv), _bptr(amax_g),
                      ptr(slot_a), B, H * W, ctx.heads)
             elif slot_a is not None:
                 call("adm_attn_bwd_amax", ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), ptr(delta), ptr(slot_a), B, H * W, ctx.heads)

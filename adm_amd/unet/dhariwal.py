@@ -299,6 +299,8 @@ class DhariwalUNet(nn.Module):
         f_y = None
         x, x2 = ops.fanout(x, 2) if self.two_decoders else (x, None)      # the bottleneck feeds both decouple modules
         s2 = ops.branch_stream() if (self.two_decoders and x.is_cuda) else None
+        # the second decoder is issued first on either path: the dropout seeds are drawn in issue order (ops.next_dropout_seed), so each
+        # decoder gets the same masks with and without ops.BRANCH_STREAM
         if s2 is not None:      # the second decoder on its own stream, concurrently with the first (ops.BRANCH_STREAM)
             main = torch.cuda.current_stream()
             with torch.cuda.stream(s2):
@@ -306,9 +308,9 @@ class DhariwalUNet(nn.Module):
             f_x = self._decode(self.dec, _decouple(self.decouple1, x), skips, emb, self.out_norm, self.out_conv, ratios, ss=ss)
             main.wait_stream(s2)
             return f_x, f_y
-        f_x = self._decode(self.dec, _decouple(self.decouple1, x), skips, emb, self.out_norm, self.out_conv, ratios, ss=ss)
         if self.two_decoders:
             f_y = self._decode(self.dec2, _decouple(self.decouple2, x2), skips2, emb, self.out_norm2, self.out_conv2, ss=ss)
+        f_x = self._decode(self.dec, _decouple(self.decouple1, x), skips, emb, self.out_norm, self.out_conv, ratios, ss=ss)
         return f_x, f_y
 
 
