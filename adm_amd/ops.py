@@ -1142,7 +1142,10 @@ class _Conv(torch.autograd.Function):
             h3 = amax_dy is not None and _h3_operands(weight, pk, 1) is not None
             wq2 = _wino2_operands(weight, pk, 1) if (wino2 and not h3) else None
             wq = _wino_operands(weight, pk)[1] if (wino and not wino2) else None
-            g6 = not use_bf16 and _use_gemm_x6(B * Ho * Wo, ks, up, cip, cop)
+            # (a data gradient that sums fewer than 32 real couts stays on the f32 kernel: over so few terms the split formats' truncated
+            #  cross products are not averaged out, and a head's dx over 1 or 3 couts measured 1.05-1.39x of twice the f32 kernel's rms
+            #  error against fp64, tests/test_hip_accuracy.py)
+            g6 = not use_bf16 and co >= 32 and _use_gemm_x6(B * Ho * Wo, ks, up, cip, cop)
             amax_g = _get_amax(dy) if (g6 and FP16X3 and H3_GEMM) else None
             g6h = amax_g is not None and _gemm_h3_operand(pk, 1) is not None
             kind = ("wino2h3" if h3 else "wino2x6" if BF16X6 else "wino2") if wino2 else "wino" if wq is not None else ("gemmh3" if g6h else "gemmx6") if g6 else "igemm"
