@@ -9,8 +9,10 @@ the deterministic sampler, as the reference returns), buffer ``eps``, attributes
 
 Differences, all documented in DESIGN.md:
   * every RNG draw (t, noise, x_T, sampler epsilons) can be injected for parity tests;
-  * the LPIPS/VGG16 term needs fetched weights and cannot run offline: ``loss_vlb`` is 0 (the
-    reference itself crashes in that configuration, ddm_const_2.py:251);
+  * the LPIPS/VGG16 term (``loss_vlb``, ddm_const.py:351-358 / ddm_const_2.py:242-251) runs on the HIP path
+    (adm_amd/ddm/lpips.py) when ``perceptual_weight > 0`` AND its weights were supplied: by the cfg key ``lpips_ckpt``, by
+    ``set_perceptual_loss()``, or by a checkpoint whose state dict carries ``perceptual_loss.*``.  No weights ship and none
+    are ever fetched; without them the wrapper warns and ``loss_vlb`` is 0;
   * ``use_augment`` runs the AugmentPipe on the GPU (adm_amd/ddm/augment.py) without the reference's per-step host
     read-back of the padding margin; its draws are injectable (``augment_draws=``).
 """
@@ -45,6 +47,7 @@ class DDPMBase(nn.Module):
                  beta_schedule="cosine", clip_x_start=True, input_keys=("image",), start_dist="normal",
                  sample_type="naive", perceptual_weight=1.0, use_l1=False, **kwargs):
         ckpt_path = kwargs.pop("ckpt_path", None)
+        lpips_ckpt = kwargs.pop("lpips_ckpt", None)
         ignore_keys = kwargs.pop("ignore_keys", [])
         only_model = kwargs.pop("only_model", False)
         cfg = kwargs.pop("cfg", None)
@@ -71,9 +74,11 @@ class DDPMBase(nn.Module):
             raise NotImplementedError("use_l1 is implemented for the latent wrappers only (no pixel-space DDM config sets it)")
         self.use_l1 = use_l1
         self.perceptual_weight = perceptual_weight
-        if perceptual_weight > 0 and self.USES_LPIPS:
-            warnings.warn("adm_amd: the LPIPS term (perceptual_weight > 0) needs VGG16 weights that cannot be fetched "
-                          "offline; loss_vlb is 0 (see DESIGN.md)", stacklevel=2)
+        if lpips_ckpt is None:
+            lpips_ckpt = _cfg_get(cfg, "lpips_ckpt", None)
+        if perceptual_weight > 0 and self.USES_LPIPS and lpips_ckpt:
+            from .lpips import LPIPS
+            self.set_perceptual_loss(LPIPS.from_file(lpips_ckpt))
         self.use_augment = bool(_cfg_get(cfg, "use_augment", False))
         if self.use_augment:      # ddm_const.py:179-180 (p = 0.15) / ddm_const_2.py:112-113 (p = 0.12)
             from .augment import AugmentPipe
@@ -81,6 +86,25 @@ class DDPMBase(nn.Module):
         self._eps_f = float(self.eps)
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys, only_model)
+        if perceptual_weight > 0 and self.USES_LPIPS and not self.lpips_active:
+            warnings.warn("adm_amd: the LPIPS term (perceptual_weight > 0) needs VGG16 weights that cannot be fetched "
+                          "offline; loss_vlb is 0 (see DESIGN.md)", stacklevel=2)
+
+    # ------------------------------------------------------------------ LPIPS term
+    @property
+    def lpips_active(self) -> bool:
+        """The LPIPS term is computed: perceptual_weight > 0 (a gate, not a factor: ddm_const.py:355) and weights were supplied."""
+        return self.USES_LPIPS and self.perceptual_weight > 0 and getattr(self, "perceptual_loss", None) is not None
+
+    def set_perceptual_loss(self, lpips):
+        """Install an adm_amd.ddm.lpips.LPIPS instance as the submodule ``perceptual_loss`` (the reference's attribute name).  It is
+        frozen: the optimiser, the EMA and the gradient reducer see no new trainable parameter."""
+        if not self.USES_LPIPS:
+            raise NotImplementedError("the latent p_losses has no LPIPS term")
+        for p in lpips.parameters():
+            p.requires_grad = False
+        self.perceptual_loss = lpips.to(self.eps.device).eval()
+        return self
 
     # ------------------------------------------------------------------ checkpoints
     def init_from_ckpt(self, path, ignore_keys=(), only_model=False, use_ema=False):
@@ -92,6 +116,10 @@ class DDPMBase(nn.Module):
         for k in list(sd.keys()):
             if any(k.startswith(ik) for ik in ignore_keys):
                 del sd[k]
+        if (self.perceptual_weight > 0 and self.USES_LPIPS and not only_model and getattr(self, "perceptual_loss", None) is None
+                and any(k.startswith("perceptual_loss.") for k in sd)):      # a reference-trained checkpoint brings its own VGG16
+            from .lpips import LPIPS
+            self.set_perceptual_loss(LPIPS.from_state_dict(sd))
         target = self.model if only_model else self
         missing, unexpected = target.load_state_dict(sd, strict=False)
         print(f"Restored from {path} with {len(missing)} missing and {len(unexpected)} unexpected keys")
@@ -167,14 +195,27 @@ class DDPMBase(nn.Module):
         t = t.to(torch.float32).contiguous()
         x_noisy = self.q_sample(x_start, noise, t)
         C_pred, noise_pred = self.model(x_noisy, t, **kwargs)
+        lpips = self.lpips_active
+        if lpips:       # the predictions get a second consumer: the gradient sum is ops.fanout's kernel, not autograd's in-place add
+            C_pred, C_lp = ops.fanout(C_pred, 2)
+            if self.SCHEDULE == "const":
+                noise_lp = None          # x_rec = -C_pred (ddm_const.py:326)
+            else:
+                noise_pred, noise_lp = ops.fanout(noise_pred, 2)
         w1, w2 = self.loss_weights(t)
         w = torch.stack([w1, w2], dim=1).contiguous()
         loss_simple_mean, per_sample = ops.ddm_loss(C_pred, noise_pred, x_start, noise, w)
         B, n = x_start.shape[0], x_start[0].numel()
-        loss_vlb = torch.zeros((), device=x_start.device)
+        if lpips:
+            # loss_vlb = LPIPS(x_rec, x_start).sum([1,2,3]) * rec_weight is [B] * [B,1] -> [B,B] in the reference, and its sum / B the
+            # PRODUCT of the two sums (ddm_const.py:351-358 / ddm_const_2.py:242-251; the same broadcast as the latent L1 term)
+            per_lpips = self.perceptual_loss.from_predictions(C_lp, noise_lp, x_noisy, t, x_start, self._sched)
+            loss_vlb = per_lpips.sum() * ((-torch.log(t) / 2).sum() / B)
+        else:
+            loss_vlb = torch.zeros((), device=x_start.device)
         loss = loss_simple_mean + loss_vlb
         log = {"train/loss_simple": per_sample.sum() / B / n,
-               "train/loss_vlb": loss_vlb / B / n,
+               "train/loss_vlb": loss_vlb.detach() / n,        # (loss_vlb carries the reference's one / B already)
                "train/loss": loss.detach() / B / n}
         return loss, log
 

@@ -142,6 +142,13 @@ _SIGS = {
     "adm_sumsq_blocks": [L],
     "adm_sumsq": [P, P, P, L, P],
     "adm_adamw_step": [P, P, P, P, P, P, L, F, F, F, F, F, F, I, F, F, P],
+    "adm_lpips_input": [P, P, P, P, P, P, P, I, I, I, P],
+    "adm_lpips_input_bwd": [P, P, P, P, P, I, I, I, P],
+    "adm_maxpool2x2_fwd": [P, P, I, I, I, I, P],
+    "adm_maxpool2x2_bwd": [P, P, P, I, I, I, I, P],
+    "adm_lpips_head_blocks": [I],
+    "adm_lpips_head_fwd": [P, P, P, P, P, I, I, I, I, P],
+    "adm_lpips_head_bwd": [P, P, P, P, P, I, I, I, P],
 }
 EXPORTS = tuple(_SIGS)
 
@@ -183,7 +190,7 @@ def ptr(t) -> c_void_p:
 
 
 NO_STREAM = ("adm_version", "adm_conv_splitk", "adm_gn_splits", "adm_aug_workspace_floats", "adm_conv_wgrad_plan",
-             "adm_sumsq_blocks", "adm_lnc_blocks", "adm_bn_blocks", "adm_linattn_ws_floats", "adm_wino2d_splitk", "adm_wino2d_x6_splitk", "adm_wino2d_variant", "adm_wino2d_h3_wide", "adm_wgrad_h3_blocks", "adm_gn_fused", "adm_conv_wgrad_x6_plan", "adm_gemm_wgrad_x6_plan")      # host-side queries: no stream argument, called as lib().name(...)
+             "adm_sumsq_blocks", "adm_lnc_blocks", "adm_bn_blocks", "adm_linattn_ws_floats", "adm_wino2d_splitk", "adm_wino2d_x6_splitk", "adm_wino2d_variant", "adm_wino2d_h3_wide", "adm_wgrad_h3_blocks", "adm_gn_fused", "adm_conv_wgrad_x6_plan", "adm_gemm_wgrad_x6_plan", "adm_lpips_head_blocks")      # host-side queries: no stream argument, called as lib().name(...)
 
 
 def call(name: str, *args):

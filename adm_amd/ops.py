@@ -2079,3 +2079,118 @@ def sampler_step_stochastic(x64, c_pred, n_pred, z64, t64, s64, schedule: int, c
     call("adm_sampler_step_stochastic", ptr(x64), ptr(_chk(c_pred, "C")), ptr(_chk(n_pred, "noise")), ptr(z64), ptr(t64),
          ptr(s64), schedule, int(clip_x0), float(scale_input), int(last), B, x64.numel() // B)
     return x64
+
+
+# ------------------------------------------------------------------------------------------------
+# LPIPS branch of the pixel-space loss (csrc/lpips.hip; the VGG16 convolutions themselves are conv2d)
+# ------------------------------------------------------------------------------------------------
+class _LpipsInput(torch.autograd.Function):
+    """(x_rec - shift) / scale as NHWC with 32 channels, x_rec formed from the predictions in the same kernel:
+    schedule -1 = `a` is the image itself, 0 = -C_pred, 1 = x_noisy - C_pred t - t noise_pred."""
+
+    @staticmethod
+    def forward(ctx, a, n_pred, x_noisy, t, shift, scale, schedule):
+        a = _chk(a, "C_pred" if schedule >= 0 else "image")
+        B, C, H, W = a.shape
+        if C != 3:
+            raise NotImplementedError("the LPIPS input has three channels")
+        if schedule == 1:
+            n_pred, x_noisy, t = _chk(n_pred, "noise_pred"), _chk(x_noisy, "x_noisy"), _chk(t, "t")
+        y = _new((B, H, W, 32), a)
+        call("adm_lpips_input", ptr(a), ptr(n_pred), ptr(x_noisy), ptr(t), ptr(shift), ptr(scale), ptr(y), B, H * W, schedule)
+        ctx.save_for_backward(t if schedule == 1 else None, scale)
+        ctx.meta = (tuple(a.shape), schedule)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        t, scale = ctx.saved_tensors
+        (B, C, H, W), schedule = ctx.meta
+        dy = _chk(dy, "dy")
+        da = _new((B, C, H, W), dy)
+        dn = _new((B, C, H, W), dy) if schedule == 1 else None
+        call("adm_lpips_input_bwd", ptr(dy), ptr(t), ptr(scale), ptr(da), ptr(dn), B, H * W, schedule)
+        return da, dn, None, None, None, None, None
+
+
+def lpips_input(a, n_pred, x_noisy, t, shift, scale, schedule: int):
+    """The LPIPS network's input [B,H,W,32] from NCHW tensors: schedule -1 takes the image `a`; 0 ('const') and 1 ('const_2')
+    take a = C_pred and rebuild x_rec (ddm_const.py:326 / ddm_const_2.py:217).  Differentiable in a and, for const_2, n_pred."""
+    if schedule not in (-1, 0, 1):
+        raise ValueError(schedule)
+    shift, scale = _chk(shift.reshape(-1), "shift"), _chk(scale.reshape(-1), "scale")
+    if schedule != 1:
+        n_pred = x_noisy = t = None
+    return _LpipsInput.apply(a, n_pred, x_noisy, t, shift, scale, int(schedule))
+
+
+class _MaxPool2x2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = _chk(x, "x")
+        B, H, W, C = x.shape
+        y = _new((B, H // 2, W // 2, C), x)
+        call("adm_maxpool2x2_fwd", ptr(x), ptr(y), B, H, W, C)
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        B, H, W, C = x.shape
+        dx = _like(x)
+        call("adm_maxpool2x2_bwd", ptr(x), ptr(_chk(dy, "dy")), ptr(dx), B, H, W, C)
+        return dx
+
+
+def maxpool2x2(x):
+    """nn.MaxPool2d(kernel_size=2, stride=2) on NHWC; ties give their gradient to the first maximum, as F.max_pool2d does."""
+    if x.shape[1] % 2 or x.shape[2] % 2:
+        raise NotImplementedError("maxpool2x2 needs even H and W")
+    return _MaxPool2x2.apply(x)
+
+
+class _LpipsHeads(torch.autograd.Function):
+    """out[b] = sum_k mean_p sum_c lin_k[c] (f0_k / (|f0_k| + 1e-10) - f1_k / (|f1_k| + 1e-10))^2 over the taps k: one launch pair per tap,
+    summed in tap order into one [B] vector.  Differentiable in the f0_k only."""
+
+    @staticmethod
+    def forward(ctx, n, *args):
+        f0s = [_chk(f, "f0") for f in args[:n]]
+        f1s = [_chk(f, "f1") for f in args[n:2 * n]]
+        ws = [_chk(w.detach().reshape(-1), "lin weight") for w in args[2 * n:]]
+        B = f0s[0].shape[0]
+        out = _new((B,), f0s[0])
+        for k, (f0, f1, w) in enumerate(zip(f0s, f1s, ws)):
+            _, H, W, C = f0.shape
+            if f1.shape != f0.shape or w.numel() != C:
+                raise RuntimeError(f"LPIPS head {k}: f0 {tuple(f0.shape)}, f1 {tuple(f1.shape)}, lin {w.numel()}")
+            part = _new((B * hip.lib().adm_lpips_head_blocks(H * W),), f0)
+            call("adm_lpips_head_fwd", ptr(f0), ptr(f1), ptr(w), ptr(out), ptr(part), B, H * W, C, int(k > 0))
+        ctx.save_for_backward(*f0s, *f1s, *ws)
+        ctx.n = n
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        n, t = ctx.n, ctx.saved_tensors
+        dout = _chk(dout, "dout")
+        grads = []
+        for k in range(n):
+            if not ctx.needs_input_grad[1 + k]:
+                grads.append(None)
+                continue
+            f0, f1, w = t[k], t[n + k], t[2 * n + k]
+            B, H, W, C = f0.shape
+            df0 = _like(f0)
+            call("adm_lpips_head_bwd", ptr(f0), ptr(f1), ptr(w), ptr(dout), ptr(df0), B, H * W, C)
+            grads.append(df0)
+        return (None, *grads, *([None] * (2 * n)))
+
+
+def lpips_heads(f0s, f1s, lins):
+    """Per-sample LPIPS value [B] from the tapped NHWC feature maps of the input (f0s) and the target (f1s) and the `lin` weights."""
+    f0s, f1s, lins = list(f0s), list(f1s), list(lins)
+    if not (len(f0s) == len(f1s) == len(lins)) or not f0s:
+        raise ValueError("lpips_heads needs one f0, f1 and lin weight per tap")
+    return _LpipsHeads.apply(len(f0s), *f0s, *[f.detach() for f in f1s], *lins)

@@ -544,6 +544,38 @@ int adm_linattn_fwd(const float* qkv, float* out, float* ctx, float* kst, float*
 int adm_linattn_bwd(const float* qkv, const float* dout, const float* ctx, const float* kst, float* dqkv, float* dctx, float* S,
                     float* ws, int B, int N, hipStream_t stream);
 
+
+/* ================================================================================================
+ * LPIPS term of the pixel-space loss (ddm_const.py:351-358 / ddm_const_2.py:242-251 with
+ * taming/modules/losses/lpips.py): everything around the VGG16 convolutions, which are adm_conv_fwd* calls.
+ * No float atomics: every sum has a fixed order.
+ * ================================================================================================ */
+
+/* y[B][HW][32] = (x_rec - shift) / scale in channels 0..2, zero in 3..31 (ScalingLayer, lpips.py:56-63, fused with the layout change).
+ * schedule -1: x_rec = a (an image, e.g. the target x_start); 0 'const': x_rec = -a with a = C_pred (ddm_const.py:326);
+ * 1 'const_2': x_rec = x_noisy - a t - t n_pred (ddm_const_2.py:217), t [B].  a, n_pred, x_noisy are NCHW [B][3][HW]; shift, scale: 3 floats. */
+int adm_lpips_input(const float* a, const float* n_pred, const float* x_noisy, const float* t, const float* shift,
+                    const float* scale, float* y, int B, int HW, int schedule, hipStream_t stream);
+/* its adjoint: d_a (and, schedule 1, d_n) in NCHW from dy [B][HW][32]. */
+int adm_lpips_input_bwd(const float* dy, const float* t, const float* scale, float* d_a, float* d_n, int B, int HW,
+                        int schedule, hipStream_t stream);
+
+/* nn.MaxPool2d(2, 2) of VGG16 `features` on NHWC: x [B][H][W][C] -> y [B][H/2][W/2][C]; H, W even, C % 4 == 0.  The backward
+ * finds the maximum again from x (no index tensor) and gives the gradient to the first one in the order (0,0), (0,1), (1,0), (1,1),
+ * as F.max_pool2d does on ties. */
+int adm_maxpool2x2_fwd(const float* x, float* y, int B, int H, int W, int C, hipStream_t stream);
+int adm_maxpool2x2_bwd(const float* x, const float* dy, float* dx, int B, int H, int W, int C, hipStream_t stream);
+
+/* One tap of LPIPS.forward (lpips.py:45-53, 115-121): out[b] (+)= mean_p sum_c w[c] (f0/(|f0|+1e-10) - f1/(|f1|+1e-10))^2 with the
+ * norms over the channels of position p; f0, f1 [B][HW][C], C in {64, 128, 256, 512}; part = workspace of
+ * B * adm_lpips_head_blocks(HW) floats.  The backward is with respect to f0 only: df0 = d out[b] / d f0 * dout[b]; where f0 is zero in
+ * every channel of a position (the reference's gradient is NaN there) it is zero. */
+int adm_lpips_head_blocks(int HW);
+int adm_lpips_head_fwd(const float* f0, const float* f1, const float* w, float* out, float* part, int B, int HW, int C,
+                       int accumulate, hipStream_t stream);
+int adm_lpips_head_bwd(const float* f0, const float* f1, const float* w, const float* dout, float* df0, int B, int HW, int C,
+                       hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
