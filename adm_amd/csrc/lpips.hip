@@ -8,7 +8,8 @@
 // input: x_rec from the predictions, ScalingLayer, NCHW -> NHWC with 32 channels (3..31 zero)
 // ---------------------------------------------------------------------------------------------------------------------------
 // schedule: -1 the image itself (a = x), 0 'const' x_rec = -C_pred (ddm_const.py:326), 1 'const_2' x_rec = x_noisy - C_pred t - t noise_pred
-// (ddm_const_2.py:217).  Eight threads per pixel, one 16-byte store each: a wave writes 1 KiB contiguous.
+// (ddm_const_2.py:217), 2 'linear' x_rec = x_noisy - K_pred t^2/2 - C_pred t - sqrt(t) noise_pred with a = theta_pred = [K_pred | C_pred],
+// six channels (ddm_linear.py:173-176, 203-204).  Eight threads per pixel, one 16-byte store each: a wave writes 1 KiB contiguous.
 __global__ __launch_bounds__(256) void lpips_input_kernel(const float* __restrict__ a, const float* __restrict__ n_pred,
                                                           const float* __restrict__ x_noisy, const float* __restrict__ t,
                                                           const float* __restrict__ shift, const float* __restrict__ scale,
@@ -19,21 +20,26 @@ __global__ __launch_bounds__(256) void lpips_input_kernel(const float* __restric
   f32x4 v = {0.f, 0.f, 0.f, 0.f};
   if ((idx & 7) == 0) {
     const long b = p / HW, hw = p - b * HW;
-    const float tb = schedule == 1 ? t[b] : 0.f;
+    const float tb = schedule >= 1 ? t[b] : 0.f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const long i = (b * 3 + c) * HW + hw;
       float xr;
       if (schedule < 0) xr = a[i];
       else if (schedule == 0) xr = -a[i];
-      else xr = x_noisy[i] - a[i] * tb - tb * n_pred[i];
+      else if (schedule == 1) xr = x_noisy[i] - a[i] * tb - tb * n_pred[i];
+      else {
+        const long ik = (b * 6 + c) * HW + hw;
+        xr = ((x_noisy[i] - a[ik] * (tb * tb / 2.f)) - a[ik + 3L * HW] * tb) - sqrtf(tb) * n_pred[i];
+      }
       v[c] = (xr - shift[c]) / scale[c];
     }
   }
   y[idx] = v;
 }
 
-// d x_rec = dy[.., c] / scale[c]; schedule -1: d_a = d x_rec; 0: d_c = -d x_rec; 1: d_c = d_n = -t d x_rec.  One thread per pixel:
+// d x_rec = dy[.., c] / scale[c]; schedule -1: d_a = d x_rec; 0: d_c = -d x_rec; 1: d_c = d_n = -t d x_rec; 2: d_a = [-t^2/2 | -t] d x_rec
+// (six channels), d_n = -sqrt(t) d x_rec.  One thread per pixel:
 // one 16-byte load of the first four channels, three stores that are contiguous across the wave.
 __global__ __launch_bounds__(256) void lpips_input_bwd_kernel(const f32x4* __restrict__ dy, const float* __restrict__ t,
                                                               const float* __restrict__ scale, float* __restrict__ d_a,
@@ -42,6 +48,18 @@ __global__ __launch_bounds__(256) void lpips_input_bwd_kernel(const f32x4* __res
   if (p >= pixels) return;
   const f32x4 g = dy[p * 8];
   const long b = p / HW, hw = p - b * HW;
+  if (schedule == 2) {
+    const float tb = t[b], mk = -(tb * tb / 2.f), ms = -sqrtf(tb);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const long i = (b * 3 + c) * HW + hw, ik = (b * 6 + c) * HW + hw;
+      const float d = g[c] / scale[c];
+      d_a[ik] = mk * d;
+      d_a[ik + 3L * HW] = -tb * d;
+      d_n[i] = ms * d;
+    }
+    return;
+  }
   const float m = schedule < 0 ? 1.f : schedule == 0 ? -1.f : -t[b];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -235,8 +253,8 @@ static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 extern "C" int adm_lpips_input(const float* a, const float* n_pred, const float* x_noisy, const float* t, const float* shift,
                                const float* scale, float* y, int B, int HW, int schedule, hipStream_t stream) {
-  if (!a || !shift || !scale || !y || B <= 0 || HW <= 0 || schedule < -1 || schedule > 1 || !al16(y)) return ADM_EINVAL;
-  if (schedule == 1 && (!n_pred || !x_noisy || !t)) return ADM_EINVAL;
+  if (!a || !shift || !scale || !y || B <= 0 || HW <= 0 || schedule < -1 || schedule > 2 || !al16(y)) return ADM_EINVAL;
+  if (schedule >= 1 && (!n_pred || !x_noisy || !t)) return ADM_EINVAL;
   const long pixels = (long)B * HW;
   hipLaunchKernelGGL(lpips_input_kernel, dim3(adm_cdiv(pixels * 8, 256)), dim3(256), 0, stream, a, n_pred, x_noisy, t, shift,
                      scale, reinterpret_cast<f32x4*>(y), pixels, HW, schedule);
@@ -246,8 +264,8 @@ extern "C" int adm_lpips_input(const float* a, const float* n_pred, const float*
 
 extern "C" int adm_lpips_input_bwd(const float* dy, const float* t, const float* scale, float* d_a, float* d_n, int B, int HW,
                                    int schedule, hipStream_t stream) {
-  if (!dy || !scale || !d_a || B <= 0 || HW <= 0 || schedule < -1 || schedule > 1 || !al16(dy)) return ADM_EINVAL;
-  if (schedule == 1 && (!t || !d_n)) return ADM_EINVAL;
+  if (!dy || !scale || !d_a || B <= 0 || HW <= 0 || schedule < -1 || schedule > 2 || !al16(dy)) return ADM_EINVAL;
+  if (schedule >= 1 && (!t || !d_n)) return ADM_EINVAL;
   const long pixels = (long)B * HW;
   hipLaunchKernelGGL(lpips_input_bwd_kernel, dim3(adm_cdiv(pixels, 256)), dim3(256), 0, stream, reinterpret_cast<const f32x4*>(dy),
                      t, scale, d_a, d_n, pixels, HW, schedule);

@@ -42,6 +42,8 @@ class DDPMBase(nn.Module):
     AUGMENT_P = 0.15            # AugmentPipe probability multiplier: 0.15 in ddm_const.py:179, 0.12 in ddm_const_2.py:112
     SUPPORTS_L1 = False         # use_l1 (L1 twins of the SSE terms) exists in the latent p_losses only (ddm_const_2.py:556-559)
     CLIP_IN_SAMPLER = True      # pixel-space 'const' sampler clamps the predicted x0 (ddm_const.py:453-454); latent ones never do
+    NO_LPIPS_WARNING = ("adm_amd: the LPIPS term (perceptual_weight > 0) needs VGG16 weights that cannot be fetched "
+                        "offline; loss_vlb is 0 (see DESIGN.md)")
 
     def __init__(self, model, *, image_size, sampling_timesteps=None, loss_type="l2", objective="pred_noise",
                  beta_schedule="cosine", clip_x_start=True, input_keys=("image",), start_dist="normal",
@@ -87,8 +89,7 @@ class DDPMBase(nn.Module):
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys, only_model)
         if perceptual_weight > 0 and self.USES_LPIPS and not self.lpips_active:
-            warnings.warn("adm_amd: the LPIPS term (perceptual_weight > 0) needs VGG16 weights that cannot be fetched "
-                          "offline; loss_vlb is 0 (see DESIGN.md)", stacklevel=2)
+            warnings.warn(self.NO_LPIPS_WARNING, stacklevel=2)
 
     # ------------------------------------------------------------------ LPIPS term
     @property
@@ -127,7 +128,7 @@ class DDPMBase(nn.Module):
     # ------------------------------------------------------------------ schedule pieces
     @property
     def _sched(self) -> int:
-        return 0 if self.SCHEDULE == "const" else 1
+        return {"const": 0, "const_2": 1, "linear": 2}[self.SCHEDULE]
 
     def _g(self, t):
         return torch.sqrt(t) if self.SCHEDULE == "const" else t

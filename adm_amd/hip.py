@@ -114,6 +114,11 @@ _SIGS = {
     "adm_ddm_loss_latent": [P, P, P, P, P, P, P, P, P, P, P, F, I, L, I, I, P],
     "adm_sampler_step": [P, P, P, D, D, I, I, D, I, L, P],
     "adm_sampler_step_stochastic": [P, P, P, P, P, P, I, I, D, I, I, L, P],
+    "adm_q_sample_linear": [P, P, P, P, P, I, L, P],
+    "adm_ddm_loss_linear": [P, P, P, P, P, P, P, P, P, P, P, P, I, L, I, P],
+    "adm_sampler_step_linear": [P, P, P, P, P, P, F, I, I, L, P],
+    "adm_nhwc_to_nchw": [P, I, P, I, I, I, P],
+    "adm_nhwc_to_nchw_bwd_amax": [P, P, I, P, I, I, I, P],
     "adm_aug_workspace_floats": [I, I, I, I],
     "adm_augment_geometric": [P, P, P, P, P, P, I, I, I, I, P],
     "adm_conv_wgrad_strided": [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P],

@@ -1900,6 +1900,37 @@ def precond_out(f_nhwc, x_nchw, c_skip, c_out):
     return _PrecondOut.apply(f_nhwc, x_nchw, c_skip, c_out)
 
 
+class _HeadOut(torch.autograd.Function):
+    """NHWC (32-padded) -> NCHW of a head without preconditioning and without a skip term: the K | C head of the linear-drift DDM
+    (six channels).  Unlike _PrecondOut it never sees the network input.  Backward: the zero-padded transpose with the bound of df,
+    so the head conv's data and weight gradients stay on the fp16 format."""
+
+    @staticmethod
+    def forward(ctx, f, C):
+        f = _chk(f, "F")
+        B, H, W, ldf = f.shape
+        out = _new((B, C, H, W), f)
+        call("adm_nhwc_to_nchw", ptr(f), ldf, ptr(out), B, C, H * W)
+        ctx.meta = (ldf, C)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        ldf, C = ctx.meta
+        dout = _chk(dout, "dout")
+        B, _, H, W = dout.shape
+        df = _new((B, H, W, ldf), dout)
+        slot = _amax_slot(dout) if (FP16X3 and BF16X6 and COMPUTE == "f32") else None
+        call("adm_nhwc_to_nchw_bwd_amax", ptr(dout), ptr(df), ldf, ptr(slot), B, C, H * W)
+        _reg_amax(df, slot)
+        return df, None
+
+
+def head_out(f_nhwc, channels: int):
+    """F as NCHW [B,channels,H,W] from the NHWC head output (channels <= 8)."""
+    return _HeadOut.apply(f_nhwc, int(channels))
+
+
 class _AxpbyB(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, x, a, s):
@@ -2082,23 +2113,76 @@ def sampler_step_stochastic(x64, c_pred, n_pred, z64, t64, s64, schedule: int, c
 
 
 # ------------------------------------------------------------------------------------------------
+# linear-drift schedule (ddm/ddm_linear.py; csrc/ddm_linear.hip)
+# ------------------------------------------------------------------------------------------------
+def q_sample_linear(x0, noise, K, t):
+    """x_t = x0 + K t^2/2 + C t + sqrt(t) eps, C = -x0 - K/2; K is clamped to [-1, 1] inside the kernel."""
+    x0, noise, K, t = _chk(x0, "x0"), _chk(noise, "noise"), _chk(K, "K"), _chk(t, "t")
+    B = x0.shape[0]
+    xt = _like(x0)
+    call("adm_q_sample_linear", ptr(x0), ptr(noise), ptr(K), ptr(t), ptr(xt), B, x0.numel() // B)
+    return xt
+
+
+class _DdmLossLinear(torch.autograd.Function):
+    """ddm_linear.DDPM.p_losses without its LPIPS summand: returns (sum_b simple_b / B + sum_b w3_b MAE_b, per-sample simple,
+    per-sample MAE); w = [B][3] = (w1, w2, w3) with w3 = mean_b (1 - t_b)^2 / B."""
+
+    @staticmethod
+    def forward(ctx, theta_pred, n_pred, x0, noise, K, xt, t, w, use_l1):
+        theta_pred, n_pred = _chk(theta_pred, "theta_pred"), _chk(n_pred, "noise_pred")
+        B = n_pred.shape[0]
+        n3 = n_pred.numel() // B
+        if theta_pred.numel() != 2 * B * n3:
+            raise RuntimeError(f"theta_pred {tuple(theta_pred.shape)} must hold K_pred | C_pred of noise_pred {tuple(n_pred.shape)}")
+        per, mae = _new((B,), n_pred), _new((B,), n_pred)
+        dth, dn = _like(theta_pred), _like(n_pred)
+        call("adm_ddm_loss_linear", ptr(theta_pred), ptr(n_pred), ptr(x0), ptr(noise), ptr(K), ptr(xt), ptr(t), ptr(w), ptr(per),
+             ptr(mae), ptr(dth), ptr(dn), B, n3, int(use_l1))
+        ctx.save_for_backward(dth, dn)
+        ctx.mark_non_differentiable(per, mae)
+        return per.sum() / B + (mae * w[:, 2]).sum(), per, mae
+
+    @staticmethod
+    def backward(ctx, gloss, _gper, _gmae):
+        dth, dn = ctx.saved_tensors
+        return dth * gloss, dn * gloss, None, None, None, None, None, None, None
+
+
+def ddm_loss_linear(theta_pred, n_pred, x0, noise, K, xt, t, w, use_l1: bool = False):
+    return _DdmLossLinear.apply(theta_pred, n_pred, _chk(x0, "x0"), _chk(noise, "noise"), _chk(K, "K"), _chk(xt, "x_t"),
+                                _chk(t, "t"), _chk(w, "weights"), bool(use_l1))
+
+
+def sampler_step_linear(x32, theta_pred, n_pred, z32, t32, s32, scale_input: float, last: bool):
+    """In-place reverse step of the linear-drift sampler on the fp32 state (per-image t, s as fp32 device vectors)."""
+    B = x32.shape[0]
+    if not x32.is_contiguous():
+        raise RuntimeError("adm_amd: the sampler state is updated in place and must be contiguous")
+    call("adm_sampler_step_linear", ptr(_chk(x32, "x")), ptr(_chk(theta_pred, "theta_pred")), ptr(_chk(n_pred, "noise")),
+         ptr(_chk(z32, "z")), ptr(_chk(t32, "t")), ptr(_chk(s32, "s")), float(scale_input), int(last), B, x32.numel() // B)
+    return x32
+
+
+# ------------------------------------------------------------------------------------------------
 # LPIPS branch of the pixel-space loss (csrc/lpips.hip; the VGG16 convolutions themselves are conv2d)
 # ------------------------------------------------------------------------------------------------
 class _LpipsInput(torch.autograd.Function):
     """(x_rec - shift) / scale as NHWC with 32 channels, x_rec formed from the predictions in the same kernel:
-    schedule -1 = `a` is the image itself, 0 = -C_pred, 1 = x_noisy - C_pred t - t noise_pred."""
+    schedule -1 = `a` is the image itself, 0 = -C_pred, 1 = x_noisy - C_pred t - t noise_pred, 2 = the linear-drift schedule with
+    a = theta_pred (six channels): x_noisy - K_pred t^2/2 - C_pred t - sqrt(t) noise_pred."""
 
     @staticmethod
     def forward(ctx, a, n_pred, x_noisy, t, shift, scale, schedule):
         a = _chk(a, "C_pred" if schedule >= 0 else "image")
         B, C, H, W = a.shape
-        if C != 3:
-            raise NotImplementedError("the LPIPS input has three channels")
-        if schedule == 1:
+        if C != (6 if schedule == 2 else 3):
+            raise NotImplementedError("the LPIPS input has three channels (theta_pred of the linear schedule: six)")
+        if schedule >= 1:
             n_pred, x_noisy, t = _chk(n_pred, "noise_pred"), _chk(x_noisy, "x_noisy"), _chk(t, "t")
         y = _new((B, H, W, 32), a)
         call("adm_lpips_input", ptr(a), ptr(n_pred), ptr(x_noisy), ptr(t), ptr(shift), ptr(scale), ptr(y), B, H * W, schedule)
-        ctx.save_for_backward(t if schedule == 1 else None, scale)
+        ctx.save_for_backward(t if schedule >= 1 else None, scale)
         ctx.meta = (tuple(a.shape), schedule)
         return y
 
@@ -2108,18 +2192,19 @@ class _LpipsInput(torch.autograd.Function):
         (B, C, H, W), schedule = ctx.meta
         dy = _chk(dy, "dy")
         da = _new((B, C, H, W), dy)
-        dn = _new((B, C, H, W), dy) if schedule == 1 else None
+        dn = _new((B, 3, H, W), dy) if schedule >= 1 else None
         call("adm_lpips_input_bwd", ptr(dy), ptr(t), ptr(scale), ptr(da), ptr(dn), B, H * W, schedule)
         return da, dn, None, None, None, None, None
 
 
 def lpips_input(a, n_pred, x_noisy, t, shift, scale, schedule: int):
     """The LPIPS network's input [B,H,W,32] from NCHW tensors: schedule -1 takes the image `a`; 0 ('const') and 1 ('const_2')
-    take a = C_pred and rebuild x_rec (ddm_const.py:326 / ddm_const_2.py:217).  Differentiable in a and, for const_2, n_pred."""
-    if schedule not in (-1, 0, 1):
+    take a = C_pred and rebuild x_rec (ddm_const.py:326 / ddm_const_2.py:217); 2 ('linear') takes a = theta_pred [B,6,H,W]
+    (ddm_linear.py:173-176).  Differentiable in a and, for const_2 and linear, n_pred."""
+    if schedule not in (-1, 0, 1, 2):
         raise ValueError(schedule)
     shift, scale = _chk(shift.reshape(-1), "shift"), _chk(scale.reshape(-1), "scale")
-    if schedule != 1:
+    if schedule < 1:
         n_pred = x_noisy = t = None
     return _LpipsInput.apply(a, n_pred, x_noisy, t, shift, scale, int(schedule))
 

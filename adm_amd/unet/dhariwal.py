@@ -189,13 +189,17 @@ class DhariwalUNet(nn.Module):
         super().__init__()
         if label_dim:
             raise NotImplementedError("class-conditional labels are not on the DDM hot path")
-        if out_mul != 1:
-            raise NotImplementedError("out_mul != 1 (ddm_linear) is out of scope")
+        if out_mul != 1 and variant not in ("uncond_unet", "uncond_unet_2"):
+            raise NotImplementedError(f"out_mul={out_mul} needs a two-decoder variant (uncond_unet, uncond_unet_2): the single-decoder "
+                                      f"variant {variant!r} derives D_y from a three-channel D_x")
+        if out_mul < 1 or out_channels * out_mul > 8:
+            raise NotImplementedError(f"out_mul={out_mul}: the head kernels take up to 8 output channels")
         if any((model_channels * m) % 32 for m in channel_mult):
             raise NotImplementedError("channel widths must be multiples of 32 (the HIP GEMM operands' channel granularity); "
                                       f"got model_channels={model_channels}, channel_mult={list(channel_mult)}")
         self.variant = variant
         self.two_decoders = variant in ("uncond_unet", "uncond_unet_2")
+        self.out_mul = out_mul              # ddm_linear: out_conv predicts theta = [K | C] (out_channels * 2); out_conv2 stays the noise head
         self.label_dropout = label_dropout
         self.in_channels_pad = ops.ceil32(in_channels)
         emb_channels = model_channels * channel_mult_emb
@@ -333,6 +337,10 @@ class EDMPrecond(nn.Module):
         self.label_dim, self.use_fp16 = label_dim, use_fp16
         self.sigma_min, self.sigma_max, self.sigma_data = sigma_min, sigma_max, sigma_data
         model_kwargs.pop("cfg", None)                 # sample_uncond.py:47-49 passes cfg= through
+        if model_kwargs.get("out_mul", 1) != 1 and precondition:
+            # the reference's own combination fails in its forward: c_skip1 * x [B,3,H,W] + c_out1 * F_x [B,6,H,W] (uncond_unet.py:630-632)
+            raise NotImplementedError(f"out_mul={model_kwargs['out_mul']} needs `precondition: False`: with preconditioning D_x would add the "
+                                      f"{img_channels}-channel input to a {img_channels * model_kwargs['out_mul']}-channel output")
         self.model = DhariwalUNet(img_resolution=img_resolution, in_channels=img_channels, out_channels=img_channels,
                                   label_dim=label_dim, variant=self.VARIANT, **model_kwargs)
 
@@ -365,7 +373,9 @@ class EDMPrecond(nn.Module):
         x = x.contiguous()
         f_x, f_y = self.model(xin, c_noise, None, augment_labels=aug)
         one, zero = torch.ones_like(sigma), torch.zeros_like(sigma)
-        if self.precondition:
+        if self.model.out_mul != 1:        # theta = F_x as it is (precondition: False, :633-634): no skip term, x is not read
+            d_x = ops.head_out(f_x, self.img_channels * self.model.out_mul)
+        elif self.precondition:
             d_x = ops.precond_out(f_x, x, c_skip1, c_out1)
         else:
             d_x = ops.precond_out(f_x, x, zero, one)

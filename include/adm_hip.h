@@ -444,6 +444,32 @@ int adm_sampler_step_stochastic(double* x, const float* c_pred, const float* n_p
                                 const double* s, int schedule, int clip_x0, double scale_input, int last, int B, long n,
                                 hipStream_t stream);
 
+/* ---------------- linear-drift schedule (ddm/ddm_linear.py): U(t) = K t^2/2 + C t, C = -x0 - K/2 ---------------- */
+
+/* x_t = x0 + K t^2/2 + C t + sqrt(t) eps with K clamped to [-1, 1] on read and C = -x0 - K/2 (ddm_linear.py:168-171, 198-200).
+ * NCHW, n3 floats per image; t [B]. */
+int adm_q_sample_linear(const float* x0, const float* noise, const float* K, const float* t, float* xt, int B, long n3,
+                        hipStream_t stream);
+/* DDPM.p_losses of ddm_linear.py:201-240 without its LPIPS summand, forward and both gradients in one launch.  theta_pred
+ * [B][2 n3] = (K_pred | C_pred), the other tensors [B][n3]; K is clamped to [-1, 1] on read; w = [B][3] = (w1, w2, w3).
+ * per_simple[b] = w1 mean (theta_pred - [K | C])^2 + w2 mean (n_pred - noise)^2, with use_l1 the mean-|.| twins added and the sum halved;
+ * per_mae[b] = mean |x_rec - x0|, x_rec = xt - K_pred t^2/2 - C_pred t - sqrt(t) n_pred.
+ * d_theta, d_n (both or neither) = gradients of  sum_b per_simple[b] / B + sum_b w3[b] per_mae[b]. */
+int adm_ddm_loss_linear(const float* theta_pred, const float* n_pred, const float* x0, const float* noise, const float* K,
+                        const float* xt, const float* t, const float* w, float* per_simple, float* per_mae, float* d_theta,
+                        float* d_n, int B, long n3, int use_l1, hipStream_t stream);
+/* One reverse step on the fp32 state (ddm_linear.py:178-186, 299-304), per-image t[B], s[B], z = the N(0,1) draw:
+ * K = clamp(K_pred, -1, 1); x <- x + K s^2/2 - K t s - C_pred s - s / sqrt(t) n_pred + sqrt(s (t - s) / t) z.
+ * last: clamp to +-scale_input, / scale_input, (x + 1) / 2. */
+int adm_sampler_step_linear(float* x, const float* theta_pred, const float* n_pred, const float* z, const float* t,
+                            const float* s, float scale_input, int last, int B, long n3, hipStream_t stream);
+/* out_nchw[b,c,p] = f_nhwc[b,p,c] for a head of C <= 8 channels (the K | C head without preconditioning: no skip term, so the
+ * network input is not read); ldf % 4 == 0, ldf >= 8. */
+int adm_nhwc_to_nchw(const float* f, int ldf, float* out, int B, int C, int HW, hipStream_t stream);
+/* its adjoint: df_nhwc[b,p,c<C] = dout_nchw[b,c,p], zero for c >= C; amax (may be NULL) is raised to max |df| (the head conv's
+ * gradients then run on the fp16 format). */
+int adm_nhwc_to_nchw_bwd_amax(const float* dout, float* df, int ldf, float* amax, int B, int C, int HW, hipStream_t stream);
+
 /* ---------------- augmentation of x_start (use_augment: True) ------------------------------- */
 
 /* Execution half of AugmentPipe for the transforms DDM enables (/root/reference/ddm/augment.py:161-172, 236-276;
@@ -553,10 +579,12 @@ int adm_linattn_bwd(const float* qkv, const float* dout, const float* ctx, const
 
 /* y[B][HW][32] = (x_rec - shift) / scale in channels 0..2, zero in 3..31 (ScalingLayer, lpips.py:56-63, fused with the layout change).
  * schedule -1: x_rec = a (an image, e.g. the target x_start); 0 'const': x_rec = -a with a = C_pred (ddm_const.py:326);
- * 1 'const_2': x_rec = x_noisy - a t - t n_pred (ddm_const_2.py:217), t [B].  a, n_pred, x_noisy are NCHW [B][3][HW]; shift, scale: 3 floats. */
+ * 1 'const_2': x_rec = x_noisy - a t - t n_pred (ddm_const_2.py:217), t [B].  a, n_pred, x_noisy are NCHW [B][3][HW]; shift, scale: 3 floats.
+ * 2 'linear': a = theta_pred [B][6][HW] = (K_pred | C_pred), x_rec = x_noisy - K_pred t^2/2 - C_pred t - sqrt(t) n_pred (ddm_linear.py:173-176). */
 int adm_lpips_input(const float* a, const float* n_pred, const float* x_noisy, const float* t, const float* shift,
                     const float* scale, float* y, int B, int HW, int schedule, hipStream_t stream);
-/* its adjoint: d_a (and, schedule 1, d_n) in NCHW from dy [B][HW][32]. */
+/* its adjoint: d_a (and, schedules 1 and 2, d_n) in NCHW from dy [B][HW][32]; schedule 2: d_a has six channels (-t^2/2 | -t) d x_rec,
+ * d_n = -sqrt(t) d x_rec. */
 int adm_lpips_input_bwd(const float* dy, const float* t, const float* scale, float* d_a, float* d_n, int B, int HW,
                         int schedule, hipStream_t stream);
 
