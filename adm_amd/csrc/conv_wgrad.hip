@@ -26,6 +26,7 @@ namespace {
 struct WgradP {
   const float* x; const float* dy; float* dwp;
   int P, H, W, Hin, Win, Cin, ldx, Cout, lddy, ks, up, tilesN, chunk, atomic, lw, lh, xbytes, dybytes;
+  int same;                // x and dy live on one H x W grid (every conv but the strided / shrinking ones)
   int stride, pad_lo;      // generic path: tap (ky, kx) of output (oy, ox) reads input (oy*stride + ky - pad_lo, ox*stride + kx - pad_lo)
   float* dbias;      // optional: dbias[co] += sum_p dY[p][co] (the conv's bias gradient), by the tap-0 / ci-tile-0 workgroups
   // deterministic mode (split_stride > 0): split z stores its partial tile at dwp + z * split_stride and its bias partial at
@@ -243,7 +244,7 @@ template <int TM, int TN>
 int launch_wgrad(WgradP p, int splits, hipStream_t st) {
   p.tilesN = adm_cdiv(p.Cin, TN);
   dim3 grid(adm_cdiv(p.Cout, TM) * p.tilesN, p.ks * p.ks, splits);
-  const bool fast = p.lw >= 0 && p.W <= 32 && !p.up && p.stride == 1;       // see load_stage
+  const bool fast = p.lw >= 0 && p.W <= 32 && !p.up && p.stride == 1 && p.same;       // see load_stage
   if (fast) hipLaunchKernelGGL((wgrad_f32_kernel<TM, TN, true>), grid, dim3(256), 0, st, p);
   else hipLaunchKernelGGL((wgrad_f32_kernel<TM, TN, false>), grid, dim3(256), 0, st, p);
   ADM_CHECK_LAUNCH();
@@ -269,7 +270,10 @@ int wgrad_impl(const float* x, const float* dy, float* dwp, float* dbias, int B,
   p.P = B * H * W; p.H = H; p.W = W; p.Hin = up ? H / 2 : (Hin > 0 ? Hin : H); p.Win = up ? W / 2 : (Win > 0 ? Win : W);
   p.Cin = Cin; p.ldx = ldx; p.Cout = Cout; p.lddy = lddy; p.ks = ks; p.up = up; p.tilesN = 0;
   p.split_stride = split_stride; p.bias_stride = bias_stride; p.stride = stride; p.pad_lo = pad_lo;
-  if (stride == 1 && (p.Hin != (up ? H / 2 : H) || p.Win != (up ? W / 2 : W))) return ADM_EINVAL;
+  // a stride-1 conv whose output is smaller than its input (4x4, pad 1: the PatchGAN discriminator's last two layers) takes the
+  // generic tap path, like the strided ones; the power-of-two fast path assumes one grid for x and dy
+  p.same = p.Hin == (up ? H / 2 : H) && p.Win == (up ? W / 2 : W);
+  if (up && !p.same) return ADM_EINVAL;
   const long xb = (long)B * p.Hin * p.Win * ldx * 4, db = (long)p.P * lddy * 4;
   if (xb >= (1L << 31) || db >= (1L << 31)) return ADM_EINVAL;      // 32-bit buffer offsets
   p.xbytes = (int)xb; p.dybytes = (int)db;
@@ -350,4 +354,17 @@ extern "C" int adm_conv_wgrad_strided(const float* x, const float* dy, float* dw
   if (Hin <= 0 || Win <= 0 || pad_lo < 0 || pad_lo >= ks) return ADM_EINVAL;
   if ((long)(Hout - 1) * stride - pad_lo >= Hin || (long)(Wout - 1) * stride - pad_lo >= Win) return ADM_EINVAL;
   return wgrad_impl(x, dy, dwp, dbias, B, Hout, Wout, Cin, ldx, Cout, lddy, ks, 0, 0, 0, 0, false, stream, stride, pad_lo, Hin, Win);
+}
+
+// adm_conv_wgrad_strided in the deterministic workspace form of adm_conv_wgrad_ws: split z stores its partial tile at
+// ws + z * Cout * ks * ks * Cin (bias partial at bws + z * Cout); adm_unpack_wgrad_splits sums them in split order.
+// splits = adm_conv_wgrad_plan(B, Hout, Wout, Cin, Cout, ks, 0, 0).
+extern "C" int adm_conv_wgrad_strided_ws(const float* x, const float* dy, float* ws, float* bws, int B, int Hin, int Win, int Hout,
+                                         int Wout, int Cin, int ldx, int Cout, int lddy, int ks, int stride, int pad_lo, int splits,
+                                         hipStream_t stream) {
+  if (splits < 1 || !ws) return ADM_EINVAL;
+  if (Hin <= 0 || Win <= 0 || pad_lo < 0 || pad_lo >= ks) return ADM_EINVAL;
+  if ((long)(Hout - 1) * stride - pad_lo >= Hin || (long)(Wout - 1) * stride - pad_lo >= Win) return ADM_EINVAL;
+  return wgrad_impl(x, dy, ws, bws, B, Hout, Wout, Cin, ldx, Cout, lddy, ks, 0, splits, (long)Cout * ks * ks * Cin, Cout, false, stream,
+                    stride, pad_lo, Hin, Win);
 }

@@ -1,4 +1,5 @@
-"""KL autoencoder ("first stage", KL-f4 for the CelebA-HQ latent configs) on the HIP hot path -- inference only.
+"""KL autoencoder ("first stage", KL-f4 for the CelebA-HQ latent configs) on the HIP hot path: inference by default, training
+after ``AutoencoderKL.enable_training()`` (see the end of this note).
 
 Mirror of the part of /root/reference/ddm/encoder_decoder.py that ``ddm_const_2.LatentDiffusion`` uses:
 ``AutoencoderKL(ddconfig, lossconfig, embed_dim, ckpt_path=...)`` with ``.encode(x) -> DiagonalGaussianDistribution``,
@@ -16,7 +17,15 @@ called.  All arithmetic runs through adm_amd.ops on NHWC fp32 buffers:
                          (scores [L, L] live in HBM: 64 MB at L = 4096), adm_softmax_rows in between; V is produced
                          already transposed ([C, L] = W_v h^T) and its bias added after PV (softmax rows sum to 1)
   posterior sample       adm_posterior_sample
-The first stage is frozen (ddm_const_2.py:436-440): everything here is forward-only and must run under no_grad.
+The first stage is frozen (ddm_const_2.py:436-440): without ``enable_training()`` everything here is forward-only and must run
+under no_grad.
+
+Training (the reference's train_vae.py / AutoencoderKL.training_step, encoder_decoder.py:978-1011) is opt-in:
+``enable_training(lpips=None)`` builds ``self.loss`` (ddm/loss.py LPIPSWithDiscriminator) from the stored ``lossconfig`` and
+switches Downsample and the attention block to their differentiable operators (adm_amd.ops_ae: the strided conv with its
+weight / data gradients, the single-head attention core that recomputes the [L, L] probabilities in its backward, posterior
+sample + KL).  ``training_step`` runs forward AND backward: the generator step needs the gradient at the reconstruction twice
+(NLL and GAN term) before the adaptive weight is known, so it cannot be a single graph loss (see ddm/loss.py).
 """
 from __future__ import annotations
 
@@ -25,7 +34,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import ops, ops_ae
 
 _CHUNK_BYTES = 1 << 30     # activations of one pass stay below 1 GiB (32-bit buffer offsets need < 2 GiB)
 
@@ -61,8 +70,11 @@ class Downsample(nn.Module):
             raise NotImplementedError("resamp_with_conv=False is not used by any DDM config")
         self.with_conv = with_conv
         self.conv = nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=2, padding=0)
+        self.trainable = False                        # set by AutoencoderKL.enable_training()
 
     def forward(self, x):
+        if self.trainable and torch.is_grad_enabled():
+            return ops_ae.conv2d_down(x, self.conv.weight, self.conv.bias, stride=2, pad_lo=0, pad_hi=1)
         return ops.conv2d_strided(x, self.conv.weight, self.conv.bias, stride=2, pad_lo=0, pad_hi=1)
 
 
@@ -76,13 +88,15 @@ class ResnetBlock(nn.Module):
         self.norm1 = Normalize(in_channels)
         self.conv1 = nn.Conv2d(in_channels, out_channels, kernel_size=3, stride=1, padding=1)
         self.norm2 = Normalize(out_channels)
-        self.dropout = nn.Dropout(dropout)            # inactive: the first stage always runs in eval mode
+        self.dropout = nn.Dropout(dropout)            # inactive: every recipe has dropout 0.0 (enable_training() raises otherwise)
         self.conv2 = nn.Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1)
         if in_channels != out_channels:
             self.nin_shortcut = nn.Conv2d(in_channels, out_channels, kernel_size=1, stride=1, padding=0)
 
     def forward(self, x, temb=None):
+        x, xs = ops.fanout(x, 2)                      # the conv branch and the skip (one summing launch in the backward)
         h = _conv(self.conv1, _gn(self.norm1, x, True))
+        x = xs
         h = _gn(self.norm2, h, True)
         if self.in_channels != self.out_channels:
             x = _conv(self.nin_shortcut, x)
@@ -98,12 +112,25 @@ class AttnBlock(nn.Module):
         self.k = nn.Conv2d(in_channels, in_channels, kernel_size=1)
         self.v = nn.Conv2d(in_channels, in_channels, kernel_size=1)
         self.proj_out = nn.Conv2d(in_channels, in_channels, kernel_size=1)
+        self.trainable = False                        # set by AutoencoderKL.enable_training()
+
+    def _forward_train(self, x):
+        """The same block with a graph: q, k, v from three 1x1 convs, the differentiable attention core, proj_out + x."""
+        B, H, W, C = x.shape
+        L = H * W
+        x, xres = ops.fanout(x, 2)
+        hq, hk, hv = ops.fanout(_gn(self.norm, x, False), 3)
+        q, k, v = (_conv(m, h).reshape(B, L, C) for m, h in ((self.q, hq), (self.k, hk), (self.v, hv)))
+        o = ops_ae.attention_single_head(q, k, v)
+        return _conv(self.proj_out, o.reshape(B, H, W, C), residual=xres)
 
     def forward(self, x):
         B, H, W, C = x.shape
         L = H * W
         if C % 32 or L % 32:
             raise RuntimeError(f"AttnBlock needs C ({C}) and H*W ({L}) to be multiples of 32")
+        if self.trainable and torch.is_grad_enabled():
+            return self._forward_train(x)
         h = _gn(self.norm, x, False)
         q = _conv(self.q, h).reshape(B, L, C)
         k = _conv(self.k, h).reshape(B, L, C)
@@ -219,8 +246,9 @@ class Decoder(nn.Module):
         self.norm_out = Normalize(block_in)
         self.conv_out = nn.Conv2d(block_in, out_ch, kernel_size=3, stride=1, padding=1)
 
-    def forward(self, z):
-        """z: NHWC fp32 [B, h, w, ceil32(z_channels)] -> NHWC [B, h f, w f, ceil32(out_ch)]."""
+    def forward(self, z, return_last=False):
+        """z: NHWC fp32 [B, h, w, ceil32(z_channels)] -> NHWC [B, h f, w f, ceil32(out_ch)]; return_last: also the input of
+        conv_out (the generator step runs that layer's weight-gradient kernel on it)."""
         h = _conv(self.conv_in, z)
         h = self.mid.block_1(h)
         h = self.mid.attn_1(h)
@@ -232,7 +260,9 @@ class Decoder(nn.Module):
                     h = self.up[i_level].attn[i_block](h)
             if i_level != 0:
                 h = self.up[i_level].upsample(h)
-        return _conv(self.conv_out, _gn(self.norm_out, h, True))
+        h = _gn(self.norm_out, h, True)
+        y = _conv(self.conv_out, h)
+        return (y, h.detach()) if return_last else y
 
 
 class DiagonalGaussianDistribution(object):
@@ -296,8 +326,10 @@ class AutoencoderKL(nn.Module):
         self.encoder = Encoder(**ddconfig)
         self.decoder = Decoder(**ddconfig)
         self.down_ratio = 2 ** (len(ddconfig["ch_mult"]) - 1)
-        # `lossconfig` (LPIPSWithDiscriminator) only matters for autoencoder TRAINING, which is out of scope; its
-        # `loss.*` checkpoint entries are skipped on load.
+        # `lossconfig` (LPIPSWithDiscriminator) only matters for autoencoder TRAINING: it is kept for enable_training(); until
+        # then there is no `loss` submodule and `loss.*` checkpoint entries are skipped on load.
+        self.lossconfig = None if lossconfig is None else dict(lossconfig)
+        self.loss = None
         assert ddconfig["double_z"]
         self.z_channels = ddconfig["z_channels"]
         self.quant_conv = nn.Conv2d(2 * ddconfig["z_channels"], 2 * embed_dim, 1)
@@ -321,8 +353,12 @@ class AutoencoderKL(nn.Module):
             sd = sd["state_dict"]
         else:
             raise ValueError("checkpoint has none of 'ema', 'model', 'state_dict'")
+        lp = "loss.perceptual_loss."
+        if self.loss is not None and self.loss.perceptual_loss is None and any(k.startswith(lp) for k in sd):
+            from .lpips import LPIPS
+            self.loss.set_perceptual_loss(LPIPS.from_state_dict({k[len("loss."):]: v for k, v in sd.items() if k.startswith(lp)}))
         for k in list(sd.keys()):
-            if k.startswith("loss.") or any(k.startswith(ik) for ik in ignore_keys):
+            if (k.startswith("loss.") and self.loss is None) or any(k.startswith(ik) for ik in ignore_keys):
                 del sd[k]
         msg = self.load_state_dict(sd, strict=False)
         print(f"Restored from {path}")
@@ -364,3 +400,102 @@ class AutoencoderKL(nn.Module):
         posterior = self.encode(input)
         z = posterior.sample() if sample_posterior else posterior.mode()
         return self.decode(z), posterior
+
+    # --------------------------------------------------------------------------------------------- training (opt-in)
+    def enable_training(self, lpips=None):
+        """Builds ``self.loss`` (LPIPSWithDiscriminator) from the lossconfig given at construction and switches the strided conv and
+        the attention block to their differentiable operators.  ``lpips``: an adm_amd.ddm.lpips.LPIPS to use as the perceptual
+        term (otherwise a checkpoint's ``loss.perceptual_loss.*`` keys or the lossconfig's ``lpips_ckpt`` provide it; without
+        weights the term is zero, with a warning).  After this the state dict carries ``loss.logvar`` and
+        ``loss.discriminator.main.*`` as the reference's does."""
+        from .loss import LPIPSWithDiscriminator
+        if self.lossconfig is None:
+            raise ValueError("enable_training() needs the lossconfig the autoencoder was constructed with")
+        for m in self.modules():
+            if isinstance(m, nn.Dropout) and m.p > 0:
+                raise NotImplementedError(f"dropout {m.p} in the autoencoder's ResnetBlocks is not implemented for training "
+                                          "(every recipe has dropout: 0.0)")
+        if self.loss is None:
+            dev = self.quant_conv.weight.device
+            self.loss = LPIPSWithDiscriminator(**self.lossconfig).to(dev)
+        if lpips is not None:
+            self.loss.set_perceptual_loss(lpips)
+        for m in self.modules():
+            if isinstance(m, (Downsample, AttnBlock)):
+                m.trainable = True
+        return self
+
+    def get_last_layer(self):
+        return self.decoder.conv_out.weight
+
+    def _check_train_shapes(self, B, C, H, W):
+        if self.loss is None:
+            raise RuntimeError("AutoencoderKL.enable_training() has not been called: this autoencoder is inference-only")
+        if ops.COMPUTE != "f32":
+            raise NotImplementedError("the autoencoder trains in the f32 compute mode only (bf16 mode is not implemented)")
+        if H % 16 or W % 16:
+            raise NotImplementedError(f"autoencoder training needs H and W that are multiples of 16, got {H}x{W}")
+        # one pass, not chunked: every activation (and the [L, L] attention scores) must stay below the 32-bit offset limit
+        enc = self.encoder
+        widest = max((H >> l) * (W >> l) * enc.ch * max(enc.in_ch_mult[l], enc.in_ch_mult[l + 1], 1)
+                     for l in range(enc.num_resolutions))
+        L = (H // self.down_ratio) * (W // self.down_ratio)
+        if B * max(widest, H * W * 32) * 4 >= 2 * _CHUNK_BYTES or L * L * 4 >= 2 * _CHUNK_BYTES:
+            raise NotImplementedError(f"a training batch of {B} x {H}x{W} needs a tensor beyond the 32-bit offset limit (2 GiB); "
+                                      "use a smaller batch")
+
+    def _forward_train(self, x, eps=None):
+        """One un-chunked pass with a graph: NHWC reconstruction (32-padded), its detached last-layer input, moments, z, kl [B]."""
+        B, C, H, W = x.shape
+        self._check_train_shapes(B, C, H, W)
+        moments = _conv(self.quant_conv, self.encoder(ops.nchw_to_nhwc(x, None, ops.ceil32(C))))
+        h, w = moments.shape[1], moments.shape[2]
+        if eps is None:
+            e = torch.randn((B, h, w, self.embed_dim), device=x.device, dtype=torch.float32)
+        else:
+            e = eps.to(device=x.device, dtype=torch.float32).permute(0, 2, 3, 1).contiguous()
+        z, kl = ops_ae.posterior_sample_kl(moments, self.embed_dim, e)
+        y, h_last = self.decoder(_conv(self.post_quant_conv, z), return_last=True)
+        return y, h_last, kl
+
+    def training_step(self, inputs, optimizer_idx, global_step, eps=None, loss_scale=1.0, backward=True, split="train"):
+        """One micro-step of the reference's AutoencoderKL.training_step, forward AND backward: gradients (times ``loss_scale``, the
+        1 / gradient_accumulate_every of the driver) are accumulated into ``.grad`` of the parameters that ``optimizer_idx`` trains
+        -- 0: encoder, decoder, the quant convs and loss.logvar; 1: the discriminator -- and of no others.  Returns
+        ``(loss, log)`` as detached device tensors; nothing is copied to the host.  ``eps`` [B, embed_dim, h, w] injects the
+        posterior's draw."""
+        inputs = inputs.to(torch.float32).contiguous()
+        out_ch = self.decoder.conv_out.out_channels
+        if optimizer_idx == 1:
+            with torch.no_grad():
+                y, _, _ = self._forward_train(inputs, eps)
+                rec = ops.head_out(y, out_ch)
+            with torch.set_grad_enabled(backward):
+                d_loss, log = self.loss(inputs, rec, None, 1, global_step, last_layer=self.get_last_layer(), split=split)
+                if backward:
+                    (d_loss * loss_scale).backward()
+            return d_loss.detach(), log
+        if optimizer_idx != 0:
+            raise ValueError(f"optimizer_idx {optimizer_idx}")
+        B = inputs.shape[0]
+        with torch.set_grad_enabled(backward):
+            y, h_last, kl = self._forward_train(inputs, eps)
+            rec = ops.head_out(y, out_ch)
+        from .loss import TrainingPosterior
+        post = TrainingPosterior(kl, h_last, self.decoder.conv_out)
+        loss, log = self.loss(inputs, rec, post, 0, global_step, last_layer=self.get_last_layer(), split=split)
+        g, dlogvar = post.g, post.dlogvar
+        if backward:
+            gkl = torch.full((B,), float(self.loss.kl_weight) * float(loss_scale) / B, device=inputs.device, dtype=torch.float32)
+            torch.autograd.backward([rec, kl], [g if loss_scale == 1.0 else g * float(loss_scale), gkl])
+            lv = self.loss.logvar
+            if lv.requires_grad:
+                dl = (dlogvar * float(loss_scale)).reshape(lv.shape)
+                lv.grad = dl if lv.grad is None else lv.grad + dl
+        return loss.detach(), log
+
+    def validation_step(self, inputs, global_step, eps=None):
+        """Both logs without touching any gradient (the reference's validation_step); BatchNorm follows the module's mode."""
+        _, log_ae = self.training_step(inputs, 0, global_step, eps=eps, backward=False, split="val")
+        _, log_disc = self.training_step(inputs, 1, global_step, eps=eps, backward=False, split="val")
+        return log_ae, log_disc

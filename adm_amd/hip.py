@@ -122,6 +122,7 @@ _SIGS = {
     "adm_aug_workspace_floats": [I, I, I, I],
     "adm_augment_geometric": [P, P, P, P, P, P, I, I, I, I, P],
     "adm_conv_wgrad_strided": [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, P],
+    "adm_conv_wgrad_strided_ws": [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, P],
     "adm_pack_weight_tconv": [P, P, I, I, I, I, I, P],
     "adm_col2im": [P, P, I, I, I, I, I, I, I, I, I, P],
     "adm_ws_fwd": [P, P, P, I, I, F, P],
@@ -154,6 +155,19 @@ _SIGS = {
     "adm_lpips_head_blocks": [I],
     "adm_lpips_head_fwd": [P, P, P, P, P, I, I, I, I, P],
     "adm_lpips_head_bwd": [P, P, P, P, P, I, I, I, P],
+    "adm_ae_blocks": [L],
+    "adm_posterior_kl_fwd": [P, I, P, P, I, P, P, I, L, I, P],
+    "adm_posterior_kl_bwd": [P, I, P, P, I, P, P, I, L, I, P],
+    "adm_ae_nll_fwd": [P, P, P, P, P, P, I, L, F, P],
+    "adm_ae_nll_bwd": [P, P, P, F, P, L, P],
+    "adm_logit_terms_fwd": [P, I, P, P, L, P],
+    "adm_logit_terms_bwd": [P, I, I, P, F, P, L, P],
+    "adm_leaky_relu_fwd": [P, P, L, F, P],
+    "adm_leaky_relu_bwd": [P, P, P, L, F, P],
+    "adm_softmax_rows_bwd": [P, P, L, I, L, F, P],
+    "adm_transpose2d": [P, P, I, I, P],
+    "adm_adaptive_weight": [P, L, P, L, P, F, P, P],
+    "adm_axpy_dev": [P, P, P, F, P, L, P],
 }
 EXPORTS = tuple(_SIGS)
 
@@ -195,7 +209,7 @@ def ptr(t) -> c_void_p:
 
 
 NO_STREAM = ("adm_version", "adm_conv_splitk", "adm_gn_splits", "adm_aug_workspace_floats", "adm_conv_wgrad_plan",
-             "adm_sumsq_blocks", "adm_lnc_blocks", "adm_bn_blocks", "adm_linattn_ws_floats", "adm_wino2d_splitk", "adm_wino2d_x6_splitk", "adm_wino2d_variant", "adm_wino2d_h3_wide", "adm_wgrad_h3_blocks", "adm_gn_fused", "adm_conv_wgrad_x6_plan", "adm_gemm_wgrad_x6_plan", "adm_lpips_head_blocks")      # host-side queries: no stream argument, called as lib().name(...)
+             "adm_sumsq_blocks", "adm_lnc_blocks", "adm_bn_blocks", "adm_linattn_ws_floats", "adm_wino2d_splitk", "adm_wino2d_x6_splitk", "adm_wino2d_variant", "adm_wino2d_h3_wide", "adm_wgrad_h3_blocks", "adm_gn_fused", "adm_conv_wgrad_x6_plan", "adm_gemm_wgrad_x6_plan", "adm_lpips_head_blocks", "adm_ae_blocks")      # host-side queries: no stream argument, called as lib().name(...)
 
 
 def call(name: str, *args):

@@ -502,10 +502,14 @@ int adm_adamw_step(float* p, const float* g, float* m, float* v, float* ema, con
  * ================================================================================================ */
 
 /* adm_conv_wgrad for a strided conv with explicit top/left padding (Downsample = Conv2d(C, C', 4, 2, 1), cond_unet_sd.py:341-342;
- * also the 7x7 stem with stride 1, pad_lo 3): tap (ky, kx) of output (oy, ox) reads x(oy*stride + ky - pad_lo, ...).  The forward
+ * also the 7x7 stem with stride 1, pad_lo 3, and stride-1 convs whose output is smaller than their input): tap (ky, kx) of output (oy, ox) reads x(oy*stride + ky - pad_lo, ...).  The forward
  * is adm_conv_fwd_strided (ks up to 7). */
 int adm_conv_wgrad_strided(const float* x, const float* dy, float* dwp, float* dbias, int B, int Hin, int Win, int Hout, int Wout,
                            int Cin, int ldx, int Cout, int lddy, int ks, int stride, int pad_lo, hipStream_t stream);
+/* ... in the deterministic workspace form of adm_conv_wgrad_ws: `splits` = adm_conv_wgrad_plan(B, Hout, Wout, Cin, Cout, ks, 0, 0)
+ * partial tiles ws[splits][Cout][ks*ks][Cin] (bias partials bws[splits][Cout], may be NULL) for adm_unpack_wgrad_splits. */
+int adm_conv_wgrad_strided_ws(const float* x, const float* dy, float* ws, float* bws, int B, int Hin, int Win, int Hout, int Wout,
+                              int Cin, int ldx, int Cout, int lddy, int ks, int stride, int pad_lo, int splits, hipStream_t stream);
 /* B operand of the GEMM form of the transposed conv (data gradient of a strided conv): out[(tap*Ci_pad + ci)][co] = w[co][ci][tap];
  * col[m][(tap, ci)] = adm_conv_fwd(dy as a 1x1 conv with this operand), then adm_col2im gathers dx. */
 int adm_pack_weight_tconv(const float* w, float* out, int Co, int Ci, int ks, int Co_pad, int Ci_pad, hipStream_t stream);
@@ -603,6 +607,60 @@ int adm_lpips_head_fwd(const float* f0, const float* f1, const float* w, float* 
                        int accumulate, hipStream_t stream);
 int adm_lpips_head_bwd(const float* f0, const float* f1, const float* w, const float* dout, float* df0, int B, int HW, int C,
                        hipStream_t stream);
+
+
+/* ================================================================================================
+ * Training of the KL autoencoder (ddm/encoder_decoder.py AutoencoderKL.training_step with ddm/loss.py
+ * LPIPSWithDiscriminator): the kernels between the convolutions.  No float atomics: every sum is a per-workgroup fp64
+ * partial, summed in workgroup order by a second launch.  adm_ae_blocks(n) = the number of partials of an n-element sum.
+ * ================================================================================================ */
+int adm_ae_blocks(long n);
+
+/* DiagonalGaussianDistribution.sample + .kl (encoder_decoder.py:854-892) on NHWC moments [B*HW][ldm] = (mean[0:C] | logvar[C:2C]):
+ * z[B*HW][ldz] = mean + exp(0.5 clamp(logvar, -30, 20)) eps in channels [0, C), zero in [C, ldz); eps [B*HW][C];
+ * kl[b] = 0.5 sum (mean^2 + var - 1 - logvar).  part = B * adm_ae_blocks(HW * ldz) doubles. */
+int adm_posterior_kl_fwd(const float* moments, int ldm, const float* eps, float* z, int ldz, float* kl, double* part, int B,
+                         long HW, int C, hipStream_t stream);
+/* its adjoint: dmoments [B*HW][ldm] from dz [B*HW][lddz] (channels [0, C) are read; may be NULL) and dkl [B] (may be NULL); the
+ * clamp passes no gradient outside [-30, 20], as torch.clamp; channels [2C, ldm) are zero. */
+int adm_posterior_kl_bwd(const float* moments, int ldm, const float* eps, const float* dz, int lddz, const float* dkl,
+                         float* dmoments, int B, long HW, int C, hipStream_t stream);
+
+/* Reconstruction term of LPIPSWithDiscriminator.forward (loss.py): x, r [B][n_per]; p [B] = the LPIPS values (NULL: none), which
+ * the reference broadcasts over the n_per elements of their image; logvar = one device float.  With
+ * S = sum (|x - r| + (x - r)^2) + pw n_per sum_b p[b] and N = B n_per:
+ *   out[0] = nll_loss = (S exp(-logvar) + N logvar) / B      out[1] = rec_loss = S / N
+ *   out[2] = d nll_loss / d logvar = (N - S exp(-logvar)) / B
+ *   out[3] = exp(-logvar) / B = d nll_loss / d (one element of rec_loss);  d nll_loss / d p[b] = pw n_per out[3]
+ * part = adm_ae_blocks(B * n_per) doubles. */
+int adm_ae_nll_fwd(const float* x, const float* r, const float* p, const float* logvar, float* out, double* part, int B,
+                   long n_per, float pw, hipStream_t stream);
+/* g = gscale[0] mul (sign(r - x) + 2 (r - x)): the gradient of the elementwise part with respect to r; gscale = one device float */
+int adm_ae_nll_bwd(const float* x, const float* r, const float* gscale, float mul, float* g, long n, hipStream_t stream);
+
+/* PatchGAN logit map [M][ld] (NHWC, channel 0 is the logit, the rest padding): out = {mean relu(1 - l), mean relu(1 + l), mean l}
+ * (hinge_d_loss halves, -g_loss); part = 3 adm_ae_blocks(M) doubles. */
+int adm_logit_terms_fwd(const float* logits, int ld, float* out, double* part, long M, hipStream_t stream);
+/* dlogits [M][ld] = s d out[mode] / d logits in channel 0 and zero in the padding; s = mul (coef ? coef[0] : 1), coef = one device
+ * float or NULL. */
+int adm_logit_terms_bwd(const float* logits, int ld, int mode, const float* coef, float mul, float* dlogits, long M,
+                        hipStream_t stream);
+
+/* nn.LeakyReLU(slope): y = x > 0 ? x : slope x; n % 4 == 0. */
+int adm_leaky_relu_fwd(const float* x, float* y, long n, float slope, hipStream_t stream);
+int adm_leaky_relu_bwd(const float* x, const float* dy, float* dx, long n, float slope, hipStream_t stream);
+
+/* Backward of adm_softmax_rows, in place on dP: dS = scale P (dP - rowsum(dP P)); P, dP [rows][ld], cols % 4 == 0. */
+int adm_softmax_rows_bwd(const float* P, float* dP, long rows, int cols, long ld, float scale, hipStream_t stream);
+/* out[cols][rows] = in[rows][cols]^T; rows, cols multiples of 4 (operands of the attention block's NT / TN products). */
+int adm_transpose2d(const float* in, float* out, int rows, int cols, hipStream_t stream);
+
+/* calculate_adaptive_weight (loss.py): out[0] = clamp(|a| / (|b| + 1e-4), 0, 1e4) disc_weight for two gradient buffers of na / nb
+ * floats; part = adm_ae_blocks(na) + adm_ae_blocks(nb) doubles. */
+int adm_adaptive_weight(const float* a, long na, const float* b, long nb, double* part, float disc_weight, float* out,
+                        hipStream_t stream);
+/* out = a + coef[0] mul b with coef one device float (the adaptive weight); n % 4 == 0. */
+int adm_axpy_dev(const float* a, const float* b, const float* coef, float mul, float* out, long n, hipStream_t stream);
 
 #ifdef __cplusplus
 }
