@@ -168,6 +168,9 @@ _SIGS = {
     "adm_transpose2d": [P, P, I, I, P],
     "adm_adaptive_weight": [P, L, P, L, P, F, P, P],
     "adm_axpy_dev": [P, P, P, F, P, L, P],
+    "adm_swin_attn_fwd": [P, P, P, P, I, I, I, I, I, I, I, I, P],
+    "adm_ln_affine_fwd": [P, P, P, P, L, I, F, P],
+    "adm_swin_merge_ln_fwd": [P, P, P, P, I, I, I, I, F, P],
 }
 EXPORTS = tuple(_SIGS)
 

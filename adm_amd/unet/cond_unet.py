@@ -12,11 +12,12 @@ Reference lines restated: BasicAttetnionLayer :152-238, RelationNet :240-279, We
 :359-368, Block / ResnetBlock :426-468, LinearAttention :502-530, Attention :532-554, Unet :591-883 (cond_unet.py:823-918 for
 the second decoder).
 
-The condition ENCODER ``init_conv_mask`` (torchvision Swin-B / EfficientNet / ResNet with fetched ImageNet weights,
-cond_unet_sd.py:637-650) is NOT part of this build: torchvision is absent offline and the weights cannot be fetched.  Its
-output -- four feature maps of f, 2f, 4f, 8f channels (f = 128 for Swin-B) at 1/4, 1/8, 1/16, 1/32 of the condition image --
-is what ``forward`` takes as ``mask`` (a list of four NCHW tensors), or what a user-supplied ``cond_encoder`` callable
-returns for the condition image.
+The condition ENCODER ``init_conv_mask`` (cond_unet_sd.py:637-650): ``cond_encoder="swin_b"`` builds the Swin-B backbone of
+``adm_amd.unet.swin_transformer`` (forward only, frozen: the reference's ``fix_bb: True`` state; its weights come from the
+checkpoint's ``init_conv_mask.*`` tensors, nothing is fetched).  EfficientNet-B7, ResNet-101 and the single-channel Swin variant
+are not built.  With ``cond_encoder=None`` (the default) the encoder's output -- four feature maps of f, 2f, 4f, 8f channels
+(f = 128 for Swin-B) at 1/4, 1/8, 1/16, 1/32 of the condition image -- is what ``forward`` takes as ``mask`` (a list of four NCHW
+tensors); a user-supplied ``cond_encoder`` callable returns it for the condition image.
 """
 from __future__ import annotations
 
@@ -28,6 +29,7 @@ import torch.nn as nn
 
 from .. import ops
 from .. import ops_cond as oc
+from .swin_transformer import SwinTransformer, swin_b
 
 F_COND = {"swin": 128, "resnet": 256, "effnet": 48}
 
@@ -306,7 +308,13 @@ class Unet(nn.Module):
         self.f_cond = f
         self.channels, self.self_condition, self.precondition = channels, self_condition, precondition
         self.two_decoders = self.TWO_DECODERS
-        # the condition encoder (torchvision backbone + fetched weights) is supplied by the caller, see the module docstring
+        # the condition encoder: the built-in Swin-B by name, else supplied by the caller (see the module docstring)
+        if isinstance(cond_encoder, str):
+            if cond_encoder != "swin_b" or cond_net != "swin":
+                raise NotImplementedError(f"cond_encoder {cond_encoder!r} with cond_net {cond_net!r}: the built-in encoder is 'swin_b'")
+            if kwargs.get("single_channel_cond", False):
+                raise NotImplementedError("single_channel_cond (swin_transformer_for_sci) is not built")
+            cond_encoder = swin_b(fix_bb=bool(kwargs.get("fix_bb", False)))
         self.init_conv_mask = cond_encoder
         init_dim = init_dim if init_dim is not None else dim
         if dim % 32 or init_dim % 32:
@@ -370,8 +378,9 @@ class Unet(nn.Module):
 
     def init_from_ckpt(self, path, ignore_keys=()):
         sd = torch.load(path, map_location="cpu", weights_only=True)["model"]
+        keep_encoder = isinstance(self.init_conv_mask, SwinTransformer)      # the built-in encoder loads its tensors; else dropped
         for k in list(sd.keys()):
-            if any(k.startswith(ik) for ik in ignore_keys) or k.startswith("init_conv_mask."):
+            if any(k.startswith(ik) for ik in ignore_keys) or (k.startswith("init_conv_mask.") and not keep_encoder):
                 del sd[k]
         msg = self.load_state_dict(sd, strict=False)
         print(f"Restored from {path}: {msg}")
@@ -384,8 +393,8 @@ class Unet(nn.Module):
             hm = list(self.init_conv_mask(mask))
         else:
             raise RuntimeError("cond_unet.Unet: no condition encoder.  Pass the four encoder feature maps as `mask` (list of "
-                               "NCHW tensors with f, 2f, 4f, 8f channels) or construct the model with cond_encoder=<callable>; "
-                               "the reference's torchvision Swin-B and its ImageNet weights are not available offline")
+                               "NCHW tensors with f, 2f, 4f, 8f channels) or construct the model with cond_encoder='swin_b' (the "
+                               "built-in encoder, weights from the checkpoint) or cond_encoder=<callable>")
         if len(hm) != 4 or any(h.shape[1] != self.f_cond * 2 ** i for i, h in enumerate(hm)):
             raise RuntimeError(f"condition features must be 4 maps with {[self.f_cond * 2 ** i for i in range(4)]} channels")
         return [ops.nchw_to_nhwc(h.to(torch.float32), None, h.shape[1]) for h in hm]

@@ -1,0 +1,173 @@
+"""MI355X-native Swin condition encoder behind the reference's module API: the ``init_conv_mask`` of the conditional denoisers
+(/root/reference/unet/swin_transformer.py, built at cond_unet_sd.py:637-650 and cond_unet.py of the reference as ``swin_b``).
+
+FORWARD ONLY.  Same constructor keywords, same module tree and therefore the same ``state_dict()`` names and shapes (torch.nn
+modules are PARAMETER HOLDERS: ``first_coonv`` (sic), ``features.{0..6}``, and the never-used ``norm`` / ``head`` so that a strict
+load of a reference checkpoint passes).  ``forward(x)`` takes the NCHW condition image and returns the four stage outputs as
+NCHW maps (E, 2E, 4E, 8E channels at 1/4 ... 1/32), computed on HIP kernels: the fused shifted-window attention, LayerNorm and
+PatchMerging kernels of csrc/swin.hip around the GEMM / GELU / residual kernels of ``adm_amd.ops`` -- there is no PyTorch fallback.
+
+What is NOT built: the backward pass.  Every parameter is created with ``requires_grad=False`` (the reference's own
+``fix_bb: True`` state, which every shipped conditional recipe uses), the forward always runs without grad and with eval
+semantics (stochastic depth and the dropouts are identities), and nothing is ever fetched: the weights come from the
+checkpoint of the conditional model.  The single-channel variant, EfficientNet-B7 and ResNet-101 are not built either.
+
+Reference lines restated: PatchMerging :51-68, shifted_window_attention :71-168, ShiftedWindowAttention :174-248,
+SwinTransformerBlock :251-305, SwinTransformer :308-425.
+"""
+from __future__ import annotations
+
+import warnings
+from typing import List, Optional
+
+import torch
+import torch.nn as nn
+
+from .. import ops
+from .. import ops_cond as oc
+from .. import ops_swin as osw
+
+__all__ = ["SwinTransformer", "swin_b"]
+
+
+def _linear(x, lin: nn.Linear, residual=None):
+    """nn.Linear over the last axis of an NHWC tensor (+ residual in the GEMM's epilogue)."""
+    lead = x.shape[:-1]
+    r = None if residual is None else residual.reshape(-1, residual.shape[-1])
+    return ops.linear(x.reshape(-1, x.shape[-1]), lin.weight, lin.bias, r).reshape(*lead, lin.out_features)
+
+
+class PatchMerging(nn.Module):
+    def __init__(self, dim: int, norm_layer=nn.LayerNorm):
+        super().__init__()
+        self.dim = dim
+        self.reduction = nn.Linear(4 * dim, 2 * dim, bias=False)
+        self.norm = norm_layer(4 * dim)
+
+    def forward(self, x):
+        return _linear(osw.merge_layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps), self.reduction)
+
+
+class ShiftedWindowAttention(nn.Module):
+    def __init__(self, dim: int, window_size: List[int], shift_size: List[int], num_heads: int, qkv_bias: bool = True,
+                 proj_bias: bool = True, attention_dropout: float = 0.0, dropout: float = 0.0):
+        super().__init__()
+        if (list(window_size) != [osw.WINDOW, osw.WINDOW] or len(shift_size) != 2 or dim != num_heads * osw.HEAD_DIM
+                or not (qkv_bias and proj_bias)):
+            raise NotImplementedError("the window attention kernel is specialised to 7x7 windows and heads of 32 channels with "
+                                      "biases (Swin-T / -S / -B)")
+        self.window_size, self.shift_size, self.num_heads = list(window_size), list(shift_size), num_heads
+        self.qkv = nn.Linear(dim, dim * 3)
+        self.proj = nn.Linear(dim, dim)
+        self.relative_position_bias_table = nn.Parameter(torch.empty((2 * osw.WINDOW - 1) ** 2, num_heads))   # values: _init_weights
+        self.register_buffer("relative_position_index", osw.relative_position_index())
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        # the kernel evaluates the index formula instead of reading this buffer: a checkpoint that holds another one is refused
+        if not torch.equal(self.relative_position_index.cpu(), osw.relative_position_index()):
+            raise RuntimeError(f"{prefix}relative_position_index of the checkpoint is not (dy + 6) * 13 + (dx + 6), the index the "
+                               "window attention kernel computes")
+
+    def forward(self, x, residual=None):
+        """x [B, H, W, C] (already normalised); returns proj(attention) + residual.  The shift is switched off per axis, per
+        call, inside the kernel (the reference writes it into the module, which makes it sticky across shapes)."""
+        qkv = _linear(x, self.qkv)
+        o = osw.window_attention(qkv, self.qkv.bias, self.relative_position_bias_table, self.num_heads, tuple(self.shift_size))
+        return _linear(o, self.proj, residual)
+
+
+class MLP(nn.Sequential):
+    """torchvision.ops.misc.MLP's layout for one hidden layer: Linear, GELU, Dropout, Linear, Dropout (keys 0 and 3)."""
+
+    def __init__(self, dim: int, hidden: int, dropout: float = 0.0):
+        super().__init__(nn.Linear(dim, hidden), nn.GELU(), nn.Dropout(dropout), nn.Linear(hidden, dim), nn.Dropout(dropout))
+
+    def forward(self, x, residual=None):
+        return _linear(oc.gelu(_linear(x, self[0])), self[3], residual)
+
+
+class SwinTransformerBlock(nn.Module):
+    def __init__(self, dim: int, num_heads: int, window_size: List[int], shift_size: List[int], mlp_ratio: float = 4.0,
+                 dropout: float = 0.0, attention_dropout: float = 0.0, stochastic_depth_prob: float = 0.0,
+                 norm_layer=nn.LayerNorm):
+        super().__init__()
+        self.norm1 = norm_layer(dim)
+        self.attn = ShiftedWindowAttention(dim, window_size, shift_size, num_heads, attention_dropout=attention_dropout,
+                                           dropout=dropout)
+        self.norm2 = norm_layer(dim)
+        self.mlp = MLP(dim, int(dim * mlp_ratio), dropout)
+
+    def forward(self, x):
+        x = self.attn(osw.layer_norm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps), residual=x)
+        return self.mlp(osw.layer_norm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps), residual=x)
+
+
+class SwinTransformer(nn.Module):
+    def __init__(self, patch_size: List[int], embed_dim: int, depths: List[int], num_heads: List[int], window_size: List[int],
+                 mlp_ratio: float = 4.0, dropout: float = 0.0, attention_dropout: float = 0.0, stochastic_depth_prob: float = 0.0,
+                 num_classes: int = 1000, norm_layer=None, block=None, fix_bb: bool = True):
+        super().__init__()
+        if list(patch_size) != [4, 4] or embed_dim % 32 or len(depths) != 4 or len(num_heads) != 4:
+            raise NotImplementedError("4x4 patches, an embedding width that is a multiple of 32 and four stages (every reference "
+                                      "config) are what is built")
+        if norm_layer is not None or block is not None:
+            raise NotImplementedError("custom norm_layer / block classes are not supported")
+        norm_layer = lambda d: nn.LayerNorm(d, eps=1e-5)
+        self.num_classes, self.fix_bb = num_classes, fix_bb
+        self._warned = False
+        self.first_coonv = nn.Sequential(nn.Conv2d(3, embed_dim, kernel_size=4, stride=4), nn.Identity(), norm_layer(embed_dim))
+        layers: List[nn.Module] = []
+        for i_stage in range(len(depths)):
+            dim = embed_dim * 2 ** i_stage
+            layers.append(nn.Sequential(*[
+                SwinTransformerBlock(dim, num_heads[i_stage], window_size=list(window_size),
+                                     shift_size=[(i_layer & 1) * (window_size[0] // 2), (i_layer & 1) * (window_size[1] // 2)],
+                                     mlp_ratio=mlp_ratio, dropout=dropout, attention_dropout=attention_dropout, norm_layer=norm_layer)
+                for i_layer in range(depths[i_stage])]))
+            if i_stage < len(depths) - 1:
+                layers.append(PatchMerging(dim, norm_layer))
+        self.features = nn.ModuleList(layers)
+        num_features = embed_dim * 2 ** (len(depths) - 1)
+        self.norm = norm_layer(num_features)              # norm / head: never used by forward (reference :419-424), kept as holders
+        self.head = nn.Linear(num_features, num_classes)
+        self._init_weights()
+        for p in self.parameters():                        # frozen: the backward pass is not part of this build
+            p.requires_grad_(False)
+
+    def _init_weights(self):
+        """Placeholder values until a checkpoint is loaded (every real use loads one): matrices and the bias tables small
+        truncated-normal, vectors of the Linears zero; the stem conv and the LayerNorms keep torch's defaults."""
+        with torch.no_grad():
+            for name, p in self.features.named_parameters():
+                if p.dim() == 2:
+                    nn.init.trunc_normal_(p, std=0.02)
+                elif ".norm" not in name and not name.startswith("norm"):
+                    p.zero_()
+            nn.init.trunc_normal_(self.head.weight, std=0.02)
+            self.head.bias.zero_()
+
+    @torch.no_grad()
+    def forward(self, x):
+        if self.training and not self.fix_bb and not self._warned:
+            self._warned = True
+            warnings.warn("SwinTransformer: the backbone is frozen in this build (forward only, eval semantics); fix_bb: False "
+                          "training of the condition encoder is not implemented")
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise RuntimeError(f"the condition encoder takes an NCHW image with 3 channels, got {tuple(x.shape)}")
+        conv, ln = self.first_coonv[0], self.first_coonv[2]
+        h = oc.conv2d_generic(ops.nchw_to_nhwc(x.contiguous(), None, 32), conv.weight, conv.bias, stride=4, pad=0)
+        h = osw.layer_norm(h, ln.weight, ln.bias, ln.eps)
+        feats = []
+        for i, layer in enumerate(self.features):
+            h = layer(h)
+            if i % 2 == 0:
+                feats.append(osw.nhwc_to_nchw(h))
+        return feats
+
+
+def swin_b(**kwargs) -> SwinTransformer:
+    """Swin-B: 4x4 patches, width 128, depths [2, 2, 18, 2], heads [4, 8, 16, 32], 7x7 windows.  No ``weights=`` argument: nothing
+    is ever fetched, the tensors come from the conditional model's checkpoint."""
+    return SwinTransformer(patch_size=[4, 4], embed_dim=128, depths=[2, 2, 18, 2], num_heads=[4, 8, 16, 32], window_size=[7, 7],
+                           **kwargs)

@@ -662,6 +662,26 @@ int adm_adaptive_weight(const float* a, long na, const float* b, long nb, double
 /* out = a + coef[0] mul b with coef one device float (the adaptive weight); n % 4 == 0. */
 int adm_axpy_dev(const float* a, const float* b, const float* coef, float mul, float* out, long n, hipStream_t stream);
 
+/* ================================================================================================
+ * Forward of the Swin condition encoder (unet/swin_transformer.py of the reference; csrc/swin.hip).
+ * ================================================================================================ */
+
+/* shifted_window_attention between its qkv and proj Linears.  qkv [B][H][W][3C] = the qkv Linear's output with its bias, last axis
+ * ordered [3][heads][32]; qkv_bias [3C]; table [169][heads] (relative_position_bias_table); out [B][H][W][C].  The zero padding of H
+ * and W up to multiples of the window, the roll by -shift, the window partition, the bias lookup
+ * table[(dy + 6) * 13 + (dx + 6)][head], the additive -100 mask between the regions of the rolled frame and the inverses are index
+ * arithmetic: a token outside H x W is a key / value equal to qkv_bias.  The shift of an axis whose padded size is one window is
+ * ignored.  Specialised to window == 7 and C == 32 * heads: anything else returns -22. */
+int adm_swin_attn_fwd(const float* qkv, const float* qkv_bias, const float* table, float* out, int B, int H, int W, int C,
+                      int heads, int window, int shift_h, int shift_w, hipStream_t stream);
+/* nn.LayerNorm(C) with weight and bias over the rows of x [M][C]; 32 <= C <= 2048, C % 4 == 0.  Two passes over the row in
+ * registers (mean, then squared deviations). */
+int adm_ln_affine_fwd(const float* x, const float* w, const float* b, float* y, long M, int C, float eps, hipStream_t stream);
+/* PatchMerging's gather fused with its LayerNorm(4C): x [B][H][W][C] -> y [B][ceil(H/2)][ceil(W/2)][4C], the 2x2 cell's pixels in
+ * the order (0,0), (1,0), (0,1), (1,1) as (dy, dx), zeros past an odd edge; w, b [4C]; C % 4 == 0, C <= 512. */
+int adm_swin_merge_ln_fwd(const float* x, const float* w, const float* b, float* y, int B, int H, int W, int C, float eps,
+                          hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

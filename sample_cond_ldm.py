@@ -12,7 +12,9 @@ What differs from the reference:
   * windows are sampled in BATCHES (``sampler.window_batch``, default all windows of an image at once) instead of one
     ``model.sample(batch_size=1)`` call per window: each window's trajectory is independent, so batching changes only which
     random draws a window receives, and keeps the GPU full; ``window_batch: 1`` reproduces the reference's call pattern;
-  * the condition encoder (torchvision Swin-B + fetched ImageNet weights in the reference) is NOT part of this build:
+  * the condition encoder: ``sampler.cond_encoder: swin_b`` selects the built-in Swin-B (adm_amd.unet.swin_transformer, forward
+    only); it is attached before the checkpoint is loaded, so the checkpoint's ``init_conv_mask.*`` tensors (or those of its EMA
+    copy) load into it -- no ImageNet weight file is ever fetched, and a checkpoint without them is refused.  Otherwise
     ``sampler.cond_encoder`` names a callable ``module:attr`` that maps a condition crop [B,3,h,w] to the four feature maps
     the denoiser consumes; ``synthetic`` selects a parameter-free pooled pyramid (smoke runs / benchmarking only);
   * every rank handles a disjoint share of the images; no collectives.
@@ -94,6 +96,9 @@ def resolve_encoder(spec, f=128):
         return None
     if spec == "synthetic":
         return SyntheticCondEncoder(f)
+    if spec == "swin_b":
+        from adm_amd.unet.swin_transformer import swin_b
+        return swin_b()
     mod, attr = spec.split(":")
     obj = getattr(importlib.import_module(mod), attr)
     return obj() if isinstance(obj, type) else obj
@@ -148,15 +153,25 @@ def main():
     mc, s = cfg.model, cfg.sampler
     assert mc.get("ldm"), "this driver is for latent models (reference :58)"
     ldm = build_model(mc).to(device).eval()
-    enc = resolve_encoder(s.get("cond_encoder"), getattr(ldm.model, "f_cond", 128))
+    builtin = s.get("cond_encoder") == "swin_b"
+    enc = getattr(ldm.model, "init_conv_mask", None) if builtin else None          # (unet.cond_encoder: swin_b built it already)
+    if not builtin and isinstance(getattr(ldm.model, "init_conv_mask", None), torch.nn.Module):
+        raise ValueError(f"the unet section built its own condition encoder (cond_encoder: swin_b) but sampler.cond_encoder is "
+                         f"{s.get('cond_encoder')!r}: set sampler.cond_encoder: swin_b, or drop the key from the unet section")
     if enc is None:
-        raise ValueError("sampler.cond_encoder is required: 'module:callable' returning the four condition feature maps, or "
-                         "'synthetic' (the reference's torchvision Swin-B and its weights are not available offline)")
+        enc = resolve_encoder(s.get("cond_encoder"), getattr(ldm.model, "f_cond", 128))
+    if enc is None:
+        raise ValueError("sampler.cond_encoder is required: 'swin_b' (the built-in encoder, weights from the checkpoint), "
+                         "'module:callable' returning the four condition feature maps, or 'synthetic'")
     ldm.model.init_conv_mask = enc.to(device) if isinstance(enc, torch.nn.Module) else enc
     if s.get("ckpt_path") and not args.random_init:
         if not os.path.exists(s.ckpt_path):
             raise FileNotFoundError(f"sampler.ckpt_path {s.ckpt_path} does not exist (pass --random-init for a smoke run)")
-        load_weights(ldm, s.ckpt_path, s.get("use_ema", True), device)
+        missing, _ = load_weights(ldm, s.ckpt_path, s.get("use_ema", True), device)
+        lost = [k for k in missing if ".init_conv_mask." in k]
+        if builtin and lost:
+            raise RuntimeError(f"sampler.cond_encoder: swin_b, but {s.ckpt_path} lacks {len(lost)} of the encoder's tensors "
+                               f"(first: {lost[0]}): the checkpoint must hold the trained init_conv_mask.* weights")
     elif not args.random_init:
         raise ValueError("sampler.ckpt_path is empty (pass --random-init for a smoke run)")
     out_dir = s.save_folder

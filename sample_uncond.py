@@ -36,6 +36,7 @@ def load_weights(model, path, use_ema, device):
     print(f"loaded {path}: {matched} tensors matched, {len(missing)} missing, {len(unexpected)} unexpected keys")
     if matched == 0:
         raise RuntimeError(f"{path}: none of the checkpoint's {len(sd)} keys matches the model (wrong config or prefix?)")
+    return missing, unexpected
 
 
 def main():
