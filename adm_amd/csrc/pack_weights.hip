@@ -102,29 +102,30 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ a
   }
 }
 
-// One launch for ALL layers of a model.  table[e] = {src, dst_fwd, dst_bwd, Co, Ci, taps, Co_pad, Ci_pad, qkv, tile_begin,
-// dst_wino_fwd, dst_wino_bwd, dst_wino2d_fwd, dst_wino2d_bwd, dst_x6_fwd, dst_x6_bwd, dst_gemm_x6_fwd, dst_gemm_x6_bwd} (int64 each; tile_begin = exclusive prefix sum of (Co_pad/32)*(Ci_pad/32) over the rows, in
-// row order; the two Winograd destinations are 0 for layers that do not use conv_wino.hip).  One workgroup per 32
+// One launch for ALL layers of a model: table[e] = one row of PT_COLS int64 per layer (the columns: adm_pack_weight_table in
+// include/adm_hip.h; adm_amd/ops.py fills them under the same names).  One workgroup per 32
 // (out-channel) x 32 (in-channel) tile of one layer: the tile's taps-interleaved source runs (32*taps contiguous floats per
 // out-channel) go through LDS once and leave as 128-byte row segments of every operand layout, so reads and writes are
 // coalesced (the previous element-per-thread gather ran at 0.7 TB/s and cost 3.8 ms per optimiser step).
-constexpr int PT_COLS = 24;      // 18, 19: fp16-format images of the 2-D Winograd operands; 20: their scale (float bits); 21: overflow flag (int*); 22, 23: fp16-format images of the 1x1 operands (same scale and flag)
+enum : int { PT_SRC, PT_FWD, PT_BWD, PT_CO, PT_CI, PT_TAPS, PT_CO_PAD, PT_CI_PAD, PT_QKV, PT_TILE_BEGIN, PT_WF, PT_WB, PT_W2F, PT_W2B, PT_W2F6,
+             PT_W2B6, PT_G6F, PT_G6B, PT_W2FH, PT_W2BH, PT_H3_SCALE, PT_H3_FLAG, PT_G6FH, PT_G6BH, PT_COLS };
+static_assert(PT_COLS == 24, "a row of adm_pack_weight_table has 24 columns (include/adm_hip.h)");
 __global__ __launch_bounds__(256) void pack_table_kernel(const long* __restrict__ table, int n_entries) {
   __shared__ float tile[32][32 * 9 + 1];
   // layer of this tile: last row whose tile_begin <= blockIdx.x
   int lo = 0, hi = n_entries - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
-    if (table[(long)mid * PT_COLS + 9] <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
+    if (table[(long)mid * PT_COLS + PT_TILE_BEGIN] <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
   }
   const long* t = table + (long)lo * PT_COLS;
-  const float* __restrict__ w = reinterpret_cast<const float*>(t[0]);
-  float* __restrict__ fwd = reinterpret_cast<float*>(t[1]);
-  float* __restrict__ bwd = reinterpret_cast<float*>(t[2]);
-  const int Co = (int)t[3], Ci = (int)t[4], taps = (int)t[5], Co_pad = (int)t[6], Ci_pad = (int)t[7], qkv = (int)t[8];
-  float* __restrict__ wf = reinterpret_cast<float*>(t[10]);
-  float* __restrict__ wb = reinterpret_cast<float*>(t[11]);
-  const int local = (int)((long)blockIdx.x - t[9]);
+  const float* __restrict__ w = reinterpret_cast<const float*>(t[PT_SRC]);
+  float* __restrict__ fwd = reinterpret_cast<float*>(t[PT_FWD]);
+  float* __restrict__ bwd = reinterpret_cast<float*>(t[PT_BWD]);
+  const int Co = (int)t[PT_CO], Ci = (int)t[PT_CI], taps = (int)t[PT_TAPS], Co_pad = (int)t[PT_CO_PAD], Ci_pad = (int)t[PT_CI_PAD], qkv = (int)t[PT_QKV];
+  float* __restrict__ wf = reinterpret_cast<float*>(t[PT_WF]);
+  float* __restrict__ wb = reinterpret_cast<float*>(t[PT_WB]);
+  const int local = (int)((long)blockIdx.x - t[PT_TILE_BEGIN]);
   const int tiles_ci = Ci_pad >> 5;
   const int co0 = (local / tiles_ci) << 5, ci0 = (local % tiles_ci) << 5;
   const int run = 32 * taps;                       // floats per out-channel row of the tile
@@ -137,13 +138,13 @@ __global__ __launch_bounds__(256) void pack_table_kernel(const long* __restrict_
     tile[r][c] = v;
   }
   __syncthreads();
-  // 1x1 layers on conv_gemm_x6.hip: the exact three-term bf16 split of both operands, [k/16][term][rows][16] (columns 16, 17)
-  unsigned short* __restrict__ g6f = reinterpret_cast<unsigned short*>(t[16]);
-  unsigned short* __restrict__ g6b = reinterpret_cast<unsigned short*>(t[17]);
-  // ... and their two-term fp16 images [k/16][term(2)][rows][16] of scale * w (conv_gemm_x6.hip FMT 1, adm_split2_rows_f16; columns 22, 23)
-  unsigned short* __restrict__ g6fh = reinterpret_cast<unsigned short*>(t[22]);
-  unsigned short* __restrict__ g6bh = reinterpret_cast<unsigned short*>(t[23]);
-  const float gscale = __uint_as_float((unsigned)t[20]);
+  // 1x1 layers on conv_gemm_x6.hip: the exact three-term bf16 split of both operands, [k/16][term][rows][16] (PT_G6F, PT_G6B)
+  unsigned short* __restrict__ g6f = reinterpret_cast<unsigned short*>(t[PT_G6F]);
+  unsigned short* __restrict__ g6b = reinterpret_cast<unsigned short*>(t[PT_G6B]);
+  // ... and their two-term fp16 images [k/16][term(2)][rows][16] of scale * w (conv_gemm_x6.hip FMT 1, adm_split2_rows_f16; PT_G6FH, PT_G6BH)
+  unsigned short* __restrict__ g6fh = reinterpret_cast<unsigned short*>(t[PT_G6FH]);
+  unsigned short* __restrict__ g6bh = reinterpret_cast<unsigned short*>(t[PT_G6BH]);
+  const float gscale = __uint_as_float((unsigned)t[PT_H3_SCALE]);
   bool gbad = false;
   auto split2_store = [&](unsigned short* dh, long termh, float v) {
     const float a = v * gscale;
@@ -189,7 +190,7 @@ __global__ __launch_bounds__(256) void pack_table_kernel(const long* __restrict_
       split2_store(g6bh + ((((long)(k >> 4) * 2) * Ci_pad + ci0 + ci_l) << 4) + (k & 15), (long)Ci_pad << 4, v);
     }
   }
-  if (gbad && t[21]) *reinterpret_cast<int*>(t[21]) = 1;      // a scaled 1x1 weight left the fp16 range: the host falls back to the bf16 format
+  if (gbad && t[PT_H3_FLAG]) *reinterpret_cast<int*>(t[PT_H3_FLAG]) = 1;      // a scaled 1x1 weight left the fp16 range: the host falls back to the bf16 format
   if (taps != 9) return;
   // Winograd F(2,3) operands (conv_wino.hip): G g per filter row, u = (g0, (g0+g1+g2)/2, (g0-g1+g2)/2, g2)
   if (wf) {                                        // wf[xi][co][ky][ci]: ci fastest
@@ -207,16 +208,16 @@ __global__ __launch_bounds__(256) void pack_table_kernel(const long* __restrict_
     }
   }
   // 2-D Winograd F(2x2, 3x3) operands (conv_wino2d.hip): U = G g G^T, plane ey * 4 + ex
-  // ... and their exact three-term bf16 splits in adm_split3_bf16's K-chunk-tiled layout for conv_wino2d_x6.hip (columns 14, 15; 0 when unused)
-  float* __restrict__ wf2 = reinterpret_cast<float*>(t[12]);
-  float* __restrict__ wb2 = reinterpret_cast<float*>(t[13]);
-  unsigned short* __restrict__ wf6 = reinterpret_cast<unsigned short*>(t[14]);
-  unsigned short* __restrict__ wb6 = reinterpret_cast<unsigned short*>(t[15]);
+  // ... and their exact three-term bf16 splits in adm_split3_bf16's K-chunk-tiled layout for conv_wino2d_x6.hip (PT_W2F6, PT_W2B6; 0 when unused)
+  float* __restrict__ wf2 = reinterpret_cast<float*>(t[PT_W2F]);
+  float* __restrict__ wb2 = reinterpret_cast<float*>(t[PT_W2B]);
+  unsigned short* __restrict__ wf6 = reinterpret_cast<unsigned short*>(t[PT_W2F6]);
+  unsigned short* __restrict__ wb6 = reinterpret_cast<unsigned short*>(t[PT_W2B6]);
   // ... and their two-term fp16 images [ey][cols/16][ex][term(2)][rows][16] of scale * U (conv_wino2d_x6.hip, X6Fmt<1>)
-  unsigned short* __restrict__ wfh = reinterpret_cast<unsigned short*>(t[18]);
-  unsigned short* __restrict__ wbh = reinterpret_cast<unsigned short*>(t[19]);
-  const float hscale = __uint_as_float((unsigned)t[20]);
-  int* __restrict__ hflag = reinterpret_cast<int*>(t[21]);
+  unsigned short* __restrict__ wfh = reinterpret_cast<unsigned short*>(t[PT_W2FH]);
+  unsigned short* __restrict__ wbh = reinterpret_cast<unsigned short*>(t[PT_W2BH]);
+  const float hscale = __uint_as_float((unsigned)t[PT_H3_SCALE]);
+  int* __restrict__ hflag = reinterpret_cast<int*>(t[PT_H3_FLAG]);
   bool hbad = false;
   if (wf2 || wb2 || wf6 || wb6 || wfh || wbh) {
     const long plane2 = (long)Co_pad * Ci_pad;

@@ -46,31 +46,50 @@ def ceil32(n: int) -> int:
     return (n + 31) // 32 * 32
 
 
-def _new(shape, like: torch.Tensor, dtype=_f32) -> torch.Tensor:
-    t = torch.empty(shape, device=like.device, dtype=dtype)
+def _forget(t: torch.Tensor) -> torch.Tensor:
+    """A fresh allocation: a recycled address forgets the bound of its previous tenant (see _reg_amax)."""
     if _grad_amax:
-        _grad_amax.pop(t.data_ptr(), None)       # (a recycled address forgets the bound of its previous tenant: see _reg_amax)
+        _grad_amax.pop(t.data_ptr(), None)
     return t
+
+
+def _new(shape, like: torch.Tensor, dtype=_f32) -> torch.Tensor:
+    return _forget(torch.empty(shape, device=like.device, dtype=dtype))
 
 
 def _chk(t: torch.Tensor, name: str) -> torch.Tensor:
     hip.require_cuda(t, name)
     if t.dtype != _f32:
         raise RuntimeError(f"adm_amd: {name} must be float32, got {t.dtype}")
-    if t.is_contiguous():
-        return t
-    t = t.contiguous()
-    if _grad_amax:
-        _grad_amax.pop(t.data_ptr(), None)
-    return t
+    return t if t.is_contiguous() else _forget(t.contiguous())
 
 
 # ------------------------------------------------------------------------------------------------
 # packed-weight cache
 # ------------------------------------------------------------------------------------------------
+# One row of adm_pack_weight_table: the column indices (the same names are the enum of csrc/pack_weights.hip; include/adm_hip.h says what
+# each column holds) ...
+(PT_SRC, PT_FWD, PT_BWD, PT_CO, PT_CI, PT_TAPS, PT_CO_PAD, PT_CI_PAD, PT_QKV, PT_TILE_BEGIN, PT_WF, PT_WB, PT_W2F, PT_W2B, PT_W2F6, PT_W2B6,
+ PT_G6F, PT_G6B, PT_W2FH, PT_W2BH, PT_H3_SCALE, PT_H3_FLAG, PT_G6FH, PT_G6BH) = range(24)
+PACK_TABLE_COLS = 24        # = PT_COLS of csrc/pack_weights.hip
+# ... and the derived weight images of a packed entry that repack_all() keeps current, each with its column.  All are built on first use
+# (_image), so most are None for most layers.
+_PACK_IMAGES = (("wf", PT_WF), ("wb", PT_WB),              # 1-D Winograd operands (conv_wino.hip)
+                ("w2f", PT_W2F), ("w2b", PT_W2B),          # 2-D Winograd planes, f32 (conv_wino2d.hip)
+                ("w2f6", PT_W2F6), ("w2b6", PT_W2B6),      # ... their three-term bf16 splits (conv_wino2d_x6.hip)
+                ("w2fh", PT_W2FH), ("w2bh", PT_W2BH),      # ... their two-term fp16 images
+                ("g6f", PT_G6F), ("g6b", PT_G6B),          # three-term bf16 splits of the 1x1 operands (conv_gemm_x6.hip)
+                ("g6fh", PT_G6FH), ("g6bh", PT_G6BH))      # ... their two-term fp16 images
+_H3_IMAGES = ("w2fh", "w2bh", "g6fh", "g6bh")              # the images that can overflow: their rows carry the device flag
+
+
 class _Packed:
-    __slots__ = ("key", "fwd", "bwd", "bias", "fwd16", "bwd16", "wf", "wb", "w2f", "w2b", "w2f6", "w2b6", "w2fh", "w2bh", "g6f", "g6b", "g6fh", "g6bh", "src",
-                 "h3_off")
+    __slots__ = ("key", "fwd", "bwd", "bias", "fwd16", "bwd16", "src", "h3_off") + tuple(name for name, _ in _PACK_IMAGES)
+
+    def __init__(self):
+        for name in self.__slots__:
+            setattr(self, name, None)
+        self.h3_off = False          # True: a fp16 image of this entry overflowed (_h3_weight_image), the layer stays on the bf16 format
 
 
 # Contraction precision of the conv / Linear kernels: "f32" (default: exact fp32 MFMA) or "bf16" (BASELINE
@@ -110,6 +129,12 @@ _h3_checks = 0
 _amax_pool, _amax_next = None, 0
 _amax_pool_captured, _amax_pool_size = False, 0
 _AMAX_POOL = 4096
+
+
+def _fp16_format() -> bool:
+    """The fp16 split format is on: kernels that can write max |output| next to their output do, and consumers that find a bound on
+    their operand use it.  Read at call time (tests switch the three); the 1x1 convs and what feeds them also ask for H3_GEMM."""
+    return FP16X3 and BF16X6 and COMPUTE == "f32"
 
 
 AMAX_FLOATS = 64 * 32      # a bound vector: ADM_AMAX_SLOTS floats at a stride of ADM_AMAX_STRIDE (include/adm_hip.h)
@@ -222,10 +247,7 @@ AMAX_CHECK = os.environ.get("ADM_AMAX_CHECK", "0") == "1"      # tests: verify e
 
 
 def _like(x: torch.Tensor) -> torch.Tensor:
-    t = torch.empty_like(x)
-    if _grad_amax:
-        _grad_amax.pop(t.data_ptr(), None)
-    return t
+    return _forget(torch.empty_like(x))
 
 
 def _h3_flag_tensor(like):
@@ -248,29 +270,55 @@ def _h3_weight_image(ent: "_Packed", split) -> bool:
     return True
 
 
+def _invalidate_pack_table():
+    """The one-launch repack table (repack_all) must be rebuilt: a destination was added, dropped or moved."""
+    global _pack_table
+    _pack_table = None
+
+
+def _image(ent: "_Packed", names: tuple, build):
+    """The derived image in the first of the slots `names` of a packed entry (slots that one kernel fills together).  Empty slots are
+    built on first use -- build() returns one tensor per slot, or None when the image cannot be had -- and stored, and the repack table
+    is invalidated so that repack_all() refreshes the new destinations from then on.  (The builders look at their slot before they come
+    here: they run on the host path of every conv launch, where the call and build's closure cost more than the lookup.)"""
+    if getattr(ent, names[0]) is None:
+        made = build()
+        if made is None:
+            return None
+        for name, t in zip(names, made):
+            setattr(ent, name, t)
+        _invalidate_pack_table()
+    return getattr(ent, names[0])
+
+
+def _wino2_planes(weight: torch.Tensor):
+    """(forward, data-gradient) f32 2-D Winograd planes G g G^T of a 3x3 weight: [16][cop][cip], [16][cip][cop]."""
+    co, ci = weight.shape[0], weight.shape[1]
+    cop, cip = ceil32(co), ceil32(ci)
+    w = _chk(weight.detach(), "weight")
+    w2f, w2b = _new((16, cop, cip), w), _new((16, cip, cop), w)
+    call("adm_pack_weight_wino2d", ptr(w), ptr(w2f), ptr(w2b), co, ci, cop, cip)
+    return w2f, w2b
+
+
 def _h3_operands(weight: torch.Tensor, ent: "_Packed", which: int):
     """fp16-format image of a 2-D Winograd operand (which = 0: forward, 1: data gradient), built on first use from the f32 planes and
     afterwards refreshed by repack_all() with the rest.  Only the direction that is asked for is built and kept current: most layers
     never need the other format's image of the same direction (a third of the repack table's bytes).  None when the layer's weights
     do not fit the fp16 image (the caller runs the bf16 format)."""
-    global _pack_table
-    name = "w2bh" if which else "w2fh"
     if ent.h3_off:
         return None
-    if getattr(ent, name) is None:
-        co, ci = weight.shape[0], weight.shape[1]
-        cop, cip = ceil32(co), ceil32(ci)
-        w = _chk(weight.detach(), "weight")
-        w2f, w2b = _new((16, cop, cip), w), _new((16, cip, cop), w)
-        call("adm_pack_weight_wino2d", ptr(w), ptr(w2f), ptr(w2b), co, ci, cop, cip)
-        rows, cols = (cip, cop) if which else (cop, cip)
-        img = torch.empty((16, 2, rows, cols), device=w.device, dtype=torch.float16)
-        if not _h3_weight_image(ent, lambda flag: call("adm_split2_f16", ptr(w2b if which else w2f), ptr(img), rows, cols, H3_WSCALE,
-                                                       ptr(flag))):
-            return None
-        setattr(ent, name, img)
-        _pack_table = None           # the one-launch repack table must learn the new destination
-    return getattr(ent, name)
+    name = "w2bh" if which else "w2fh"
+    if getattr(ent, name) is not None:
+        return getattr(ent, name)
+
+    def build():
+        src = _wino2_planes(weight)[which]
+        rows, cols = src.shape[1], src.shape[2]
+        img = torch.empty((16, 2, rows, cols), device=src.device, dtype=torch.float16)
+        ok = _h3_weight_image(ent, lambda flag: call("adm_split2_f16", ptr(src), ptr(img), rows, cols, H3_WSCALE, ptr(flag)))
+        return (img,) if ok else None
+    return _image(ent, (name,), build)
 
 
 # ADM_DETERMINISTIC=1: bitwise reproducible backward.  The weight / bias gradient kernels normally combine their pixel-range
@@ -323,9 +371,9 @@ def set_compute_precision(mode: str):
 
 
 def _bf16_operand(ent: "_Packed", which: str) -> torch.Tensor:
-    """bf16 copy of a packed weight operand, built on first use per packed entry."""
+    """bf16 copy of a packed weight operand, built on first use per packed entry (no row of the repack table: repack_all() drops it)."""
     name = which + "16"
-    t = getattr(ent, name, None)
+    t = getattr(ent, name)
     if t is None:
         src = getattr(ent, which)
         t = torch.empty(src.shape, device=src.device, dtype=torch.bfloat16)
@@ -336,15 +384,15 @@ def _bf16_operand(ent: "_Packed", which: str) -> torch.Tensor:
 
 def _wino_operands(weight: torch.Tensor, ent: "_Packed"):
     """Winograd operands (G g) of a packed 3x3 entry, built on first use; afterwards refreshed by repack_all()."""
-    if ent.wf is None:
-        global _pack_table
+    def build():
         co, ci = weight.shape[0], weight.shape[1]
         cop, cip = ceil32(co), ceil32(ci)
         w = _chk(weight.detach(), "weight")
-        ent.wf = _new((4, cop, 3, cip), w)
-        ent.wb = _new((4, cip, 3, cop), w)
-        call("adm_pack_weight_wino", ptr(w), ptr(ent.wf), ptr(ent.wb), co, ci, cop, cip)
-        _pack_table = None           # the one-launch repack table must learn the new destinations
+        wf, wb = _new((4, cop, 3, cip), w), _new((4, cip, 3, cop), w)
+        call("adm_pack_weight_wino", ptr(w), ptr(wf), ptr(wb), co, ci, cop, cip)
+        return wf, wb
+    if ent.wf is None:
+        _image(ent, ("wf", "wb"), build)
     return ent.wf, ent.wb
 
 
@@ -353,35 +401,24 @@ def _wino2_operands(weight: torch.Tensor, ent: "_Packed", which: int):
     first use; refreshed by repack_all().  With BF16X6 only the three-term bf16 split of the direction that is asked for is built
     and kept (conv_wino2d_x6.hip reads nothing else): the f32 planes, and the image of a direction that runs on the fp16 format,
     would be rewritten by every repack without ever being read."""
-    global _pack_table
     if not BF16X6:
         if ent.w2f is None:
-            co, ci = weight.shape[0], weight.shape[1]
-            cop, cip = ceil32(co), ceil32(ci)
-            w = _chk(weight.detach(), "weight")
-            ent.w2f = _new((16, cop, cip), w)
-            ent.w2b = _new((16, cip, cop), w)
-            call("adm_pack_weight_wino2d", ptr(w), ptr(ent.w2f), ptr(ent.w2b), co, ci, cop, cip)
-            _pack_table = None
+            _image(ent, ("w2f", "w2b"), lambda: _wino2_planes(weight))
         return ent.w2b if which else ent.w2f
     name = "w2b6" if which else "w2f6"
-    if getattr(ent, name) is None:
-        planes = (ent.w2f, ent.w2b)
-        if planes[0] is None:
-            co, ci = weight.shape[0], weight.shape[1]
-            cop, cip = ceil32(co), ceil32(ci)
-            w = _chk(weight.detach(), "weight")
-            planes = (_new((16, cop, cip), w), _new((16, cip, cop), w))
-            call("adm_pack_weight_wino2d", ptr(w), ptr(planes[0]), ptr(planes[1]), co, ci, cop, cip)
-        src = planes[which]
+    if getattr(ent, name) is not None and ent.w2f is None:
+        return getattr(ent, name)
+
+    def build():
+        src = (ent.w2b if which else ent.w2f) if ent.w2f is not None else _wino2_planes(weight)[which]
         img = torch.empty((16, 3) + tuple(src.shape[1:]), device=src.device, dtype=torch.bfloat16)
         call("adm_split3_bf16", ptr(src), ptr(img), src.shape[1], src.shape[2])     # K-chunk-tiled: a = a0 + a1 + a2 exactly
-        setattr(ent, name, img)
-        _pack_table = None           # the one-launch repack table must learn the new destination
+        return (img,)
+    img = _image(ent, (name,), build)
     if ent.w2f is not None:          # (left from a run with BF16X6 off)
         ent.w2f = ent.w2b = None
-        _pack_table = None
-    return getattr(ent, name)
+        _invalidate_pack_table()
+    return img
 
 
 GEMM_X6_MIN_M = int(os.environ.get("ADM_GEMM_X6_MIN_M", "2048"))      # (8192 until round 3: the 4x4 level's 1x1 convs, +0.7 %)
@@ -402,33 +439,34 @@ def _use_gemm_x6(M: int, ks: int, up, n_p: int, k_p: int) -> bool:
 def _gemm_x6_operand(ent: "_Packed", which: int):
     """[K/16][3][rows][16] bf16 image of a packed 1x1 operand (which = 0 forward: rows = couts; 1 data gradient: rows = cins), built on
     first use (only the direction that is asked for), refreshed by repack_all() afterwards."""
-    global _pack_table
     name = "g6b" if which else "g6f"
-    if getattr(ent, name) is None:
+    if getattr(ent, name) is not None:
+        return getattr(ent, name)
+
+    def build():
         src = ent.bwd if which else ent.fwd
         img = torch.empty((3,) + tuple(src.shape), device=src.device, dtype=torch.bfloat16)
         call("adm_split3_rows", ptr(src), ptr(img), src.shape[0], src.shape[1], src.shape[1])
-        setattr(ent, name, img)
-        _pack_table = None           # the one-launch repack table must learn the new destination
-    return getattr(ent, name)
+        return (img,)
+    return _image(ent, (name,), build)
 
 
 def _gemm_h3_operand(ent: "_Packed", which: int):
     """[K/16][2][rows][16] fp16 image (scale H3_WSCALE) of a packed 1x1 operand: which = 0 forward (rows = couts), 1 data gradient (rows =
     cins); built on first use, refreshed by repack_all() afterwards; None when the weights do not fit it (see _h3_weight_image)."""
-    global _pack_table
-    name = "g6bh" if which else "g6fh"
     if ent.h3_off:
         return None
-    if getattr(ent, name) is None:
+    name = "g6bh" if which else "g6fh"
+    if getattr(ent, name) is not None:
+        return getattr(ent, name)
+
+    def build():
         src = ent.bwd if which else ent.fwd
         img = torch.empty((2,) + tuple(src.shape), device=src.device, dtype=torch.float16)
-        if not _h3_weight_image(ent, lambda flag: call("adm_split2_rows_f16", ptr(src), ptr(img), src.shape[0], src.shape[1], src.shape[1],
-                                                       H3_WSCALE, ptr(flag))):
-            return None
-        setattr(ent, name, img)
-        _pack_table = None           # the one-launch repack table must learn the new destination
-    return getattr(ent, name)
+        ok = _h3_weight_image(ent, lambda flag: call("adm_split2_rows_f16", ptr(src), ptr(img), src.shape[0], src.shape[1], src.shape[1],
+                                                     H3_WSCALE, ptr(flag)))
+        return (img,) if ok else None
+    return _image(ent, (name,), build)
 
 
 _pack_epoch = 0     # bumped by code that rewrites parameters through raw pointers (fused optimiser)
@@ -449,19 +487,10 @@ def packed(weight: torch.Tensor, bias: Optional[torch.Tensor], ks: int, qkv: boo
     w = _chk(weight.detach(), "weight")
     ent = _Packed()
     ent.key = key
-    ent.fwd16 = ent.bwd16 = None
-    ent.wf = ent.wb = None
-    ent.w2f = ent.w2b = None
-    ent.w2f6 = ent.w2b6 = None
-    ent.w2fh = ent.w2bh = None
-    ent.g6f = ent.g6b = None
-    ent.g6fh = ent.g6bh = None
-    ent.h3_off = False
     ent.src = (co, ci, ks, qkv)
     ent.fwd = _new((cop, ks * ks * cip), w)
     ent.bwd = _new((cip, ks * ks * cop), w)
     call("adm_pack_weight", ptr(w), ptr(ent.fwd), ptr(ent.bwd), co, ci, ks, cop, cip, int(qkv))
-    ent.bias = None
     if bias is not None and not qkv and cop == co:
         ent.bias = _chk(bias.detach(), "bias")          # usable as is
     elif bias is not None:
@@ -474,8 +503,7 @@ def packed(weight: torch.Tensor, bias: Optional[torch.Tensor], ks: int, qkv: boo
         # would only churn it
         if isinstance(weight, torch.nn.Parameter):
             _pack_registry[id(weight)] = (weakref.ref(weight), None if bias is None else weakref.ref(bias), ks, qkv)
-            global _pack_table
-            _pack_table = None
+            _invalidate_pack_table()
     except (AttributeError, TypeError):
         pass
     return ent
@@ -493,7 +521,23 @@ _pack_table = None          # (device int64 table, [entries], total 32x32 tiles,
 
 
 _H3_WSCALE_BITS = int.from_bytes(__import__("struct").pack("<f", H3_WSCALE), "little")
-PACK_TABLE_COLS = 24        # = PT_COLS of csrc/pack_weights.hip: a row of adm_pack_weight_table
+
+
+def _pack_row(src: torch.Tensor, ent: _Packed, co: int, ci: int, ks: int, qkv: bool, tile_begin: int) -> list:
+    """The row of adm_pack_weight_table that re-derives every operand of the packed entry `ent` from the OIHW / [out, in] tensor `src`:
+    fwd, bwd and whichever images exist (_PACK_IMAGES); tile_begin = the 32 x 32 tiles of the rows before this one."""
+    row = [0] * PACK_TABLE_COLS
+    row[PT_SRC], row[PT_FWD], row[PT_BWD] = src.data_ptr(), ent.fwd.data_ptr(), ent.bwd.data_ptr()
+    row[PT_CO], row[PT_CI], row[PT_TAPS], row[PT_CO_PAD], row[PT_CI_PAD] = co, ci, ks * ks, ceil32(co), ceil32(ci)
+    row[PT_QKV], row[PT_TILE_BEGIN] = int(qkv), tile_begin
+    for name, col in _PACK_IMAGES:
+        img = getattr(ent, name)
+        if img is not None:
+            row[col] = img.data_ptr()
+    row[PT_H3_SCALE] = _H3_WSCALE_BITS
+    if any(getattr(ent, name) is not None for name in _H3_IMAGES):      # an image that leaves the fp16 range raises the device flag
+        row[PT_H3_FLAG] = _h3_flag_tensor(src).data_ptr()
+    return row
 
 
 def repack_all():
@@ -516,18 +560,8 @@ def repack_all():
                 _pack_registry.pop(key, None)
                 continue
             co, ci = w.shape[0], w.shape[1]
-            cop, cip = ceil32(co), ceil32(ci)
-            rows.append([w.data_ptr(), ent.fwd.data_ptr(), ent.bwd.data_ptr(), co, ci, ks * ks, cop, cip, int(qkv), tiles,
-                         0 if ent.wf is None else ent.wf.data_ptr(), 0 if ent.wb is None else ent.wb.data_ptr(),
-                         0 if ent.w2f is None else ent.w2f.data_ptr(), 0 if ent.w2b is None else ent.w2b.data_ptr(),
-                         0 if ent.w2f6 is None else ent.w2f6.data_ptr(), 0 if ent.w2b6 is None else ent.w2b6.data_ptr(),
-                         0 if ent.g6f is None else ent.g6f.data_ptr(), 0 if ent.g6b is None else ent.g6b.data_ptr(),
-                         0 if ent.w2fh is None else ent.w2fh.data_ptr(), 0 if ent.w2bh is None else ent.w2bh.data_ptr(),
-                         _H3_WSCALE_BITS,
-                         0 if (ent.w2fh is None and ent.w2bh is None and ent.g6fh is None and ent.g6bh is None) else _h3_flag_tensor(w).data_ptr(),
-                         0 if ent.g6fh is None else ent.g6fh.data_ptr(), 0 if ent.g6bh is None else ent.g6bh.data_ptr()])
-            assert len(rows[-1]) == PACK_TABLE_COLS
-            tiles += (cop // 32) * (cip // 32)         # column 9 = exclusive prefix sum of 32x32 tiles
+            rows.append(_pack_row(w, ent, co, ci, ks, qkv, tiles))
+            tiles += (ceil32(co) // 32) * (ceil32(ci) // 32)       # PT_TILE_BEGIN = exclusive prefix sum of 32x32 tiles
             ents.append((wref, bref, ks, qkv, ent))
         if not rows:
             return
@@ -536,7 +570,7 @@ def repack_all():
     table, ents, total_tiles, rows = _pack_table
     for (wref, bref, ks, qkv, ent), row in zip(ents, rows):      # storage moved or parameter died -> rebuild lazily
         w = wref()
-        if w is None or w.data_ptr() != row[0] or getattr(w, "_adm_packed", None) is not ent:
+        if w is None or w.data_ptr() != row[PT_SRC] or getattr(w, "_adm_packed", None) is not ent:
             _pack_table = None
             return
     call("adm_pack_weight_table", ptr(table), len(ents), total_tiles)
@@ -560,12 +594,21 @@ def repack_all():
 # scatters all layers and clears what it read.  A gradient sink (the bucketed DDP reducer) needs the gradient when it is
 # notified, so any notification flushes first.  ADM_DEFER_UNPACK=0 restores the per-layer launches.
 DEFER_UNPACK = os.environ.get("ADM_DEFER_UNPACK", "1") != "0"
-_rest_ws = {}               # (weight data_ptr, numel) -> zero-at-rest workspace
-_unpack_rows = []           # pending rows of the table (host ints) + the tensors they point into
-_unpack_keep = []
+_UT_ITEMS = 2048            # gradient elements per workgroup of adm_unpack_wgrad_table
+_TABLE_CACHE = 256          # row sets kept per table cache
+_rest_ws = {}               # (weight data_ptr, shape) -> zero-at-rest workspace
+# pending weight-gradient rows (host ints; the last entry of a row = its block count), the tensors they point into, and the workspaces
+# among them: a layer applied twice in one pass must not meet its own pending tile
+_unpack_rows, _unpack_keep, _unpack_pending = [], [], set()
+# ... and the pending GroupNorm parameter-gradient reductions (tot, ss, bstride, dgamma, dbeta, B, C, blocks), with their dgamma destinations
+_gn_rows, _gn_keep, _gn_pending = [], [], set()
 _unpack_tables = {}         # row set -> (device table, total blocks)
+_gn_tables = {}             # ... the same: with a bucketed reducer every bucket flushes its own set, every step
+_pinned_tables = []         # host copies of uploaded tables (pinned: the copy is asynchronous; kept alive with the cache)
+table_uploads = 0           # diagnostics: host->device table copies (asynchronous, from pinned memory)
+_producer_streams = {}      # streams on which queued work was produced since the last flush (the flush waits for them)
 _unpack_queued = -2         # id of the backward pass (autograd graph task) whose end-of-pass callback is queued
-_UT_ITEMS = 2048
+_rows_task = -2             # the pass the pending rows belong to
 
 
 def _graph_task_id() -> int:
@@ -573,9 +616,6 @@ def _graph_task_id() -> int:
     mark by the pass id (not a flag) means a pass that raised half-way cannot leave the mark set for every later pass."""
     f = getattr(torch._C, "_current_graph_task_id", None)
     return f() if f is not None else -1
-
-
-_rows_task = -2             # the pass the pending rows belong to
 
 
 def _begin_defer():
@@ -594,10 +634,6 @@ def _queue_flush():
     if tid < 0 or _unpack_queued != tid:       # (no id available: queue every time -- the flush is idempotent)
         _unpack_queued = tid
         torch.autograd.Variable._execution_engine.queue_callback(flush_deferred_unpack)
-_producer_streams = {}      # streams on which queued work was produced since the last flush (the flush waits for them)
-
-
-_pinned_tables = []         # host copies of uploaded tables (pinned: the copy is asynchronous; kept alive with the cache)
 
 
 def _upload_table(rows, device):
@@ -611,6 +647,26 @@ def _upload_table(rows, device):
         del _pinned_tables[: 2 * _TABLE_CACHE]
     _pinned_tables.append(host)
     return host.to(device, non_blocking=True)
+
+
+def _pending_table(pending, cache, table_row, device):
+    """(device table, blocks) of a list of pending rows, from `cache` when this row set was flushed before (the workspaces are
+    persistent, so the weight-gradient rows repeat from the second step on; the GroupNorm rows point into fresh allocations, whose
+    addresses repeat only after a few steps).  table_row(row, begin) = the table's row for a pending row whose workgroups start at
+    block `begin`: the exclusive prefix sum of the block counts, the last entry of every pending row."""
+    global table_uploads
+    key = tuple(pending)
+    ent = cache.get(key)
+    if ent is None:
+        rows, begin = [], 0
+        for r in pending:
+            rows.append(table_row(r, begin))
+            begin += r[-1]
+        if len(cache) >= _TABLE_CACHE:
+            cache.clear()
+        ent = cache[key] = (_upload_table(rows, device), begin)
+        table_uploads += 1
+    return ent
 
 
 def _note_producer_stream():
@@ -628,21 +684,6 @@ def _rest_workspace(weight, shape, like):
     return ws
 
 
-def _defer_unpack(ws, dst, co, ci, taps, cip, qkv):
-    """Queue `dst (OIHW) += unpack(ws)` for the end-of-backward table launch; taps = 0 for the 2-D Winograd planes."""
-    _begin_defer()
-    items = co * ci * (taps if taps else 3)
-    _unpack_rows.append((ws.data_ptr(), dst.data_ptr(), co, ci, taps, cip, int(qkv), 1, 1, (items + _UT_ITEMS - 1) // _UT_ITEMS))
-    _unpack_keep.append((ws, dst))
-    _unpack_pending.add(ws.data_ptr())
-    _note_producer_stream()
-    _queue_flush()
-
-
-_unpack_pending = set()     # workspaces with a queued row: a layer applied twice in one pass must not meet its own pending tile
-_gn_pending = set()         # ... and the same for the dgamma destinations of the GroupNorm rows
-
-
 def _rest_workspace_for(weight, shape, like):
     """The layer's zero-at-rest workspace, flushed first when a row for it is already queued (a module applied twice in one
     forward pass: the second weight-gradient kernel may use plain stores, and two table rows with one workspace would be read,
@@ -653,11 +694,15 @@ def _rest_workspace_for(weight, shape, like):
     return ws
 
 
-_gn_rows = []               # pending GroupNorm parameter-gradient reductions: (tot, ss, bstride, dgamma, dbeta, B, C, blocks)
-_gn_keep = []
-_gn_tables = {}            # row set -> (device table, blocks): with a bucketed reducer every bucket flushes its own set, every step
-_TABLE_CACHE = 256
-table_uploads = 0           # diagnostics: host->device table copies (asynchronous, from pinned memory)
+def _defer_unpack(ws, dst, co, ci, taps, cip, qkv):
+    """Queue `dst (OIHW) += unpack(ws)` for the end-of-backward table launch; taps = 0 for the 2-D Winograd planes."""
+    _begin_defer()
+    items = co * ci * (taps if taps else 3)
+    _unpack_rows.append((ws.data_ptr(), dst.data_ptr(), co, ci, taps, cip, int(qkv), 1, 1, (items + _UT_ITEMS - 1) // _UT_ITEMS))
+    _unpack_keep.append((ws, dst))
+    _unpack_pending.add(ws.data_ptr())
+    _note_producer_stream()
+    _queue_flush()
 
 
 def _defer_gn_param(red, tot_off, ss, bstride, dgamma, dbeta, B, C):
@@ -689,21 +734,7 @@ def _used_on(stream, *tensors):
 def _flush_gn_params():
     if not _gn_rows:
         return
-    # (the partial-sum buffers and scale/shift tensors are fresh allocations: their addresses repeat only after a few steps, so a
-    #  new row set is common here -- its upload is asynchronous, from pinned memory)
-    key = tuple(_gn_rows)
-    ent = _gn_tables.get(key)
-    if ent is None:
-        rows, begin = [], 0
-        for r in _gn_rows:
-            rows.append(list(r[:7]) + [begin])
-            begin += r[7]
-        if len(_gn_tables) >= _TABLE_CACHE:
-            _gn_tables.clear()
-        ent = _gn_tables[key] = (_upload_table(rows, _gn_keep[0][0].device), begin)
-        global table_uploads
-        table_uploads += 1
-    table, blocks = ent
+    table, blocks = _pending_table(_gn_rows, _gn_tables, lambda r, begin: list(r[:7]) + [begin], _gn_keep[0][0].device)
     call("adm_gn_bwd_param_table", ptr(table), len(_gn_rows), blocks)
     cur = torch.cuda.current_stream() if table.is_cuda else None
     _used_on(cur, table)            # (a cached table may have been uploaded on another stream and can be dropped by the cache)
@@ -730,21 +761,9 @@ def flush_deferred_unpack():
     _flush_gn_params()
     if not _unpack_rows:
         return
-    key = tuple(_unpack_rows)
-    ent = _unpack_tables.get(key)
-    if ent is None:           # (first step only: the upload is a synchronising copy)
-        rows, begin = [], 0
-        for r in _unpack_rows:
-            rows.append(list(r[:9]) + [begin, 0, 0])
-            begin += r[9]
-        if len(_unpack_tables) >= _TABLE_CACHE:
-            _unpack_tables.clear()
-        ent = _unpack_tables[key] = (_upload_table(rows, _unpack_keep[0][0].device), begin)
-        global table_uploads
-        table_uploads += 1
-    table, blocks = ent
+    table, blocks = _pending_table(_unpack_rows, _unpack_tables, lambda r, begin: list(r[:9]) + [begin, 0, 0], _unpack_keep[0][0].device)
     n = len(_unpack_rows)
-    _unpack_rows.clear()
+    _unpack_rows.clear()         # (before the launch, unlike the GroupNorm rows: a launch that raises drops its rows)
     _unpack_keep.clear()         # (workspaces and gradient views are persistent: nothing is released here)
     _unpack_pending.clear()
     call("adm_unpack_wgrad_table", ptr(table), n, blocks)
@@ -933,9 +952,10 @@ class _Conv(torch.autograd.Function):
         g6 = not use_bf16 and _use_gemm_x6(_sel_batch(B) * Ho * Wo, ks, up, cop, cip)
         g6h = g6 and FP16X3 and H3_GEMM and amax is not None and _gemm_h3_operand(pk, 0) is not None
         # the bound of a 1x1 conv's OUTPUT (qkv -> attention -> proj; proj + residual -> the next block's skip conv): written by the epilogue
-        global _conv_amax_out
-        _conv_amax_out = None
-        want_out = FP16X3 and H3_GEMM and BF16X6 and not bf16 and x.is_cuda
+        # (bias and residual included) and handed to the consumer on y, where conv2d / attention look for it
+        fmt = _fp16_format()
+        want_out = fmt and H3_GEMM
+        amax_y = None
         kind = ("wino2h3" if h3 else "wino2x6" if BF16X6 else "wino2") if wino2 else "wino" if wq is not None else ("gemmh3" if g6h else "gemmx6") if g6 else "igemm"
         with _Prof(kind, 2.0 * B * Ho * Wo * co * ci * ks * ks,
                    f"fwd{'-' + kind if kind != 'igemm' else ''} M={B * Ho * Wo} N={cop} K={ks * ks * cip}"):
@@ -947,13 +967,13 @@ class _Conv(torch.autograd.Function):
                 call("adm_conv_fwd_wino2d_h3", ptr(x), ptr(_h3_operands(weight, pk, 0)), ptr(pk.bias), ptr(res), ptr(y), ptr(wsk),
                      0 if wsk is None else wsk.numel(), B, Ho, Wo, cip, cip, cop, cop, cop, cop, _bptr(amax), H3_WSCALE, int(up))
             elif g6h:
-                _conv_amax_out = _amax_slot(x) if want_out else None
+                amax_y = _amax_slot(x) if want_out else None
                 call("adm_gemm_x6_h3", ptr(x), ptr(_gemm_h3_operand(pk, 0)), ptr(pk.bias), ptr(res), ptr(y), B * Ho * Wo, cip, cip, cop,
-                     cop, cop, cop, _bptr(amax), H3_WSCALE, ptr(_conv_amax_out))
+                     cop, cop, cop, _bptr(amax), H3_WSCALE, ptr(amax_y))
             elif g6 and want_out:
-                _conv_amax_out = _amax_slot(x)
+                amax_y = _amax_slot(x)
                 call("adm_gemm_x6_amax", ptr(x), ptr(_gemm_x6_operand(pk, 0)), ptr(pk.bias), ptr(res), ptr(y), B * Ho * Wo, cip, cip, cop,
-                     cop, cop, cop, ptr(_conv_amax_out))
+                     cop, cop, cop, ptr(amax_y))
             elif g6:
                 call("adm_gemm_x6", ptr(x), ptr(_gemm_x6_operand(pk, 0)), ptr(pk.bias), ptr(res), ptr(y), B * Ho * Wo, cip, cip, cop,
                      cop, cop, cop)
@@ -966,7 +986,9 @@ class _Conv(torch.autograd.Function):
         ctx.save_for_backward(x16 if x16 is not None else x, weight, bias)      # (the carrier is not kept)
         _mark_uses(ctx, (1, weight), (2, bias))
         ctx.meta = (ks, up, qkv, residual is not None, bf16)
-        ctx.amax_x = amax if (FP16X3 and BF16X6 and not bf16) else None       # the weight gradient reads x on the same format
+        ctx.amax_x = amax if fmt else None       # the weight gradient reads x on the same format
+        if amax_y is not None:
+            y._adm_amax = amax_y
         return y
 
     @staticmethod
@@ -1185,18 +1207,8 @@ def conv2d(x, weight, bias=None, residual=None, *, up=False, qkv=False, tile=-1,
     (default: the one a GroupNorm kernel attached to x) -- lets the 3x3 layers run on the fp16 split format."""
     if amax is None:
         amax = getattr(x, "_adm_amax", None)
-    if AMAX_CHECK and amax is not None:
-        got, bound = float(x.detach().abs().max()), float(amax.max())
-        if not got <= bound:
-            raise RuntimeError(f"adm_amd: the bound {bound} that came with a conv input is below its maximum {got}")
-    global _conv_amax_out
-    y = _Conv.apply(x, weight, bias, residual, weight.shape[-1] if weight.dim() == 4 else 1, bool(up), bool(qkv), tile, amax)
-    if _conv_amax_out is not None:       # the kernel's epilogue wrote the bound of y (bias and residual included)
-        y._adm_amax, _conv_amax_out = _conv_amax_out, None
-    return y
-
-
-_conv_amax_out = None       # bound vector of the last conv forward's output (handed from _Conv.forward to conv2d(), as _gn_amax_out)
+    _check_bound(x, amax, "a conv input")
+    return _Conv.apply(x, weight, bias, residual, weight.shape[-1] if weight.dim() == 4 else 1, bool(up), bool(qkv), tile, amax)
 
 
 def linear(x, weight, bias=None, residual=None):
@@ -1245,16 +1257,16 @@ class _GroupNormAct(torch.autograd.Function):
         if out_bf16 and C % 64 == 0:
             # bf16 storage: the VALUES go to y16; `y` is only the f32 shape / dtype carrier autograd needs between this node and the
             # conv that consumes it (its storage is never written or read, and is released as soon as the conv has run)
-            global _gn_bf16_out
-            _gn_bf16_out = y16 = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
+            y16 = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
             call("adm_gn_fwd_bf16out", ptr(x), ptr(stats), ptr(ws), ptr(g), ptr(b), ptr(ssc), bstride, ptr(y16), B, HW, C, G, float(eps),
                  int(silu), float(drop_p), seed)
+            y._adm_bf16 = y16       # conv2d looks for the values here
         else:
             if want_amax:     # the conv that consumes y runs on the fp16 format: it needs max |y| (written next to y by the same kernel)
-                global _gn_amax_out
-                _gn_amax_out = slot_a = _amax_slot(x)
+                slot_a = _amax_slot(x)
                 call("adm_gn_fwd_amax", ptr(x), ptr(stats), ptr(ws), ptr(g), ptr(b), ptr(ssc), bstride, ptr(y), ptr(slot_a), B, HW, C, G,
                      float(eps), int(silu), float(drop_p), seed)
+                y._adm_amax = slot_a      # conv2d looks for the bound on its input
             else:
                 call("adm_gn_fwd", ptr(x), ptr(stats), ptr(ws), ptr(g), ptr(b), ptr(ssc), bstride, ptr(y), B, HW, C, G, float(eps),
                      int(silu), float(drop_p), seed)
@@ -1298,7 +1310,7 @@ class _GroupNormAct(torch.autograd.Function):
         defer = direct and DEFER_UNPACK and not DETERMINISTIC      # the batch reduction joins the end-of-backward table launch
         if defer:
             _begin_defer()
-        slot_a = _amax_slot(x) if (FP16X3 and BF16X6 and COMPUTE == "f32") else None      # max |dx| for the conv that consumes dx
+        slot_a = _amax_slot(x) if _fp16_format() else None      # max |dx| for the conv that consumes dx
         with _Prof("gn", (12.0 if add is None else 16.0) * x.numel(), f"gn-bwd B={B} HW={HW} C={C} drop={int(drop_p > 0)} (TB/s)"):
             if slot_a is not None:
                 call("adm_gn_bwd_add_amax", ptr(x), ptr(dy), ptr(stats), ptr(gamma.detach()), ptr(beta.detach()), ptr(ss), bstride,
@@ -1320,28 +1332,8 @@ class _GroupNormAct(torch.autograd.Function):
         return dx, dgamma, dbeta, dss, None, None, None, None, None, None, None, None, None, None
 
 
-_gn_bf16_out = None      # the bf16 values of the last bf16-storage GroupNorm forward (picked up by the wrapper below)
-_gn_amax_out = None      # the max |y| slot of the last GroupNorm forward that was asked for one
-
-
-def _attach_amax(y):
-    """Hands max |y| (a device float the GroupNorm kernel wrote) to the consumer: conv2d looks for `_adm_amax` on its input."""
-    global _gn_amax_out
-    if _gn_amax_out is not None:
-        y._adm_amax, _gn_amax_out = _gn_amax_out, None
-    return y
-
-
-def _want_amax(to_conv, x):
-    return bool(to_conv) and FP16X3 and BF16X6 and COMPUTE == "f32" and x.is_cuda
-
-
-def _attach_bf16(y):
-    """Hands the bf16 values of a bf16-storage GroupNorm output to its consumer: conv2d looks for `_adm_bf16` on its input."""
-    global _gn_bf16_out
-    if _gn_bf16_out is not None:
-        y._adm_bf16, _gn_bf16_out = _gn_bf16_out, None
-    return y
+def _want_amax(to_conv) -> bool:
+    return bool(to_conv) and _fp16_format()
 
 
 def group_norm_act(x, gamma, beta, scale_shift=None, *, silu=True, drop_p=0.0, seed=0, groups=0, eps=1e-5, to_conv=False, bound=False):
@@ -1350,10 +1342,9 @@ def group_norm_act(x, gamma, beta, scale_shift=None, *, silu=True, drop_p=0.0, s
     mode the values are then written as bf16 and the returned f32 tensor is an unwritten carrier (see _GroupNormAct.forward)."""
     out16 = bool(to_conv) and bf16_storage()
     slot = getattr(scale_shift, "_adm_dss", None) if scale_shift is not None else None       # (set by affine_group())
-    wa = _want_amax(to_conv or bound, x)      # bound=True: the consumer is a conv behind a 2x2 mean (which keeps the bound)
-    y = _GroupNormAct.apply(x, gamma, beta, scale_shift, bool(silu), float(drop_p), int(seed), int(groups), float(eps), False, out16,
-                            None if slot is None else slot[0], None if slot is None else slot[1], wa)
-    return _attach_bf16(y) if out16 else (_attach_amax(y) if wa else y)
+    wa = _want_amax(to_conv or bound)         # bound=True: the consumer is a conv behind a 2x2 mean (which keeps the bound)
+    return _GroupNormAct.apply(x, gamma, beta, scale_shift, bool(silu), float(drop_p), int(seed), int(groups), float(eps), False, out16,
+                               None if slot is None else slot[0], None if slot is None else slot[1], wa)
 
 
 def group_norm_act_fork(x, gamma, beta, scale_shift=None, *, silu=True, drop_p=0.0, seed=0, groups=0, eps=1e-5, to_conv=False, bound=False):
@@ -1364,13 +1355,13 @@ def group_norm_act_fork(x, gamma, beta, scale_shift=None, *, silu=True, drop_p=0
         return group_norm_act(x, gamma, beta, scale_shift, silu=silu, drop_p=drop_p, seed=seed, groups=groups, eps=eps, to_conv=to_conv,
                               bound=bound), x
     out16 = bool(to_conv) and bf16_storage()
-    wa = _want_amax(to_conv or bound, x)
+    wa = _want_amax(to_conv or bound)
     y, xo = _GroupNormAct.apply(x, gamma, beta, scale_shift, bool(silu), float(drop_p), int(seed), int(groups), float(eps), True, out16,
                                 None, None, wa)
     a = getattr(x, "_adm_amax", None)
     if a is not None:
-        xo._adm_amax = a             # (xo is x: the skip / residual branch keeps its bound)
-    return (_attach_bf16(y) if out16 else (_attach_amax(y) if wa else y)), xo
+        xo._adm_amax = a             # (xo is x: the skip / residual branch keeps its bound; an input that is returned does not keep attributes)
+    return y, xo
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1409,7 +1400,6 @@ class AffineGroup:
     def operands(self):
         """Current [total][K] forward operand and [total] bias; re-homes the per-layer packed operands into one buffer on first use
         (or after a parameter was replaced) and refreshes the gathered bias when a parameter changed."""
-        global _pack_table
         dev = self.linears[0].weight.device
         if self.wcat is None or self.wcat.device != dev:
             self.wcat = torch.empty((self.total, self.K), device=dev, dtype=_f32)
@@ -1426,7 +1416,7 @@ class AffineGroup:
                 view.copy_(ent.fwd)
                 ent.fwd = view
                 ent.fwd16 = None
-                _pack_table = None                          # the repack table must learn the new destination
+                _invalidate_pack_table()                    # the repack table must learn the new destination
                 self.sig = None
             sig += w._version + b._version + (w.data_ptr() ^ b.data_ptr())
         if sig != self.sig:
@@ -1452,8 +1442,9 @@ class AffineGroup:
             # the LDS-tiled table kernel with ONE row: the [total][K] operand as the source of its own forward image (an in-place
             # identity) and of the [K][total] data-gradient image (adm_pack_weight's element-wise transpose: 0.50 ms; this: ~0.13)
             if self.t_table is None:
-                row = [self.wcat.data_ptr(), self.wcat.data_ptr(), self.wcat_t.data_ptr(), self.total, self.K, 1, self.total, self.K, 0, 0] + [0] * (PACK_TABLE_COLS - 10)
-                self.t_table = torch.tensor([row], dtype=torch.int64).to(self.wcat.device)
+                ent = _Packed()       # (no images; total and K are multiples of 32, so the row's padded sizes are the sizes themselves)
+                ent.fwd, ent.bwd = self.wcat, self.wcat_t
+                self.t_table = torch.tensor([_pack_row(self.wcat, ent, self.total, self.K, 1, False, 0)], dtype=torch.int64).to(self.wcat.device)
             call("adm_pack_weight_table", ptr(self.t_table), 1, (self.total // 32) * (self.K // 32))
             self.sig_t = self.sig
         return self.wcat_t
@@ -1573,6 +1564,7 @@ class _Attention(torch.autograd.Function):
             raise RuntimeError(f"qkv has {C3} channels, expected {heads * 192}")
         out = _new((B, H, W, heads * 64), qkv)
         lse = _new((B * heads, L), qkv)
+        # (not _fp16_format(): this kernel has no bf16 twin, so a qkv that came with a bound runs on it whatever BF16X6 says)
         h3 = amax is not None and ATTN_H3 and FP16X3 and COMPUTE == "f32" and (L in (32, 64, 128, 256) or (L % 256 == 0 and L <= 16384))
         with _Prof("attnh3" if h3 else "attn", 4.0 * L * L * 64 * B * heads):
             if h3:
@@ -1592,7 +1584,7 @@ class _Attention(torch.autograd.Function):
         B, H, W, _ = qkv.shape
         dqkv = _like(qkv)
         delta = _like(lse)
-        slot_a = _amax_slot(qkv) if (FP16X3 and H3_GEMM and BF16X6 and COMPUTE == "f32") else None     # max |dqkv| for the qkv conv's gradients
+        slot_a = _amax_slot(qkv) if (_fp16_format() and H3_GEMM) else None     # max |dqkv| for the qkv conv's gradients
         amax_g = _get_amax(dout) if (ctx.amax_qkv is not None and ATTN_H3_BWD) else None
         with _Prof("attnh3" if amax_g is not None else "attn", 10.0 * (H * W) ** 2 * 64 * B * ctx.heads):
             if amax_g is not None:      # both bounds at hand: the fp16 split format (attention_h3.hip)
@@ -1661,10 +1653,11 @@ class _Concat(torch.autograd.Function):
         ca, cb = a.shape[-1], b.shape[-1]
         M = a.numel() // ca
         y = _new((*a.shape[:-1], ca + cb), a)
-        global _cat_amax_out
-        _cat_amax_out = slot = _amax_slot(a) if (FP16X3 and H3_GEMM and BF16X6 and COMPUTE == "f32" and a.is_cuda) else None
+        slot = _amax_slot(a) if (_fp16_format() and H3_GEMM) else None
         # one launch for both halves; the concatenation feeds a block's 1x1 skip conv: the copy leaves the bound of what it wrote
         call("adm_concat2", ptr(a), ca, ptr(b), cb, ptr(y), M, float(scale_b), ptr(slot))
+        if slot is not None:
+            y._adm_amax = slot
         ctx.meta = (ca, cb, scale_b)
         return y
 
@@ -1705,7 +1698,7 @@ class _Fanout(torch.autograd.Function):
             out = _like(acc)
             if acc.numel() % 4 == 0:
                 last = i + 2 >= len(gs)
-                slot_a = _amax_slot(acc) if (last and FP16X3 and BF16X6 and COMPUTE == "f32") else None
+                slot_a = _amax_slot(acc) if (last and _fp16_format()) else None
                 call("adm_add3", ptr(acc), ptr(gs[i]), ptr(c), ptr(out), ptr(slot_a), acc.numel())
                 _reg_amax(out, slot_a)
                 i += 2
@@ -1728,15 +1721,8 @@ def fanout(x, n: int):
     return outs
 
 
-_cat_amax_out = None
-
-
 def concat_channels(a, b, scale_b: float = 1.0):
-    global _cat_amax_out
-    y = _Concat.apply(a, b, scale_b)
-    if _cat_amax_out is not None:
-        y._adm_amax, _cat_amax_out = _cat_amax_out, None
-    return y
+    return _Concat.apply(a, b, scale_b)
 
 
 class _Silu(torch.autograd.Function):
@@ -1803,17 +1789,14 @@ def spatial_att_gate(att, qk, h, xres):
 # ------------------------------------------------------------------------------------------------
 # layout + preconditioning
 # ------------------------------------------------------------------------------------------------
-_in_amax_out = None     # bound vector of the last _nchw_to_nhwc output (handed to nchw_to_nhwc(), as _gn_amax_out)
-
-
 def _nchw_to_nhwc(x, mul, cpad):
     B, C, H, W = x.shape
     y = _new((B, H, W, cpad), x)
     bs = 0 if (mul is None or mul.numel() == 1) else 1
-    global _in_amax_out
-    _in_amax_out = slot = _amax_slot(x) if (FP16X3 and BF16X6 and COMPUTE == "f32" and x.is_cuda) else None
+    slot = _amax_slot(x) if _fp16_format() else None
     if slot is not None:        # the UNet's input with its bound: the stem conv and its weight gradient run on the fp16 format
         call("adm_nchw_to_nhwc_amax", ptr(x), int(x.dtype == torch.float64), ptr(mul), bs, ptr(y), ptr(slot), B, C, H * W, cpad)
+        y._adm_amax = slot
     else:
         call("adm_nchw_to_nhwc", ptr(x), int(x.dtype == torch.float64), ptr(mul), bs, ptr(y), B, C, H * W, cpad)
     return y
@@ -1848,14 +1831,9 @@ def nchw_to_nhwc(x: torch.Tensor, mul: Optional[torch.Tensor], cpad: int) -> tor
     if x.dtype not in (torch.float32, torch.float64):
         x = x.to(torch.float32)
     x = x if x.is_contiguous() else x.contiguous()
-    global _in_amax_out
     if torch.is_grad_enabled() and x.requires_grad:
-        y = _NchwToNhwc.apply(x, None if mul is None else mul.detach(), cpad)
-    else:
-        y = _nchw_to_nhwc(x, mul, cpad)
-    if _in_amax_out is not None:
-        y._adm_amax, _in_amax_out = _in_amax_out, None
-    return y
+        return _NchwToNhwc.apply(x, None if mul is None else mul.detach(), cpad)
+    return _nchw_to_nhwc(x, mul, cpad)
 
 
 class _PrecondOut(torch.autograd.Function):
@@ -1881,7 +1859,7 @@ class _PrecondOut(torch.autograd.Function):
         df = dx = None
         if ctx.needs_input_grad[0]:
             df = _new((B, H, W, ldf), dout)
-            slot = _amax_slot(dout) if (FP16X3 and BF16X6 and COMPUTE == "f32") else None
+            slot = _amax_slot(dout) if _fp16_format() else None
             if slot is not None:    # the output conv's dy with its bound: its data and weight gradients run on the fp16 format
                 call("adm_precond_out_bwd_amax", ptr(dout), ptr(s), cbs, ptr(df), ldf, ptr(slot), B, C, H * W)
                 _reg_amax(df, slot)
@@ -1920,7 +1898,7 @@ class _HeadOut(torch.autograd.Function):
         dout = _chk(dout, "dout")
         B, _, H, W = dout.shape
         df = _new((B, H, W, ldf), dout)
-        slot = _amax_slot(dout) if (FP16X3 and BF16X6 and COMPUTE == "f32") else None
+        slot = _amax_slot(dout) if _fp16_format() else None
         call("adm_nhwc_to_nchw_bwd_amax", ptr(dout), ptr(df), ldf, ptr(slot), B, C, H * W)
         _reg_amax(df, slot)
         return df, None

@@ -242,9 +242,22 @@ int adm_f32_to_bf16(const float* src, unsigned short* dst, long n, hipStream_t s
 int adm_pack_weight(const float* w, float* wp_fwd, float* wp_bwd, int Co, int Ci, int ks, int Co_pad, int Ci_pad,
                     int qkv, hipStream_t stream);
 /* adm_pack_weight (+ adm_pack_weight_wino) for every layer of a model in ONE launch (used after each optimiser step).
- * table = device array of n_entries rows of 12 int64: {src, dst_fwd, dst_bwd, Co, Ci, ks*ks, Co_pad, Ci_pad, qkv, tile_begin,
- * dst_wino_fwd, dst_wino_bwd, dst_wino2d_fwd, dst_wino2d_bwd}; tile_begin = the exclusive prefix sum of (Co_pad/32)*(Ci_pad/32) in row order; total_tiles =
- * the sum; the Winograd destinations may be 0.  dst_fwd / dst_bwd are required. */
+ * table = device array of n_entries rows of 24 int64 (the PT_* names of csrc/pack_weights.hip and adm_amd/ops.py):
+ *    0 src          the OIHW / [out, in] parameter
+ *    1 fwd          wp_fwd of adm_pack_weight (required)
+ *    2 bwd          wp_bwd of adm_pack_weight (required)
+ *    3 Co, 4 Ci, 5 taps = ks*ks, 6 Co_pad, 7 Ci_pad, 8 qkv   as adm_pack_weight
+ *    9 tile_begin   exclusive prefix sum of (Co_pad/32)*(Ci_pad/32) in row order; total_tiles = the sum over all rows
+ *   10 wf, 11 wb    1-D Winograd operands of adm_pack_weight_wino (forward, data gradient)
+ *   12 w2f, 13 w2b  f32 2-D Winograd planes of adm_pack_weight_wino2d
+ *   14 w2f6, 15 w2b6   their three-term bf16 splits, as adm_split3_bf16
+ *   16 g6f, 17 g6b  three-term bf16 splits of the 1x1 operands fwd / bwd, as adm_split3_rows
+ *   18 w2fh, 19 w2bh   two-term fp16 images of scale * (2-D Winograd planes), as adm_split2_f16
+ *   20 h3_scale     that scale: the bits of a float in the low 32 bits
+ *   21 h3_flag      int* raised to 1 when a scaled weight of columns 18, 19, 22, 23 leaves the fp16 range; 0 = none
+ *   22 g6fh, 23 g6bh   two-term fp16 images of scale * (1x1 operands), as adm_split2_rows_f16
+ * Columns 10-19, 22 and 23 are destinations and may be 0 (not derived); 10-15, 18 and 19 are read for 3x3 layers only, 16, 17, 22 and 23
+ * for 1x1 layers only. */
 int adm_pack_weight_table(const long* table, int n_entries, long total_tiles, hipStream_t stream);
 /* inverse of the fwd packing for gradients: dw OIHW = (accumulate ? dw : 0) + dwp */
 int adm_unpack_wgrad(const float* dwp, float* dw, int Co, int Ci, int ks, int Co_pad, int Ci_pad, int qkv,

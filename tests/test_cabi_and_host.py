@@ -263,6 +263,71 @@ def test_selection_context_and_use_counts_host_logic():
     assert not hasattr(q, "_adm_uses")
 
 
+def test_attributes_set_in_forward_survive_apply():
+    """adm_amd.ops hands a bound vector (or the bf16 values) from a kernel to its consumer as an attribute that Function.forward
+    sets on the FRESH output tensor it returns: autograd must hand that very Python object back from apply() -- with a graph, without
+    one, and for the first of two outputs -- and a bound that is a view of its pool must stay one (ops._bound_use finds the pool
+    through ``_base``).  An input that is returned as an output is wrapped anew and keeps nothing, which is why
+    ops.group_norm_act_fork copies that bound itself.  A torch upgrade that changes any of this fails here, not as an overflow."""
+    pool = torch.zeros(8)
+
+    class Toy(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, two):
+            y = x * 2
+            y._adm_amax = pool[2:4]
+            return (y, x + 1) if two else y
+
+        @staticmethod
+        def backward(ctx, g, g2=None):
+            return g * 2, None
+
+    for requires_grad, grad_mode in ((True, True), (True, False), (False, True), (False, False)):
+        for two in (False, True):
+            x = torch.ones(3, requires_grad=requires_grad)
+            with torch.set_grad_enabled(grad_mode):
+                out = Toy.apply(x, two)
+            y = out[0] if two else out
+            assert y.requires_grad == (requires_grad and grad_mode)
+            a = getattr(y, "_adm_amax", None)
+            assert a is not None and a._base is pool and a.data_ptr() == pool[2:4].data_ptr(), (requires_grad, grad_mode, two)
+
+
+def test_repack_table_row_layout(monkeypatch):
+    """One row of adm_pack_weight_table as ops._pack_row lays it out, against the 24 columns of include/adm_hip.h written out here:
+    every image slot in its own column, the fp16 scale always, the overflow flag exactly when one of the four fp16 images exists."""
+    import struct
+    from adm_amd import ops
+    monkeypatch.setattr(ops, "_h3_flag", None)
+    images = ("wf", "wb", "w2f", "w2b", "w2f6", "w2b6", "w2fh", "w2bh", "g6f", "g6b", "g6fh", "g6bh")
+    src = torch.zeros(4)
+    ent = ops._Packed()
+    assert all(getattr(ent, n) is None for n in images + ("fwd", "bwd", "bias", "fwd16", "bwd16")) and ent.h3_off is False
+    for n in ("fwd", "bwd") + images:
+        setattr(ent, n, torch.zeros(4))
+    p = {n: getattr(ent, n).data_ptr() for n in ("fwd", "bwd") + images}
+    flag = ops._h3_flag_tensor(src).data_ptr()
+    assert len({src.data_ptr(), flag, *p.values()}) == 16
+    scale = struct.unpack("<I", struct.pack("<f", ops.H3_WSCALE))[0]
+    want = [src.data_ptr(), p["fwd"], p["bwd"], 40, 24, 9, 64, 32, 1, 7, p["wf"], p["wb"], p["w2f"], p["w2b"], p["w2f6"], p["w2b6"],
+            p["g6f"], p["g6b"], p["w2fh"], p["w2bh"], scale, flag, p["g6fh"], p["g6bh"]]
+    row = ops._pack_row(src, ent, 40, 24, 3, True, 7)
+    assert len(row) == len(want) == ops.PACK_TABLE_COLS == 24
+    for col, (got, exp) in enumerate(zip(row, want)):
+        assert got == exp, (col, got, exp)
+    # only fwd and bwd: no image column, no flag
+    bare = ops._Packed()
+    bare.fwd, bare.bwd = ent.fwd, ent.bwd
+    row = ops._pack_row(src, bare, 128, 512, 1, False, 0)
+    assert row == [src.data_ptr(), p["fwd"], p["bwd"], 128, 512, 1, 128, 512, 0, 0] + [0] * 10 + [scale, 0, 0, 0]
+    for n in images:      # each slot alone: its own column and nothing else; the flag with the fp16 images only
+        one = ops._Packed()
+        one.fwd, one.bwd = ent.fwd, ent.bwd
+        setattr(one, n, getattr(ent, n))
+        row = ops._pack_row(src, one, 128, 512, 1, False, 0)
+        assert [c for c in range(10, 24) if row[c] and c != 20] == sorted([want.index(p[n])] + ([21] if n in ("w2fh", "w2bh", "g6fh", "g6bh") else [])), n
+
+
 def test_bench_dump_outputs_samples_real_parameter_positions(tmp_path, monkeypatch):
     """bench.py --dump-outputs: the sampled positions are fixed by a seed, never fall into the alignment padding of the flat
     buffers, and map to the right entries of params / grads; the files are float32 / float64."""

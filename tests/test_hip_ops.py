@@ -805,3 +805,79 @@ def test_conv_h3_weights_follow_repack_all(ops, monkeypatch):
     _hip.call("adm_split2_f16", big.data_ptr(), torch.empty((16, 2, 32, 32), device=w.device, dtype=torch.float16).data_ptr(), 32, 32,
               ops.H3_WSCALE, flag.data_ptr())
     assert int(flag) == 1
+
+
+def test_every_weight_image_follows_repack_all(ops, monkeypatch):
+    """Every derived weight image a layer can hold -- both directions, 3x3 and 1x1, f32 planes, bf16 splits and fp16 images -- is built
+    on first use by forward and backward under the setting that needs it, and after an in-place change of the weights is refreshed by
+    the one launch of ops.repack_all() bit for bit as the per-layer pack / split kernels produce it."""
+    from adm_amd import hip as _hip
+    monkeypatch.setattr(ops, "WINO_MIN_M", 1)
+    monkeypatch.setattr(ops, "GEMM_X6_MIN_M", 1)
+    monkeypatch.setattr(ops, "WINOGRAD", True)
+    monkeypatch.setattr(ops, "_pack_registry", {})           # the table of this test holds its own layers only ...
+    monkeypatch.setattr(ops, "_pack_table", None)
+    monkeypatch.setattr(ops, "_h3_flag", None)               # ... and raises a flag of its own
+    images = ("wf", "wb", "w2f", "w2b", "w2f6", "w2b6", "w2fh", "w2bh", "g6f", "g6b", "g6fh", "g6bh")
+    x3, g3 = fill.hash_tensor((2, 64, 8, 8), "evx3", 1.0), fill.hash_tensor((2, 96, 8, 8), "evg3", 1.0)
+    x1, g1 = fill.hash_tensor((2, 128, 8, 8), "evx1", 1.0), fill.hash_tensor((2, 128, 8, 8), "evg1", 1.0)
+    layers = []
+    for name, (w2d, x6, h3), want3, want1 in (("1d", (False, True, False), {"wf", "wb"}, None),
+                                              ("f32", (True, False, False), {"w2f", "w2b"}, None),
+                                              ("x6", (True, True, False), {"w2f6", "w2b6"}, {"g6f", "g6b"}),
+                                              ("h3", (True, True, True), {"w2fh", "w2bh"}, {"g6fh", "g6bh"})):
+        monkeypatch.setattr(ops, "WINOGRAD2D", w2d)
+        monkeypatch.setattr(ops, "BF16X6", x6)
+        monkeypatch.setattr(ops, "FP16X3", h3)
+        for x, gy, shape, want in ((x3, g3, (96, 64, 3, 3), want3), (x1, g1, (128, 128, 1, 1), want1)):
+            if want is None:
+                continue
+            w = torch.nn.Parameter(dev(fill.hash_tensor(shape, f"evw{name}{shape[-1]}", 0.05)))
+            xd = nhwc(x).requires_grad_(True)
+            y = ops.conv2d(xd, w, None, amax=_amax(xd) if h3 else None)
+            if h3:      # the bound of dy, registered inside the backward pass as its producer would
+                y.register_hook(lambda g: ops._reg_amax(g, _amax(g)))
+            (y * nhwc(gy)).sum().backward()
+            pk = w._adm_packed
+            assert {n for n in images if getattr(pk, n) is not None} == want, (name, shape)
+            layers.append((name, w, pk, want))
+    with torch.no_grad():
+        for _, w, _, _ in layers:
+            w.data.mul_(1.5).add_(0.01)              # in place, as the optimiser kernel does (same storage)
+    ops.repack_all()
+    f32, bf16, f16 = torch.float32, torch.bfloat16, torch.float16
+    gpu = layers[0][1].device
+    flag = torch.zeros(1, dtype=torch.int32, device=gpu)
+
+    def made(shape, dtype, symbol, src, *args):
+        t = torch.empty(shape, device=gpu, dtype=dtype)
+        _hip.call(symbol, src.data_ptr(), t.data_ptr(), *args)
+        return t
+
+    for name, w, pk, want in layers:
+        assert w._adm_packed is pk, name
+        co, ci, ks = w.shape[0], w.shape[1], w.shape[-1]
+        cop, cip = ops.ceil32(co), ops.ceil32(ci)
+        ref = {"fwd": torch.empty((cop, ks * ks * cip), device=gpu), "bwd": torch.empty((cip, ks * ks * cop), device=gpu)}
+        _hip.call("adm_pack_weight", w.data_ptr(), ref["fwd"].data_ptr(), ref["bwd"].data_ptr(), co, ci, ks, cop, cip, 0)
+        if ks == 3:
+            ref["wf"], ref["wb"] = torch.empty((4, cop, 3, cip), device=gpu), torch.empty((4, cip, 3, cop), device=gpu)
+            _hip.call("adm_pack_weight_wino", w.data_ptr(), ref["wf"].data_ptr(), ref["wb"].data_ptr(), co, ci, cop, cip)
+            ref["w2f"], ref["w2b"] = torch.empty((16, cop, cip), device=gpu), torch.empty((16, cip, cop), device=gpu)
+            _hip.call("adm_pack_weight_wino2d", w.data_ptr(), ref["w2f"].data_ptr(), ref["w2b"].data_ptr(), co, ci, cop, cip)
+            for d in "fb":
+                src = ref["w2" + d]
+                rows, cols = src.shape[1], src.shape[2]
+                ref[f"w2{d}6"] = made((16, 3, rows, cols), bf16, "adm_split3_bf16", src, rows, cols)
+                ref[f"w2{d}h"] = made((16, 2, rows, cols), f16, "adm_split2_f16", src, rows, cols, ops.H3_WSCALE, flag.data_ptr())
+        else:
+            for d, src in (("f", ref["fwd"]), ("b", ref["bwd"])):
+                rows, cols = src.shape
+                ref[f"g6{d}"] = made((3, rows, cols), bf16, "adm_split3_rows", src, rows, cols, cols)
+                ref[f"g6{d}h"] = made((2, rows, cols), f16, "adm_split2_rows_f16", src, rows, cols, cols, ops.H3_WSCALE, flag.data_ptr())
+        for n in ("fwd", "bwd") + tuple(sorted(want)):
+            got, exp = getattr(pk, n), ref[n]
+            assert got.shape == exp.shape and got.dtype == exp.dtype, (name, n, got.shape, exp.shape)
+            assert torch.equal(got.view(torch.int32 if got.dtype == f32 else torch.int16), exp.view(torch.int32 if got.dtype == f32 else torch.int16)), (name, n)
+    assert int(flag) == 0 and (ops._h3_flag is None or int(ops._h3_flag) == 0)
+
