@@ -258,3 +258,480 @@ extern "C" int adm_swin_merge_ln_fwd(const float* x, const float* w, const float
   ADM_CHECK_LAUNCH();
   return ADM_OK;
 }
+
+// ================================================================================================
+// Backward kernels: the gradient of the window attention, of the two LayerNorm kernels, and stochastic depth.
+// ================================================================================================
+
+// ------------------------------------------------------------------------------------------------
+// Window attention, backward.  One wave (one workgroup) owns one (window, head) unit, with the forward's index arithmetic.
+// Nothing is saved by the forward: scores and softmax are recomputed.  With S = q k^T + table + mask, P = softmax(S), O = P V:
+//   dP = dO V^T      D_i = sum_j P_ij dP_ij      dS = P (dP - D)      dq = scale * dS K      dK = dS^T q      dV = P^T dO
+// Pass 1, lane = query i (K, V broadcast from LDS, q and dO in registers): row i of P and of dS go to LDS, dq to d_qkv.
+// Pass 2, lane = key j (q, dO broadcast from LDS -- they take the place of K, V): dK_j, dV_j as sums over the column j of dS, P.
+//   A real key stores them to d_qkv; a padding key's k / v ARE the qkv bias, so its dK, dV are summed (over the unit's padding
+//   keys, in token order) into the unit's partial of d_qkv_bias.
+// Fold, lane = table index: d_table[(dy + 6) * 13 + (dx + 6)] of the unit = sum of dS_ij over the pairs with i - j = (dy, dx).
+// A padded query row is never produced: its dO is zero here, which zeroes its dS row and its share of dV.
+// Per unit the partial is SWIN_PART floats: 169 table entries, 32 of dK, 32 of dV (padding keys).  swin_attn_bwd_reduce sums the
+// partials in unit order, one thread per entry: no float atomics, the same bits every run.
+// LDS per wave: 2 x 49 x 32 + 2 x 49 x 49 + table + labels = 32.7 KB, so four units are resident per CU (160 KB).
+// ------------------------------------------------------------------------------------------------
+#define SWIN_PART 240          // floats per unit partial (169 + 64, padded)
+
+struct SwinAttnBwdP {
+  const float* qkv; const float* qkv_bias; const float* table; const float* d_out;
+  float* d_qkv; float* part;
+  int B, H, W, C, heads, Ph, Pw, sh, sw, nWw, nWin;
+  long units;
+};
+
+__global__ __launch_bounds__(64) void swin_attn_bwd_kernel(SwinAttnBwdP p) {
+  __shared__ __attribute__((aligned(16))) float sA[SWIN_T * SWIN_D];          // K, then scaled q
+  __shared__ __attribute__((aligned(16))) float sB[SWIN_T * SWIN_D];          // V, then dO
+  __shared__ float sP[SWIN_T * SWIN_T];
+  __shared__ float sDS[SWIN_T * SWIN_T];
+  __shared__ float sTab[176];
+  __shared__ int sLab[64];
+  const int lane = threadIdx.x;
+  const long unit = blockIdx.x;
+  const int C3 = 3 * p.C;
+  const int head = (int)(unit % p.heads);
+  const long win = unit / p.heads;
+  const int b = (int)(win / p.nWin);
+  const int wi = (int)(win % p.nWin);
+  const int wy = wi / p.nWw, wx = wi % p.nWw;
+  const size_t img = (size_t)b * p.H * p.W;
+  const float scale = 0.17677669529663687f;      // 32 ** -0.5
+  for (int idx = lane; idx < SWIN_T * (SWIN_D / 4); idx += 64) {
+    const int t = idx >> 3, c4 = idx & 7;
+    const int sy = (wy * SWIN_WIN + t / SWIN_WIN + p.sh) % p.Ph, sx = (wx * SWIN_WIN + t % SWIN_WIN + p.sw) % p.Pw;
+    const float* src = (sy < p.H && sx < p.W) ? p.qkv + (img + (size_t)sy * p.W + sx) * C3 : p.qkv_bias;
+    const int off = head * SWIN_D + c4 * 4;
+    *reinterpret_cast<f32x4*>(&sA[t * SWIN_D + c4 * 4]) = *reinterpret_cast<const f32x4*>(src + p.C + off);
+    *reinterpret_cast<f32x4*>(&sB[t * SWIN_D + c4 * 4]) = *reinterpret_cast<const f32x4*>(src + 2 * p.C + off);
+  }
+  for (int idx = lane; idx < 169; idx += 64) sTab[idx] = p.table[(size_t)idx * p.heads + head];
+  // this lane's token, as a query in pass 1 and as a key in pass 2
+  const int t = lane < SWIN_T ? lane : 0;
+  const int ty = t / SWIN_WIN, tx = t % SWIN_WIN;
+  const int ry = wy * SWIN_WIN + ty, rx = wx * SWIN_WIN + tx;
+  const int ly = p.sh == 0 ? 0 : (ry >= p.Ph - SWIN_WIN) + (ry >= p.Ph - p.sh);
+  const int lx = p.sw == 0 ? 0 : (rx >= p.Pw - SWIN_WIN) + (rx >= p.Pw - p.sw);
+  const int lab = ly * 3 + lx;
+  sLab[lane] = lab;
+  const int sy = (ry + p.sh) % p.Ph, sx = (rx + p.sw) % p.Pw;
+  const bool tok = lane < SWIN_T;
+  const bool valid = tok && sy < p.H && sx < p.W;
+  const size_t pix = img + (size_t)sy * p.W + sx;          // used only where valid
+  __syncthreads();
+  // ---------------------------------------------------------------- pass 1: lane = query
+  // (the row's scores, then its P, live in sP; its dP, then its dS, in sDS: register arrays of 49 made the compiler spill)
+  if (tok) {
+    float q[SWIN_D], g[SWIN_D];
+    const float* src = valid ? p.qkv + pix * C3 : p.qkv_bias;
+#pragma unroll
+    for (int c4 = 0; c4 < SWIN_D / 4; ++c4) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(src + head * SWIN_D + c4 * 4);
+      f32x4 d = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (valid) d = *reinterpret_cast<const f32x4*>(p.d_out + pix * p.C + head * SWIN_D + c4 * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        q[c4 * 4 + e] = v[e] * scale;
+        g[c4 * 4 + e] = d[e];
+      }
+    }
+    float* rowP = sP + lane * SWIN_T;
+    float* rowS = sDS + lane * SWIN_T;
+    float m = -3.0e38f;
+    for (int jy = 0; jy < SWIN_WIN; ++jy) {
+#pragma unroll
+      for (int jx = 0; jx < SWIN_WIN; ++jx) {
+        const int j = jy * SWIN_WIN + jx;
+        float acc = 0.f, accp = 0.f;
+#pragma unroll
+        for (int c4 = 0; c4 < SWIN_D / 4; ++c4) {
+          const f32x4 kv = *reinterpret_cast<const f32x4*>(&sA[j * SWIN_D + c4 * 4]);
+          const f32x4 vv = *reinterpret_cast<const f32x4*>(&sB[j * SWIN_D + c4 * 4]);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            acc = fmaf(q[c4 * 4 + e], kv[e], acc);
+            accp = fmaf(g[c4 * 4 + e], vv[e], accp);
+          }
+        }
+        acc += sTab[(ty - jy + SWIN_WIN - 1) * (2 * SWIN_WIN - 1) + (tx - jx + SWIN_WIN - 1)];
+        acc += sLab[j] != lab ? -100.0f : 0.0f;
+        rowP[j] = acc;
+        rowS[j] = accp;
+        m = fmaxf(m, acc);
+      }
+    }
+    float sum = 0.f, D = 0.f;
+    for (int j = 0; j < SWIN_T; ++j) {
+      const float e = expf(rowP[j] - m);
+      rowP[j] = e;
+      sum += e;
+      D = fmaf(e, rowS[j], D);
+    }
+    const float inv = 1.0f / sum;
+    D *= inv;
+    float dq[SWIN_D];
+#pragma unroll
+    for (int d = 0; d < SWIN_D; ++d) dq[d] = 0.f;
+#pragma unroll 7
+    for (int j = 0; j < SWIN_T; ++j) {
+      const float pj = rowP[j] * inv;
+      const float ds = pj * (rowS[j] - D);
+      rowP[j] = pj;
+      rowS[j] = ds;
+#pragma unroll
+      for (int c4 = 0; c4 < SWIN_D / 4; ++c4) {
+        const f32x4 kv = *reinterpret_cast<const f32x4*>(&sA[j * SWIN_D + c4 * 4]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) dq[c4 * 4 + e] = fmaf(ds, kv[e], dq[c4 * 4 + e]);
+      }
+    }
+    if (valid) {
+      float* dst = p.d_qkv + pix * C3 + head * SWIN_D;
+#pragma unroll
+      for (int c4 = 0; c4 < SWIN_D / 4; ++c4) {
+        f32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = dq[c4 * 4 + e] * scale;
+        *reinterpret_cast<f32x4*>(dst + c4 * 4) = v;
+      }
+    }
+  }
+  __syncthreads();
+  // scaled q and dO of the unit take the place of K and V (a padding token: q = the bias, dO = 0)
+  for (int idx = lane; idx < SWIN_T * (SWIN_D / 4); idx += 64) {
+    const int tt = idx >> 3, c4 = idx & 7;
+    const int yy = (wy * SWIN_WIN + tt / SWIN_WIN + p.sh) % p.Ph, xx = (wx * SWIN_WIN + tt % SWIN_WIN + p.sw) % p.Pw;
+    const bool real = yy < p.H && xx < p.W;
+    const size_t px = img + (size_t)yy * p.W + xx;
+    const int off = head * SWIN_D + c4 * 4;
+    f32x4 qv = *reinterpret_cast<const f32x4*>((real ? p.qkv + px * C3 : p.qkv_bias) + off);
+    f32x4 gv = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (real) gv = *reinterpret_cast<const f32x4*>(p.d_out + px * p.C + off);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) qv[e] *= scale;
+    *reinterpret_cast<f32x4*>(&sA[tt * SWIN_D + c4 * 4]) = qv;
+    *reinterpret_cast<f32x4*>(&sB[tt * SWIN_D + c4 * 4]) = gv;
+  }
+  __syncthreads();
+  // ---------------------------------------------------------------- pass 2: lane = key
+  float dk[SWIN_D], dv[SWIN_D];
+#pragma unroll
+  for (int d = 0; d < SWIN_D; ++d) dk[d] = dv[d] = 0.f;
+#pragma unroll 7
+  for (int i = 0; i < SWIN_T; ++i) {
+    const float ds = sDS[i * SWIN_T + t], pr = sP[i * SWIN_T + t];
+#pragma unroll
+    for (int c4 = 0; c4 < SWIN_D / 4; ++c4) {
+      const f32x4 qv = *reinterpret_cast<const f32x4*>(&sA[i * SWIN_D + c4 * 4]);
+      const f32x4 gv = *reinterpret_cast<const f32x4*>(&sB[i * SWIN_D + c4 * 4]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        dk[c4 * 4 + e] = fmaf(ds, qv[e], dk[c4 * 4 + e]);
+        dv[c4 * 4 + e] = fmaf(pr, gv[e], dv[c4 * 4 + e]);
+      }
+    }
+  }
+  if (valid) {
+    float* dst = p.d_qkv + pix * C3 + head * SWIN_D;
+#pragma unroll
+    for (int c4 = 0; c4 < SWIN_D / 4; ++c4) {
+      *reinterpret_cast<f32x4*>(dst + p.C + c4 * 4) = f32x4{dk[c4 * 4], dk[c4 * 4 + 1], dk[c4 * 4 + 2], dk[c4 * 4 + 3]};
+      *reinterpret_cast<f32x4*>(dst + 2 * p.C + c4 * 4) = f32x4{dv[c4 * 4], dv[c4 * 4 + 1], dv[c4 * 4 + 2], dv[c4 * 4 + 3]};
+    }
+  }
+  // ---------------------------------------------------------------- fold: the unit's table partial
+  float* part = p.part + (size_t)unit * SWIN_PART;
+  for (int idx = lane; idx < 169; idx += 64) {
+    const int oy = idx / (2 * SWIN_WIN - 1) - (SWIN_WIN - 1), ox = idx % (2 * SWIN_WIN - 1) - (SWIN_WIN - 1);
+    float acc = 0.f;
+    for (int iy = 0; iy < SWIN_WIN; ++iy) {
+      const int jy = iy - oy;
+      if (jy < 0 || jy >= SWIN_WIN) continue;
+      for (int ix = 0; ix < SWIN_WIN; ++ix) {
+        const int jx = ix - ox;
+        if (jx < 0 || jx >= SWIN_WIN) continue;
+        acc += sDS[(iy * SWIN_WIN + ix) * SWIN_T + jy * SWIN_WIN + jx];
+      }
+    }
+    part[idx] = acc;
+  }
+  __syncthreads();          // q and dO have been read: their tiles now carry the padding keys' dK and dV
+  if (tok) {
+    const bool padk = !valid;
+#pragma unroll
+    for (int d = 0; d < SWIN_D; ++d) {
+      sA[lane * SWIN_D + d] = padk ? dk[d] : 0.f;
+      sB[lane * SWIN_D + d] = padk ? dv[d] : 0.f;
+    }
+  }
+  __syncthreads();
+  {
+    const float* srcp = lane < SWIN_D ? sA : sB;
+    const int c = lane & (SWIN_D - 1);
+    float acc = 0.f;
+    for (int j = 0; j < SWIN_T; ++j) acc += srcp[j * SWIN_D + c];
+    part[169 + lane] = acc;
+  }
+}
+
+// Sums the unit partials in unit order.  Thread (head, e): e < 169 -> d_table[e][head]; 169 <= e < 233 -> the K and V thirds of
+// d_qkv_bias (the Q third is zero: a padding token is never a query).  acc_*: add to what the destination holds.
+__global__ __launch_bounds__(256) void swin_attn_bwd_reduce(const float* __restrict__ part, float* __restrict__ d_table,
+                                                            float* __restrict__ d_bias, long groups, int heads, int C,
+                                                            int acc_table, int acc_bias) {
+  const int gid = blockIdx.x * 256 + threadIdx.x;
+  if (gid >= heads * SWIN_PART) return;
+  const int head = gid / SWIN_PART, e = gid % SWIN_PART;
+  if (e >= 169 + 2 * SWIN_D) return;
+  float acc = 0.f;
+  for (long n = 0; n < groups; ++n) acc += part[(size_t)(n * heads + head) * SWIN_PART + e];
+  if (e < 169) {
+    float* dst = d_table + (size_t)e * heads + head;
+    *dst = acc_table ? *dst + acc : acc;
+  } else {
+    const int c = e - 169;                                   // [0, 32): dK, [32, 64): dV
+    float* dst = d_bias + (c < SWIN_D ? C : 2 * C - SWIN_D) + head * SWIN_D + c;
+    *dst = acc_bias ? *dst + acc : acc;
+    if (c < SWIN_D && !acc_bias) d_bias[head * SWIN_D + c] = 0.f;
+  }
+}
+
+extern "C" long adm_swin_attn_bwd_ws_floats(int B, int H, int W, int heads) {
+  if (B <= 0 || H <= 0 || W <= 0 || heads <= 0) return 0;
+  const long nWin = (long)((H + SWIN_WIN - 1) / SWIN_WIN) * ((W + SWIN_WIN - 1) / SWIN_WIN);
+  return (long)B * nWin * heads * SWIN_PART;
+}
+
+extern "C" int adm_swin_attn_bwd(const float* qkv, const float* qkv_bias, const float* table, const float* d_out, float* d_qkv,
+                                 float* d_table, float* d_qkv_bias, float* ws, int B, int H, int W, int C, int heads, int window,
+                                 int shift_h, int shift_w, int acc_table, int acc_bias, hipStream_t stream) {
+  if (!qkv || !qkv_bias || !table || !d_out || !d_qkv || !d_table || !d_qkv_bias || !ws) return ADM_EINVAL;
+  if (B <= 0 || H <= 0 || W <= 0 || heads <= 0) return ADM_EINVAL;
+  if (window != SWIN_WIN || C != heads * SWIN_D) return ADM_EINVAL;
+  if (shift_h < 0 || shift_h >= SWIN_WIN || shift_w < 0 || shift_w >= SWIN_WIN) return ADM_EINVAL;
+  if (((uintptr_t)qkv | (uintptr_t)qkv_bias | (uintptr_t)d_out | (uintptr_t)d_qkv) & 15) return ADM_EINVAL;
+  SwinAttnBwdP p;
+  p.qkv = qkv; p.qkv_bias = qkv_bias; p.table = table; p.d_out = d_out; p.d_qkv = d_qkv; p.part = ws;
+  p.B = B; p.H = H; p.W = W; p.C = C; p.heads = heads;
+  p.Ph = (H + SWIN_WIN - 1) / SWIN_WIN * SWIN_WIN;
+  p.Pw = (W + SWIN_WIN - 1) / SWIN_WIN * SWIN_WIN;
+  p.sh = p.Ph > SWIN_WIN ? shift_h : 0;
+  p.sw = p.Pw > SWIN_WIN ? shift_w : 0;
+  p.nWw = p.Pw / SWIN_WIN;
+  p.nWin = (p.Ph / SWIN_WIN) * p.nWw;
+  p.units = (long)B * p.nWin * heads;
+  if (p.units > 0x7fffffffL) return ADM_EINVAL;
+  hipLaunchKernelGGL(swin_attn_bwd_kernel, dim3((unsigned)p.units), dim3(64), 0, stream, p);
+  ADM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(swin_attn_bwd_reduce, dim3((unsigned)adm_cdiv((long)heads * SWIN_PART, 256)), dim3(256), 0, stream, ws, d_table,
+                     d_qkv_bias, (long)B * p.nWin, heads, C, acc_table, acc_bias);
+  ADM_CHECK_LAUNCH();
+  return ADM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// LayerNorm, backward.  With xh = (x - mean) * rstd (the forward's shifted two-pass statistics, recomputed) and g = dy * w:
+//   dx = rstd * (g - mean(g) - xh * mean(g * xh))        dw = sum over rows of dy * xh        db = sum over rows of dy
+// One wave per row; a wave walks rows wave, wave + NW, ... and keeps its dw / db share in registers, then writes it as the partial
+// part[wave][2][C].  ln_bwd_reduce sums the NW partials in wave order (no atomics).  MERGE: x is gathered from the 2x2 cell as in
+// the forward and dx goes back through the same gather -- every source pixel has one destination, a position past an odd edge none.
+// ------------------------------------------------------------------------------------------------
+#define LN_BWD_MAXBLOCKS 256
+
+static long ln_bwd_blocks(long M) {
+  long b = (M + 4 * LN_ROWS - 1) / (4 * LN_ROWS);          // >= 4 rows per wave
+  return b < 1 ? 1 : b > LN_BWD_MAXBLOCKS ? LN_BWD_MAXBLOCKS : b;
+}
+
+extern "C" long adm_ln_bwd_ws_floats(long M, int C) { return M <= 0 || C <= 0 ? 0 : ln_bwd_blocks(M) * LN_ROWS * 2 * (long)C; }
+
+template <bool MERGE, int NQ>
+__global__ __launch_bounds__(LN_ROWS * 64) void ln_affine_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                     const float* __restrict__ dy, float* __restrict__ dx,
+                                                                     float* __restrict__ part, long M, int C, float eps, int H,
+                                                                     int W, int Cin) {
+  const int lane = threadIdx.x & 63;
+  const long wave = (long)blockIdx.x * LN_ROWS + (threadIdx.x >> 6);
+  const long NW = (long)gridDim.x * LN_ROWS;
+  const int C4 = C >> 2;
+  const int Ho = (H + 1) >> 1, Wo = (W + 1) >> 1;
+  f32x4 aw[NQ], ab[NQ];
+#pragma unroll
+  for (int it = 0; it < NQ; ++it) aw[it] = ab[it] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (long row = wave; row < M; row += NW) {
+    int oy = 0, ox = 0;
+    long b = 0;
+    if (MERGE) {
+      b = row / ((long)Ho * Wo);
+      const int r = (int)(row % ((long)Ho * Wo));
+      oy = r / Wo; ox = r % Wo;
+    }
+    f32x4 v[NQ], d[NQ];
+    long src[NQ];          // element offset of this lane's quad in x / dx, -1: past the edge
+#pragma unroll
+    for (int it = 0; it < NQ; ++it) {
+      const int i4 = lane + 64 * it;
+      v[it] = d[it] = f32x4{0.f, 0.f, 0.f, 0.f};
+      src[it] = -1;
+      if (i4 < C4) {
+        if (MERGE) {
+          const int c = i4 * 4, quad = c / Cin, ci = c - quad * Cin;
+          const int iy = 2 * oy + (quad & 1), ix = 2 * ox + (quad >> 1);
+          if (iy < H && ix < W) src[it] = (long)((((size_t)b * H + iy) * W + ix) * Cin + ci);
+        } else {
+          src[it] = (long)((size_t)row * C + (size_t)i4 * 4);
+        }
+        if (src[it] >= 0) v[it] = *reinterpret_cast<const f32x4*>(x + src[it]);
+        d[it] = *reinterpret_cast<const f32x4*>(dy + (size_t)row * C + (size_t)i4 * 4);
+      }
+    }
+    const float x0 = __shfl(v[0][0], 0, 64);
+    float sum = 0.f;
+#pragma unroll
+    for (int it = 0; it < NQ; ++it) {
+      if (lane + 64 * it < C4) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[it][e] -= x0;
+        sum += (v[it][0] + v[it][1]) + (v[it][2] + v[it][3]);
+      }
+    }
+    const float mean = wave_sum(sum) / (float)C;
+    float sq = 0.f;
+#pragma unroll
+    for (int it = 0; it < NQ; ++it) {
+      if (lane + 64 * it < C4) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          v[it][e] -= mean;
+          sq = fmaf(v[it][e], v[it][e], sq);
+        }
+      }
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)C + eps);
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int it = 0; it < NQ; ++it) {
+      if (lane + 64 * it < C4) {
+        const f32x4 g = *reinterpret_cast<const f32x4*>(w + (lane + 64 * it) * 4);          // (from cache: every row re-reads it)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          v[it][e] *= rstd;                                  // xh
+          aw[it][e] = fmaf(d[it][e], v[it][e], aw[it][e]);
+          ab[it][e] += d[it][e];
+          d[it][e] *= g[e];                                  // from here on: dy * w
+          s1 += d[it][e];
+          s2 = fmaf(d[it][e], v[it][e], s2);
+        }
+      }
+    }
+    const float m1 = wave_sum(s1) / (float)C, m2 = wave_sum(s2) / (float)C;
+#pragma unroll
+    for (int it = 0; it < NQ; ++it) {
+      if (lane + 64 * it < C4 && src[it] >= 0) {
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = rstd * (d[it][e] - m1 - v[it][e] * m2);
+        *reinterpret_cast<f32x4*>(dx + src[it]) = o;
+      }
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < NQ; ++it) {
+    const int i4 = lane + 64 * it;
+    if (i4 < C4) {
+      *reinterpret_cast<f32x4*>(part + (size_t)wave * 2 * C + (size_t)i4 * 4) = aw[it];
+      *reinterpret_cast<f32x4*>(part + (size_t)wave * 2 * C + C + (size_t)i4 * 4) = ab[it];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void ln_bwd_reduce(const float* __restrict__ part, float* __restrict__ dw, float* __restrict__ db,
+                                                     long NW, int C, int acc) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 2 * C) return;
+  float s = 0.f;
+  for (long n = 0; n < NW; ++n) s += part[(size_t)n * 2 * C + i];
+  float* dst = i < C ? dw + i : db + (i - C);
+  *dst = acc ? *dst + s : s;
+}
+
+template <bool MERGE>
+static void ln_bwd_launch(const float* x, const float* w, const float* dy, float* dx, float* part, long M, int C, float eps, int H,
+                          int W, int Cin, unsigned blocks, hipStream_t stream) {
+  const int q = (C / 4 + 63) / 64;
+#define LN_GO(NQ) hipLaunchKernelGGL((ln_affine_bwd_kernel<MERGE, NQ>), dim3(blocks), dim3(LN_ROWS * 64), 0, stream, x, w, dy, dx, part, M, C, eps, H, W, Cin)
+  if (q <= 1) LN_GO(1);
+  else if (q <= 2) LN_GO(2);
+  else if (q <= 4) LN_GO(4);
+  else LN_GO(8);
+#undef LN_GO
+}
+
+extern "C" int adm_ln_affine_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, float* ws,
+                                 long M, int C, float eps, int accumulate, hipStream_t stream) {
+  if (!x || !w || !dy || !dx || !dw || !db || !ws || M <= 0 || C < 32 || C > 64 * LN_MAXQ * 4 || (C & 3)) return ADM_EINVAL;
+  if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)ws) & 15) return ADM_EINVAL;
+  const long blocks = ln_bwd_blocks(M);
+  ln_bwd_launch<false>(x, w, dy, dx, ws, M, C, eps, 0, 0, 0, (unsigned)blocks, stream);
+  ADM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(ln_bwd_reduce, dim3((unsigned)adm_cdiv(2L * C, 256)), dim3(256), 0, stream, ws, dw, db, blocks * LN_ROWS, C,
+                     accumulate);
+  ADM_CHECK_LAUNCH();
+  return ADM_OK;
+}
+
+extern "C" int adm_swin_merge_ln_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, float* ws,
+                                     int B, int H, int W, int C, float eps, int accumulate, hipStream_t stream) {
+  if (!x || !w || !dy || !dx || !dw || !db || !ws || B <= 0 || H <= 0 || W <= 0 || C < 8 || (C & 3) || 4 * C > 64 * LN_MAXQ * 4)
+    return ADM_EINVAL;
+  if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)ws) & 15) return ADM_EINVAL;
+  const long M = (long)B * ((H + 1) / 2) * ((W + 1) / 2);
+  const long blocks = ln_bwd_blocks(M);
+  ln_bwd_launch<true>(x, w, dy, dx, ws, M, 4 * C, eps, H, W, C, (unsigned)blocks, stream);
+  ADM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(ln_bwd_reduce, dim3((unsigned)adm_cdiv(8L * C, 256)), dim3(256), 0, stream, ws, dw, db, blocks * LN_ROWS, 4 * C,
+                     accumulate);
+  ADM_CHECK_LAUNCH();
+  return ADM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Stochastic depth in "row" mode: y[b, :] = x[b, :] + s[b] * r[b, :], s[b] = keep_b / (1 - p) drawn by the caller.  x == nullptr:
+// y = s[b] * r, the gradient of the branch.  A dropped row (s[b] == 0) copies x, bit for bit.  n = elements per sample, n % 4 == 0.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rowscale_add_kernel(const float* __restrict__ x, const float* __restrict__ r,
+                                                           const float* __restrict__ s, float* __restrict__ y, long n4, long total4) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total4) return;
+  const float sc = s[i / n4];
+  const f32x4 rv = reinterpret_cast<const f32x4*>(r)[i];
+  f32x4 o;
+  if (x) {
+    o = reinterpret_cast<const f32x4*>(x)[i];
+    if (sc != 0.f) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = fmaf(sc, rv[e], o[e]);
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = sc == 0.f ? 0.f : sc * rv[e];
+  }
+  reinterpret_cast<f32x4*>(y)[i] = o;
+}
+
+extern "C" int adm_rowscale_add(const float* x, const float* r, const float* s, float* y, int B, long n, hipStream_t stream) {
+  if (!r || !s || !y || B <= 0 || n <= 0 || (n & 3)) return ADM_EINVAL;
+  if (((uintptr_t)x | (uintptr_t)r | (uintptr_t)y) & 15) return ADM_EINVAL;
+  const long total4 = (long)B * (n / 4);
+  const long blocks = (total4 + 255) / 256;
+  if (blocks > 0x7fffffffL) return ADM_EINVAL;
+  hipLaunchKernelGGL(rowscale_add_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, r, s, y, n / 4, total4);
+  ADM_CHECK_LAUNCH();
+  return ADM_OK;
+}

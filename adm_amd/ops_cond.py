@@ -241,9 +241,40 @@ def bilinear(x, Ho: int, Wo: int, align_corners: bool):
     return _Bilinear.apply(x, int(Ho), int(Wo), bool(align_corners))
 
 
+class _BilinearInto(torch.autograd.Function):
+    """bilinear_into with a gradient for x (a condition feature whose encoder trains): y is written in place; backward gathers
+    channels [coff, coff + C) of dy back to x's grid and hands dy on to whatever produced y's other channels."""
+
+    @staticmethod
+    def forward(ctx, x, y, coff, align):
+        x = _chk(x, "x")
+        B, Hi, Wi, C = x.shape
+        call("adm_bilinear_fwd", ptr(x), ptr(y), B, Hi, Wi, y.shape[1], y.shape[2], C, y.shape[3], coff, int(align))
+        ctx.mark_dirty(y)
+        ctx.meta = (B, Hi, Wi, C, coff, align)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, Hi, Wi, C, coff, align = ctx.meta
+        dy = _chk(dy, "dy")
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = _new((B, Hi, Wi, C), dy)
+            src, ld, off = dy, dy.shape[3], coff
+            if coff & 3:          # the gather reads float4: the stem's slice starts at channel 3, so it is copied out first
+                src, ld, off = dy[..., coff:coff + C].contiguous(), C, 0
+            call("adm_bilinear_bwd", ptr(src), ptr(dx), B, Hi, Wi, dy.shape[1], dy.shape[2], C, ld, off, int(align))
+        return dx, dy, None, None
+
+
 def bilinear_into(x, y, coff: int, align_corners: bool):
-    """No-grad: writes the resized x into channels [coff, coff + C) of the NHWC tensor y (the stem's concatenation of the
-    latent with the up-sampled condition feature, cond_unet_sd.py:824)."""
+    """Writes the resized x into channels [coff, coff + C) of the NHWC tensor y (the stem's concatenation of the latent with the
+    up-sampled condition feature, cond_unet_sd.py:824).  Without a gradient unless x requires one (a trainable encoder)."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        if not y.is_contiguous():
+            raise RuntimeError("bilinear_into: the destination must be contiguous")
+        return _BilinearInto.apply(x, y, int(coff), bool(align_corners))
     B, Hi, Wi, C = x.shape
     call("adm_bilinear_fwd", ptr(_chk(x, "x")), ptr(y), B, Hi, Wi, y.shape[1], y.shape[2], C, y.shape[3], int(coff),
          int(align_corners))

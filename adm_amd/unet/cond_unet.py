@@ -13,8 +13,9 @@ Reference lines restated: BasicAttetnionLayer :152-238, RelationNet :240-279, We
 the second decoder).
 
 The condition ENCODER ``init_conv_mask`` (cond_unet_sd.py:637-650): ``cond_encoder="swin_b"`` builds the Swin-B backbone of
-``adm_amd.unet.swin_transformer`` (forward only, frozen: the reference's ``fix_bb: True`` state; its weights come from the
-checkpoint's ``init_conv_mask.*`` tensors, nothing is fetched).  EfficientNet-B7, ResNet-101 and the single-channel Swin variant
+``adm_amd.unet.swin_transformer`` (frozen by default: the reference's ``fix_bb: True`` state; ``train_cond_encoder=True``, also as
+a key of the YAML's ``unet:`` section, calls its ``enable_training()`` so that it trains with the denoiser as under the reference's
+``fix_bb: False``; its weights come from the checkpoint's ``init_conv_mask.*`` tensors, nothing is fetched).  EfficientNet-B7, ResNet-101 and the single-channel Swin variant
 are not built.  With ``cond_encoder=None`` (the default) the encoder's output -- four feature maps of f, 2f, 4f, 8f channels
 (f = 128 for Swin-B) at 1/4, 1/8, 1/16, 1/32 of the condition image -- is what ``forward`` takes as ``mask`` (a list of four NCHW
 tensors); a user-supplied ``cond_encoder`` callable returns it for the condition image.
@@ -292,7 +293,8 @@ class Unet(nn.Module):
                  cond_dim_mults=(2, 4, 8), channels=1, out_mul=1, self_condition=False, resnet_block_groups=8,
                  learned_variance=False, learned_sinusoidal_cond=False, random_fourier_features=False, learned_sinusoidal_dim=16,
                  window_sizes1=((16, 16), (8, 8), (4, 4), (2, 2)), window_sizes2=((16, 16), (8, 8), (4, 4), (2, 2)),
-                 fourier_scale=16, precondition=True, ckpt_path=None, ignore_keys=(), cfg=None, cond_encoder=None, **kwargs):
+                 fourier_scale=16, precondition=True, ckpt_path=None, ignore_keys=(), cfg=None, cond_encoder=None, train_cond_encoder=False,
+                 **kwargs):
         super().__init__()
         if self_condition or learned_variance or learned_sinusoidal_cond or random_fourier_features or out_mul != 1:
             raise NotImplementedError("self_condition / learned_variance / learned sinusoidal embeddings / out_mul != 1 are not "
@@ -315,6 +317,12 @@ class Unet(nn.Module):
             if kwargs.get("single_channel_cond", False):
                 raise NotImplementedError("single_channel_cond (swin_transformer_for_sci) is not built")
             cond_encoder = swin_b(fix_bb=bool(kwargs.get("fix_bb", False)))
+            if train_cond_encoder:
+                if cond_encoder.fix_bb:
+                    raise ValueError("train_cond_encoder=True contradicts fix_bb=True (a fixed backbone is not trained)")
+                cond_encoder.enable_training()          # before any FlatParams is built: its tensors join the flat buffer
+        elif train_cond_encoder:
+            raise ValueError("train_cond_encoder=True needs the built-in encoder (cond_encoder='swin_b')")
         self.init_conv_mask = cond_encoder
         init_dim = init_dim if init_dim is not None else dim
         if dim % 32 or init_dim % 32:
@@ -435,7 +443,7 @@ class Unet(nn.Module):
         # stem input: [latent (channels) | bilinear(hm[0]) (f)] in ONE NHWC tensor padded to a multiple of 32 channels
         cin = ops.ceil32(Cx + self.f_cond)
         xin = ops.nchw_to_nhwc(x, None, cin)
-        oc.bilinear_into(hm[0], xin, Cx, False)
+        xin = oc.bilinear_into(hm[0], xin, Cx, False)
         h0 = oc.conv2d_generic(xin, self.init_conv[0].weight, self.init_conv[0].bias, stride=1, pad=3)
         gn = self.init_conv[1]
         xx = ops.group_norm_act(h0, gn.weight, gn.bias, None, silu=False, groups=gn.num_groups, eps=gn.eps)

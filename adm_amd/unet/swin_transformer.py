@@ -1,16 +1,20 @@
 """MI355X-native Swin condition encoder behind the reference's module API: the ``init_conv_mask`` of the conditional denoisers
 (/root/reference/unet/swin_transformer.py, built at cond_unet_sd.py:637-650 and cond_unet.py of the reference as ``swin_b``).
 
-FORWARD ONLY.  Same constructor keywords, same module tree and therefore the same ``state_dict()`` names and shapes (torch.nn
+Same constructor keywords, same module tree and therefore the same ``state_dict()`` names and shapes (torch.nn
 modules are PARAMETER HOLDERS: ``first_coonv`` (sic), ``features.{0..6}``, and the never-used ``norm`` / ``head`` so that a strict
 load of a reference checkpoint passes).  ``forward(x)`` takes the NCHW condition image and returns the four stage outputs as
 NCHW maps (E, 2E, 4E, 8E channels at 1/4 ... 1/32), computed on HIP kernels: the fused shifted-window attention, LayerNorm and
 PatchMerging kernels of csrc/swin.hip around the GEMM / GELU / residual kernels of ``adm_amd.ops`` -- there is no PyTorch fallback.
 
-What is NOT built: the backward pass.  Every parameter is created with ``requires_grad=False`` (the reference's own
-``fix_bb: True`` state, which every shipped conditional recipe uses), the forward always runs without grad and with eval
-semantics (stochastic depth and the dropouts are identities), and nothing is ever fetched: the weights come from the
-checkpoint of the conditional model.  The single-channel variant, EfficientNet-B7 and ResNet-101 are not built either.
+FROZEN BY DEFAULT, TRAINING IS OPT-IN.  Every parameter is created with ``requires_grad=False`` (the reference's own
+``fix_bb: True`` state) and the forward runs without grad and with eval semantics, until ``enable_training()`` is called:
+that sets ``requires_grad`` on every parameter ``forward`` uses (``norm.*`` / ``head.*`` stay frozen: they are never used, the
+reference leaves their ``.grad`` at None), makes ``forward`` run with grad through the HIP backward kernels of
+``adm_amd.ops_swin``, and switches stochastic depth on in ``.train()`` mode: torchvision's ``StochasticDepth(p_k, "row")`` around
+both branches of block k, p_k = p * k / (n_blocks - 1) (reference :292,303-304,379), restated in ``ops_swin.row_scale_add``.
+Nothing is ever fetched: the weights come from the checkpoint of the conditional model.  Attention / output dropout (0.0 in
+every config), the single-channel variant, EfficientNet-B7 and ResNet-101 are not built.
 
 Reference lines restated: PatchMerging :51-68, shifted_window_attention :71-168, ShiftedWindowAttention :174-248,
 SwinTransformerBlock :251-305, SwinTransformer :308-425.
@@ -23,7 +27,7 @@ from typing import List, Optional
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import hip, ops
 from .. import ops_cond as oc
 from .. import ops_swin as osw
 
@@ -97,10 +101,15 @@ class SwinTransformerBlock(nn.Module):
                                            dropout=dropout)
         self.norm2 = norm_layer(dim)
         self.mlp = MLP(dim, int(dim * mlp_ratio), dropout)
+        self.sd_prob = 0.0          # set by SwinTransformer.enable_training(); the constructor's value is kept there
 
-    def forward(self, x):
-        x = self.attn(osw.layer_norm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps), residual=x)
-        return self.mlp(osw.layer_norm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps), residual=x)
+    def forward(self, x, scales=None):
+        """scales: None (both branches join through the GEMM's fused residual) or the two [B] row scales keep / (1 - p) of
+        stochastic depth, attention branch first."""
+        h = osw.layer_norm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)
+        x = self.attn(h, residual=x) if scales is None else osw.row_scale_add(x, self.attn(h), scales[0])
+        h = osw.layer_norm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps)
+        return self.mlp(h, residual=x) if scales is None else osw.row_scale_add(x, self.mlp(h), scales[1])
 
 
 class SwinTransformer(nn.Module):
@@ -115,6 +124,8 @@ class SwinTransformer(nn.Module):
             raise NotImplementedError("custom norm_layer / block classes are not supported")
         norm_layer = lambda d: nn.LayerNorm(d, eps=1e-5)
         self.num_classes, self.fix_bb = num_classes, fix_bb
+        self.stochastic_depth_prob = float(stochastic_depth_prob)      # used only after enable_training()
+        self.trainable = False
         self._warned = False
         self.first_coonv = nn.Sequential(nn.Conv2d(3, embed_dim, kernel_size=4, stride=4), nn.Identity(), norm_layer(embed_dim))
         layers: List[nn.Module] = []
@@ -132,7 +143,7 @@ class SwinTransformer(nn.Module):
         self.norm = norm_layer(num_features)              # norm / head: never used by forward (reference :419-424), kept as holders
         self.head = nn.Linear(num_features, num_classes)
         self._init_weights()
-        for p in self.parameters():                        # frozen: the backward pass is not part of this build
+        for p in self.parameters():                        # frozen until enable_training()
             p.requires_grad_(False)
 
     def _init_weights(self):
@@ -147,22 +158,73 @@ class SwinTransformer(nn.Module):
             nn.init.trunc_normal_(self.head.weight, std=0.02)
             self.head.bias.zero_()
 
-    @torch.no_grad()
-    def forward(self, x):
-        if self.training and not self.fix_bb and not self._warned:
+    def blocks(self) -> List[SwinTransformerBlock]:
+        """The transformer blocks in running order (the index k of p_k)."""
+        return [b for i, stage in enumerate(self.features) if i % 2 == 0 for b in stage]
+
+    def enable_training(self, stochastic_depth_prob: Optional[float] = None):
+        """Make the encoder trainable (the reference's ``fix_bb: False``): requires_grad on every parameter ``forward`` uses
+        (not ``norm.*`` / ``head.*``), ``forward`` with grad, and in ``.train()`` mode stochastic depth with
+        p_k = stochastic_depth_prob * k / (n_blocks - 1) for block k.  None = the constructor's ``stochastic_depth_prob``
+        (0.5 for ``swin_b()``, as in the reference); 0.0 switches stochastic depth off.  Call it before the optimiser's flat
+        parameter buffer is built."""
+        p = self.stochastic_depth_prob if stochastic_depth_prob is None else float(stochastic_depth_prob)
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"stochastic_depth_prob must be in [0, 1), got {p}")
+        blocks = self.blocks()
+        for k, b in enumerate(blocks):
+            b.sd_prob = p * float(k) / max(len(blocks) - 1, 1)
+        for name, q in self.named_parameters():
+            q.requires_grad_(not (name.startswith("norm.") or name.startswith("head.")))
+        self.trainable = True
+        return self
+
+    def draw_keep(self, batch: int, device) -> torch.Tensor:
+        """[n_blocks, 2, batch] of 0. / 1.: the Bernoulli(1 - p_k) draws of one training forward (attention branch, MLP branch),
+        from the device's generator."""
+        p = torch.tensor([b.sd_prob for b in self.blocks()], device=device, dtype=torch.float32)
+        return (torch.rand(p.numel(), 2, batch, device=device) >= p[:, None, None]).to(torch.float32)
+
+    def forward(self, x, keep=None):
+        """keep: the stochastic-depth draws ([n_blocks, 2, B] of 0 / 1; block k, branch, sample) in place of ``draw_keep()``:
+        injectable for tests, used only by a trainable module in ``.train()`` mode and only where p_k > 0."""
+        if not self.trainable:
+            if keep is not None:
+                raise RuntimeError("SwinTransformer: `keep` needs enable_training()")
+            with torch.no_grad():
+                return self._forward(x, None)
+        return self._forward(x, keep)
+
+    def _forward(self, x, keep):
+        if self.training and not self.fix_bb and not self.trainable and not self._warned:
             self._warned = True
-            warnings.warn("SwinTransformer: the backbone is frozen in this build (forward only, eval semantics); fix_bb: False "
-                          "training of the condition encoder is not implemented")
+            warnings.warn("SwinTransformer: the backbone is frozen in this build (forward only, eval semantics) until "
+                          "enable_training() is called (Unet(..., train_cond_encoder=True)); fix_bb: False alone does not train it")
         if x.dim() != 4 or x.shape[1] != 3:
             raise RuntimeError(f"the condition encoder takes an NCHW image with 3 channels, got {tuple(x.shape)}")
+        blocks = self.blocks()
+        scales = None
+        if self.trainable and self.training and any(b.sd_prob > 0.0 for b in blocks):
+            hip.require_cuda(x, "x")
+            if keep is None:
+                keep = self.draw_keep(x.shape[0], x.device)
+            if tuple(keep.shape) != (len(blocks), 2, x.shape[0]):
+                raise RuntimeError(f"keep must be [{len(blocks)}, 2, {x.shape[0]}], got {tuple(keep.shape)}")
+            inv = torch.tensor([1.0 / (1.0 - b.sd_prob) for b in blocks], device=x.device, dtype=torch.float32)
+            scales = (keep.to(device=x.device, dtype=torch.float32) * inv[:, None, None]).contiguous()
         conv, ln = self.first_coonv[0], self.first_coonv[2]
         h = oc.conv2d_generic(ops.nchw_to_nhwc(x.contiguous(), None, 32), conv.weight, conv.bias, stride=4, pad=0)
         h = osw.layer_norm(h, ln.weight, ln.bias, ln.eps)
         feats = []
+        k = 0
         for i, layer in enumerate(self.features):
-            h = layer(h)
-            if i % 2 == 0:
-                feats.append(osw.nhwc_to_nchw(h))
+            if i % 2:
+                h = layer(h)
+                continue
+            for b in layer:
+                h = b(h, None if scales is None or b.sd_prob <= 0.0 else scales[k])
+                k += 1
+            feats.append(osw.nhwc_to_nchw(h))
         return feats
 
 
@@ -170,4 +232,4 @@ def swin_b(**kwargs) -> SwinTransformer:
     """Swin-B: 4x4 patches, width 128, depths [2, 2, 18, 2], heads [4, 8, 16, 32], 7x7 windows.  No ``weights=`` argument: nothing
     is ever fetched, the tensors come from the conditional model's checkpoint."""
     return SwinTransformer(patch_size=[4, 4], embed_dim=128, depths=[2, 2, 18, 2], num_heads=[4, 8, 16, 32], window_size=[7, 7],
-                           **kwargs)
+                           **{"stochastic_depth_prob": 0.5, **kwargs})          # 0.5: reference :612-645, used after enable_training()

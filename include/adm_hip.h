@@ -695,6 +695,34 @@ int adm_ln_affine_fwd(const float* x, const float* w, const float* b, float* y, 
 int adm_swin_merge_ln_fwd(const float* x, const float* w, const float* b, float* y, int B, int H, int W, int C, float eps,
                           hipStream_t stream);
 
+/* ================================================================================================
+ * Backward of the Swin condition encoder (csrc/swin.hip).  No float atomics: every sum over units / rows goes through partials in
+ * the caller's workspace and a second kernel that adds them in a fixed order, so the results are the same bits every run.
+ * ================================================================================================ */
+
+/* Gradient of adm_swin_attn_fwd (same geometry arguments; scores and softmax are recomputed, nothing is saved by the forward).
+ * d_out [B][H][W][C] -> d_qkv [B][H][W][3C] (every element written), d_table [169][heads], d_qkv_bias [3C].  A padding token is a
+ * key / value equal to qkv_bias, so its dK and dV go to the K and V thirds of d_qkv_bias (the Q third is zero); the share of the
+ * real tokens reaches the bias through the qkv Linear's own backward.  acc_table / acc_bias != 0: add to what d_table / d_qkv_bias
+ * hold.  ws: adm_swin_attn_bwd_ws_floats(B, H, W, heads) floats (need not be cleared). */
+long adm_swin_attn_bwd_ws_floats(int B, int H, int W, int heads);
+int adm_swin_attn_bwd(const float* qkv, const float* qkv_bias, const float* table, const float* d_out, float* d_qkv, float* d_table,
+                      float* d_qkv_bias, float* ws, int B, int H, int W, int C, int heads, int window, int shift_h, int shift_w,
+                      int acc_table, int acc_bias, hipStream_t stream);
+/* Gradients of adm_ln_affine_fwd: dx [M][C], dw [C], db [C] from x, w and dy; the row statistics are recomputed in the forward's
+ * shifted two-pass form.  accumulate != 0: add to what dw / db hold.  ws: adm_ln_bwd_ws_floats(M, C) floats. */
+long adm_ln_bwd_ws_floats(long M, int C);
+int adm_ln_affine_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, float* ws, long M, int C,
+                      float eps, int accumulate, hipStream_t stream);
+/* Gradients of adm_swin_merge_ln_fwd: dy [B][ceil(H/2)][ceil(W/2)][4C] -> dx [B][H][W][C] (scattered back through the 2x2 gather:
+ * every pixel has one destination, positions past an odd edge are dropped), dw, db [4C].
+ * ws: adm_ln_bwd_ws_floats(B * ceil(H/2) * ceil(W/2), 4C) floats. */
+int adm_swin_merge_ln_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, float* ws, int B, int H,
+                          int W, int C, float eps, int accumulate, hipStream_t stream);
+/* Stochastic depth in "row" mode: y[b][i] = x[b][i] + s[b] * r[b][i] for B samples of n elements (n % 4 == 0), s[b] = keep_b /
+ * (1 - p).  x == NULL: y = s[b] * r (the gradient of the branch).  A row with s[b] == 0 copies x bit for bit. */
+int adm_rowscale_add(const float* x, const float* r, const float* s, float* y, int B, long n, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,14 @@ counter pass of its own, merged into the same file afterwards:
 (one launch of each kernel at stage 1 of the same batch; FETCH_SIZE / WRITE_SIZE are in KB, and on gfx950 FETCH_SIZE reports
 half the bytes of wide coalesced reads -- tools/summarize_profiles.py -- so it is recorded raw next to the analytic count).
 
+  python tools/swin_cost.py --train --out profiles/swin_train_cost.json [--parent-forward-ms MS]
+
+times the TRAINING path instead: the Swin-B forward + backward (enable_training(), stochastic depth off and at the reference's
+0.5) for the same window batch, the forward alone of the frozen module, and every backward kernel of csrc/swin.hip at every
+stage's shape (window attention with and without shift, LayerNorm, PatchMerging's LayerNorm, row_scale_add).  The file records,
+next to these, the forward-only time measured at the parent commit when it is given with --parent-forward-ms (the figure a run of
+this tool at that commit printed as encoder_forward_ms.batch_<B>); null until then.
+
 The weights are the default initialisation (the cost does not depend on their values; nothing is fetched).
 """
 import argparse
@@ -117,8 +125,77 @@ def counters_pass(B, crop):
     print("counter pass: one launch of each kernel done")
 
 
+def train_cost(args):
+    from adm_amd import hip, ops_swin as osw
+    from adm_amd.unet.swin_transformer import swin_b
+    hip.lib()
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(7)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    B, g = args.batch, args.crop // 4
+    x = torch.rand(B, 3, args.crop, args.crop, device=dev, generator=gen) * 2 - 1
+    res = {"what": "Swin-B condition encoder, training path (f32, HIP kernels), one MI355X; ms = median (min, max) of HIP-event timings",
+           "crop": [args.crop, args.crop], "batch": B, "reps": args.reps,
+           "forward_only_ms_at_parent_commit": args.parent_forward_ms, "forward_backward_ms": {}, "backward_kernels_ms": []}
+    frozen = swin_b().to(dev).eval()
+    res["forward_only_ms_frozen"] = timed(lambda: frozen(x), args.warmup, args.reps)
+    del frozen
+    enc = swin_b().to(dev)
+    for tag, p in (("stochastic_depth_0", 0.0), ("stochastic_depth_0.5", None)):
+        enc.enable_training(p).train()
+
+        def step():
+            for q in enc.parameters():
+                q.grad = None
+            feats = enc(x)
+            torch.autograd.backward(feats, [torch.ones_like(f) for f in feats])
+
+        res["forward_backward_ms"][tag] = timed(step, args.warmup, args.reps)
+        res["forward_backward_ms"][tag + "_forward_part"] = timed(lambda: enc(x), args.warmup, args.reps)
+    del enc
+    one = lambda *s: torch.randn(*s, device=dev, generator=gen)
+    for st, (heads, depth) in enumerate(zip((4, 8, 16, 32), (2, 2, 18, 2))):
+        H = W = -(-g // 2 ** st)
+        C = 128 * 2 ** st
+        ent = {"stage": st + 1, "grid": [H, W], "C": C, "heads": heads, "batch": B, "blocks_in_stage": depth}
+        qkv, qb, tab, do = one(B, H, W, 3 * C), one(3 * C) * 0.1, one(169, heads) * 0.1, one(B, H, W, C)
+        dq, dt, db = torch.empty_like(qkv), torch.empty_like(tab), torch.empty_like(qb)
+        ws = torch.empty(hip.lib().adm_swin_attn_bwd_ws_floats(B, H, W, heads), device=dev)
+        for shift in (0, 3):
+            ent[f"swin_attn_bwd_shift{shift}"] = timed(lambda: hip.call(
+                "adm_swin_attn_bwd", hip.ptr(qkv), hip.ptr(qb), hip.ptr(tab), hip.ptr(do), hip.ptr(dq), hip.ptr(dt), hip.ptr(db), hip.ptr(ws),
+                B, H, W, C, heads, 7, shift, shift, 0, 0), args.warmup, args.reps)
+            ent[f"swin_attn_fwd_shift{shift}"] = timed(lambda: osw.window_attention(qkv, qb, tab, heads, shift), args.warmup, args.reps)
+        xs, w, dy, dx = one(B, H, W, C), torch.ones(C, device=dev), one(B, H, W, C), torch.empty(B, H, W, C, device=dev)
+        dw, dbb = torch.empty(C, device=dev), torch.empty(C, device=dev)
+        ws = torch.empty(hip.lib().adm_ln_bwd_ws_floats(B * H * W, C), device=dev)
+        ent["ln_affine_bwd"] = timed(lambda: hip.call("adm_ln_affine_bwd", hip.ptr(xs), hip.ptr(w), hip.ptr(dy), hip.ptr(dx), hip.ptr(dw),
+                                                      hip.ptr(dbb), hip.ptr(ws), B * H * W, C, 1e-5, 0), args.warmup, args.reps)
+        s = torch.ones(B, device=dev)
+        ent["rowscale_add"] = timed(lambda: hip.call("adm_rowscale_add", hip.ptr(xs), hip.ptr(dy), hip.ptr(s), hip.ptr(dx), B, H * W * C),
+                                    args.warmup, args.reps)
+        if st < 3:
+            Ho, Wo = (H + 1) // 2, (W + 1) // 2
+            w4, dy4 = torch.ones(4 * C, device=dev), one(B, Ho, Wo, 4 * C)
+            dw4, db4 = torch.empty(4 * C, device=dev), torch.empty(4 * C, device=dev)
+            ws = torch.empty(hip.lib().adm_ln_bwd_ws_floats(B * Ho * Wo, 4 * C), device=dev)
+            ent["swin_merge_ln_bwd"] = timed(lambda: hip.call("adm_swin_merge_ln_bwd", hip.ptr(xs), hip.ptr(w4), hip.ptr(dy4), hip.ptr(dx),
+                                                              hip.ptr(dw4), hip.ptr(db4), hip.ptr(ws), B, H, W, C, 1e-5, 0),
+                                             args.warmup, args.reps)
+        res["backward_kernels_ms"].append(ent)
+    print(json.dumps(res))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--train", action="store_true", help="time the training path (forward + backward and every backward kernel)")
+    ap.add_argument("--parent-forward-ms", type=float, default=None,
+                    help="with --train: the forward-only time measured at the parent commit, recorded next to the new figures")
     ap.add_argument("--mode", choices=["time", "counters"], default="time")
     ap.add_argument("--merge-counters", default=None, help="directory of a rocprofv3 --pmc pass; merged into --out (no GPU needed)")
     ap.add_argument("--batch", type=int, default=16)
@@ -132,6 +209,8 @@ def main():
         return merge_counters(args.merge_counters, args.out, args.batch, args.crop)
     if args.mode == "counters":
         return counters_pass(args.batch, args.crop)
+    if args.train:
+        return train_cost(args)
 
     from adm_amd import hip, ops_swin as osw
     from adm_amd.unet.swin_transformer import swin_b
