@@ -890,35 +890,84 @@ def _use_wino2d(B, Ho, Wo, ks, up, tile) -> bool:
     return WINOGRAD2D and (not up or BF16X6) and (Ho & 1) == 0 and _use_wino(B, Ho, Wo, ks, up, tile)
 
 
-def _conv_f32(x, wp, bias, res, y, B, Ho, Wo, cin_p, n_p, ks, up, tile, wq=None, wq2=None, wq6=None):
-    """fp32 conv: 2-D Winograd F(2x2,3x3) kernel when `wq2` is given, 1-D F(2,3) when `wq`, else the direct implicit GEMM;
-    small-M problems get the deterministic split-K path (workspace + fixed-order reduce)."""
-    nosplit = _SELECT_BATCH is not None        # batch_invariant(): the split count depends on the call's size
-    if wq2 is not None and wq6 is not None:
-        sk = 1 if nosplit else hip.lib().adm_wino2d_x6_splitk(B, Ho, Wo, cin_p, n_p)
-        ws = _new((sk * B * Ho * Wo * n_p,), x) if sk > 1 else None
-        call("adm_conv_fwd_wino2d_x6_up" if up else "adm_conv_fwd_wino2d_x6", ptr(x), ptr(wq6), ptr(bias), ptr(res), ptr(y), ptr(ws),
-             0 if ws is None else ws.numel(), B, Ho, Wo, cin_p, cin_p, n_p, n_p, n_p, n_p)
-        return
-    if wq2 is not None:
-        sk = 1 if nosplit else hip.lib().adm_wino2d_splitk(B, Ho, Wo, cin_p, n_p)
-        ws = _new((sk * B * Ho * Wo * n_p,), x) if sk > 1 else None       # small maps: split over the input channels, fixed-order reduce
-        call("adm_conv_fwd_wino2d", ptr(x), ptr(wq2), ptr(bias), ptr(res), ptr(y), ptr(ws), 0 if ws is None else ws.numel(), B, Ho, Wo,
-             cin_p, cin_p, n_p, n_p, n_p, n_p)
-        return
-    if wq is not None:
-        call("adm_conv_fwd_wino_up" if up else "adm_conv_fwd_wino", ptr(x), ptr(wq), ptr(bias), ptr(res), ptr(y), B, Ho, Wo,
-             cin_p, cin_p, n_p, n_p, n_p, n_p)
-        return
-    if tile < 0 and not nosplit:
-        sk = hip.lib().adm_conv_splitk(B * Ho * Wo, n_p, ks * ks * cin_p)
-        if sk > 1:
-            ws = _new((sk * B * Ho * Wo * n_p,), x)
-            call("adm_conv_fwd_ws", ptr(x), ptr(wp), ptr(bias), ptr(res), ptr(y), ptr(ws), ws.numel(), B, Ho, Wo, cin_p,
-                 cin_p, n_p, n_p, n_p, n_p, ks, up)
-            return
-    call("adm_conv_fwd", ptr(x), ptr(wp), ptr(bias), ptr(res), ptr(y), B, Ho, Wo, cin_p, cin_p, n_p, n_p, n_p, n_p, ks,
-         up, tile)
+def _conv_data_pass(tag, x, x16, weight, pk, which, bias, res, y, ks, up, tile, qkv, bf16, amax, find_amax, *, gemm_m, gemm_ok,
+                    h3_nosplit, bound_h3, bound_x6):
+    """One stride-1 conv x -> y on the operands of direction `which` of a packed weight: 0 = the forward, 1 = the data gradient (the
+    same conv over dy, cin and cout exchanged).  Selects the kernel and launches it; returns the bound vector that the kernel raised
+    to max |y|, or None.  Where the two directions differ, the caller states the rule:
+      amax / find_amax  the bound of x, or a function that looks it up -- called only where a fp16-format kernel could use the result
+                        (under ADM_AMAX_CHECK the look-up reads the device)
+      x16               the bf16-stored values of x (x is then only the f32 carrier), or None
+      gemm_m            the pixel count that decides whether a 1x1 conv takes the split GEMM
+      gemm_ok           False keeps a 1x1 conv off the split GEMM whatever its size
+      h3_nosplit        batch_invariant() suppresses split-K on the fp16-format 3x3 kernel too (on every other kernel it always does)
+      bound_h3 / _x6    the fp16-format / bf16-format 1x1 kernel leaves max |y|"""
+    B, Ho, Wo, n_p = y.shape
+    k_p = x.shape[-1]
+    co, ci = weight.shape[0], weight.shape[1]
+    use_bf16 = bf16 and k_p % 64 == 0
+    if x16 is not None and not use_bf16:
+        raise RuntimeError("a bf16-stored activation reached a conv that does not run in the bf16 mode")
+    wino = not use_bf16 and _use_wino(B, Ho, Wo, ks, up, tile) and not qkv
+    wino2 = wino and _use_wino2d(B, Ho, Wo, ks, up, tile)
+    g6 = not use_bf16 and gemm_ok and _use_gemm_x6(gemm_m, ks, up, n_p, k_p)
+    # fp16 format: the operand came with its max |x| ...
+    if FP16X3 and ((wino2 and BF16X6) or (g6 and H3_GEMM)) and find_amax is not None:
+        amax = find_amax(x)
+    h3 = (wino2 and BF16X6 and FP16X3 and amax is not None
+          and _h3_operands(weight, pk, which) is not None)           # ... and the weights fit their fp16 image
+    wq2 = _wino2_operands(weight, pk, which) if (wino2 and not h3) else None
+    wq = _wino_operands(weight, pk)[which] if (wino and not wino2) else None
+    g6h = g6 and FP16X3 and H3_GEMM and amax is not None and _gemm_h3_operand(pk, which) is not None
+    # small-M problems: split over the input channels into a workspace, fixed-order reduce
+    sk = 1
+    if _SELECT_BATCH is None or (h3 and not h3_nosplit):        # (not under batch_invariant(): the split count depends on the call's size)
+        if wino2:
+            sk = (hip.lib().adm_wino2d_x6_splitk if BF16X6 else hip.lib().adm_wino2d_splitk)(B, Ho, Wo, k_p, n_p)
+        elif not (wino or g6 or use_bf16) and tile < 0:
+            sk = hip.lib().adm_conv_splitk(B * Ho * Wo, n_p, ks * ks * k_p)
+    ws = _new((sk * B * Ho * Wo * n_p,), x) if sk > 1 else None
+    ws_n = 0 if ws is None else ws.numel()
+    amax_y = None
+    kind = ("wino2h3" if h3 else "wino2x6" if BF16X6 else "wino2") if wino2 else "wino" if wino else ("gemmh3" if g6h else "gemmx6") if g6 else "igemm"
+    with _Prof(kind, 2.0 * B * Ho * Wo * co * ci * ks * ks,
+               f"{tag}{'-' + kind if kind != 'igemm' else ''} M={B * Ho * Wo} N={n_p} K={ks * ks * k_p}"):
+        if h3:
+            # (no output bound from this kernel: tracking it in the epilogue cost the 96- / 128-cout forms ten more spilled registers,
+            #  +10 % on their launches, for the handful of encoder skip convs that would have used it)
+            call("adm_conv_fwd_wino2d_h3", ptr(x), ptr(_h3_operands(weight, pk, which)), ptr(bias), ptr(res), ptr(y), ptr(ws), ws_n,
+                 B, Ho, Wo, k_p, k_p, n_p, n_p, n_p, n_p, _bptr(amax), H3_WSCALE, int(up))
+        elif g6h:
+            amax_y = _amax_slot(x) if bound_h3 else None
+            call("adm_gemm_x6_h3", ptr(x), ptr(_gemm_h3_operand(pk, which)), ptr(bias), ptr(res), ptr(y), B * Ho * Wo, k_p, k_p, n_p,
+                 n_p, n_p, n_p, _bptr(amax), H3_WSCALE, ptr(amax_y))
+        elif g6 and bound_x6:
+            amax_y = _amax_slot(x)
+            call("adm_gemm_x6_amax", ptr(x), ptr(_gemm_x6_operand(pk, which)), ptr(bias), ptr(res), ptr(y), B * Ho * Wo, k_p, k_p, n_p,
+                 n_p, n_p, n_p, ptr(amax_y))
+        elif g6:
+            call("adm_gemm_x6", ptr(x), ptr(_gemm_x6_operand(pk, which)), ptr(bias), ptr(res), ptr(y), B * Ho * Wo, k_p, k_p, n_p,
+                 n_p, n_p, n_p)
+        elif use_bf16:
+            call("adm_conv_fwd_bf16a" if x16 is not None else "adm_conv_fwd_bf16", ptr(x16 if x16 is not None else x),
+                 ptr(_bf16_operand(pk, "bwd" if which else "fwd")), ptr(bias), ptr(res), ptr(y), B, Ho, Wo, k_p, k_p, n_p, n_p, n_p,
+                 n_p, ks, int(up), -1)
+        elif wino2 and BF16X6:
+            call("adm_conv_fwd_wino2d_x6_up" if up else "adm_conv_fwd_wino2d_x6", ptr(x), ptr(wq2), ptr(bias), ptr(res), ptr(y), ptr(ws),
+                 ws_n, B, Ho, Wo, k_p, k_p, n_p, n_p, n_p, n_p)
+        elif wino2:
+            call("adm_conv_fwd_wino2d", ptr(x), ptr(wq2), ptr(bias), ptr(res), ptr(y), ptr(ws), ws_n, B, Ho, Wo, k_p, k_p, n_p, n_p,
+                 n_p, n_p)
+        elif wino:
+            call("adm_conv_fwd_wino_up" if up else "adm_conv_fwd_wino", ptr(x), ptr(wq), ptr(bias), ptr(res), ptr(y), B, Ho, Wo,
+                 k_p, k_p, n_p, n_p, n_p, n_p)
+        elif sk > 1:
+            call("adm_conv_fwd_ws", ptr(x), ptr(pk.bwd if which else pk.fwd), ptr(bias), ptr(res), ptr(y), ptr(ws), ws_n, B, Ho, Wo,
+                 k_p, k_p, n_p, n_p, n_p, n_p, ks, int(up))
+        else:
+            call("adm_conv_fwd", ptr(x), ptr(pk.bwd if which else pk.fwd), ptr(bias), ptr(res), ptr(y), B, Ho, Wo, k_p, k_p, n_p,
+                 n_p, n_p, n_p, ks, int(up), tile)
+    return amax_y
 
 
 class _Conv(torch.autograd.Function):
@@ -939,50 +988,13 @@ class _Conv(torch.autograd.Function):
             if tuple(res.shape) != tuple(y.shape):
                 raise RuntimeError(f"residual shape {tuple(res.shape)} != output {tuple(y.shape)}")
         bf16 = COMPUTE == "bf16"
-        use_bf16 = bf16 and cip % 64 == 0
         x16 = getattr(x, "_adm_bf16", None)          # bf16-storage mode: the values of this input live here (x is the f32 carrier)
-        if x16 is not None and not use_bf16:
-            raise RuntimeError("a bf16-stored activation reached a conv that does not run in the bf16 mode")
-        wino = not use_bf16 and _use_wino(B, Ho, Wo, ks, up, tile) and not qkv
-        wino2 = wino and _use_wino2d(B, Ho, Wo, ks, up, tile)
-        h3 = (wino2 and BF16X6 and FP16X3 and amax is not None       # fp16 format: the operand came with its max |x| ...
-              and _h3_operands(weight, pk, 0) is not None)           # ... and the weights fit their fp16 image
-        wq2 = _wino2_operands(weight, pk, 0) if (wino2 and not h3) else None
-        wq = _wino_operands(weight, pk)[0] if (wino and not wino2) else None
-        g6 = not use_bf16 and _use_gemm_x6(_sel_batch(B) * Ho * Wo, ks, up, cop, cip)
-        g6h = g6 and FP16X3 and H3_GEMM and amax is not None and _gemm_h3_operand(pk, 0) is not None
         # the bound of a 1x1 conv's OUTPUT (qkv -> attention -> proj; proj + residual -> the next block's skip conv): written by the epilogue
         # (bias and residual included) and handed to the consumer on y, where conv2d / attention look for it
         fmt = _fp16_format()
         want_out = fmt and H3_GEMM
-        amax_y = None
-        kind = ("wino2h3" if h3 else "wino2x6" if BF16X6 else "wino2") if wino2 else "wino" if wq is not None else ("gemmh3" if g6h else "gemmx6") if g6 else "igemm"
-        with _Prof(kind, 2.0 * B * Ho * Wo * co * ci * ks * ks,
-                   f"fwd{'-' + kind if kind != 'igemm' else ''} M={B * Ho * Wo} N={cop} K={ks * ks * cip}"):
-            if h3:
-                # (no output bound from this kernel: tracking it in the epilogue cost the 96- / 128-cout forms ten more spilled registers,
-                #  +10 % on their launches, for the handful of encoder skip convs that would have used it)
-                sk = 1 if _SELECT_BATCH is not None else hip.lib().adm_wino2d_x6_splitk(B, Ho, Wo, cip, cop)
-                wsk = _new((sk * B * Ho * Wo * cop,), x) if sk > 1 else None
-                call("adm_conv_fwd_wino2d_h3", ptr(x), ptr(_h3_operands(weight, pk, 0)), ptr(pk.bias), ptr(res), ptr(y), ptr(wsk),
-                     0 if wsk is None else wsk.numel(), B, Ho, Wo, cip, cip, cop, cop, cop, cop, _bptr(amax), H3_WSCALE, int(up))
-            elif g6h:
-                amax_y = _amax_slot(x) if want_out else None
-                call("adm_gemm_x6_h3", ptr(x), ptr(_gemm_h3_operand(pk, 0)), ptr(pk.bias), ptr(res), ptr(y), B * Ho * Wo, cip, cip, cop,
-                     cop, cop, cop, _bptr(amax), H3_WSCALE, ptr(amax_y))
-            elif g6 and want_out:
-                amax_y = _amax_slot(x)
-                call("adm_gemm_x6_amax", ptr(x), ptr(_gemm_x6_operand(pk, 0)), ptr(pk.bias), ptr(res), ptr(y), B * Ho * Wo, cip, cip, cop,
-                     cop, cop, cop, ptr(amax_y))
-            elif g6:
-                call("adm_gemm_x6", ptr(x), ptr(_gemm_x6_operand(pk, 0)), ptr(pk.bias), ptr(res), ptr(y), B * Ho * Wo, cip, cip, cop,
-                     cop, cop, cop)
-            elif use_bf16:
-                call("adm_conv_fwd_bf16a" if x16 is not None else "adm_conv_fwd_bf16", ptr(x16 if x16 is not None else x),
-                     ptr(_bf16_operand(pk, "fwd")), ptr(pk.bias), ptr(res), ptr(y), B, Ho, Wo, cip, cip, cop, cop, cop, cop, ks, int(up), -1)
-            else:
-                _conv_f32(x, pk.fwd, pk.bias, res, y, B, Ho, Wo, cip, cop, ks, int(up), tile, wq, wq2,
-                          wq2 if (BF16X6 and wq2 is not None) else None)
+        amax_y = _conv_data_pass("fwd", x, x16, weight, pk, 0, pk.bias, res, y, ks, up, tile, qkv, bf16, amax, None,
+                                 gemm_m=_sel_batch(B) * Ho * Wo, gemm_ok=True, h3_nosplit=True, bound_h3=want_out, bound_x6=want_out)
         ctx.save_for_backward(x16 if x16 is not None else x, weight, bias)      # (the carrier is not kept)
         _mark_uses(ctx, (1, weight), (2, bias))
         ctx.meta = (ks, up, qkv, residual is not None, bf16)
@@ -1001,15 +1013,22 @@ class _Conv(torch.autograd.Function):
         cip = ceil32(ci)
         dx = dw = db = None
         wsink = _direct_grad(weight) if ctx.needs_input_grad[1] else None
-        need_b = bias is not None and ctx.needs_input_grad[2]
-        bsink = _direct_grad(bias) if need_b else None
-        # a bias whose packed order differs from its parameter's (qkv interleave, padded couts) goes through a zero-at-rest vector and a
-        # row of the end-of-backward table (which permutes, accumulates and clears) instead of zeros + permute + autograd's add
-        b_table = (need_b and bsink is not None and not bf16 and (qkv or cop != co) and DEFER_UNPACK and not DETERMINISTIC
-                   and wsink is not None)
+        bsink = _direct_grad(bias) if ctx.needs_input_grad[2] else None
+        # how the bias gradient travels -- the one place that decides it
+        bias_to = None
+        if bias is not None and ctx.needs_input_grad[2]:
+            if not qkv and cop == co:       # the packed order is the parameter's:
+                bias_to = "sink" if bsink is not None else "fresh"      # straight into the flat gradient buffer / a new [co] for autograd
+            # a bias whose packed order differs from its parameter's (qkv interleave, padded couts) goes through a zero-at-rest vector and a
+            # row of the end-of-backward table (which permutes, accumulates and clears) instead of zeros + permute + autograd's add
+            elif bsink is not None and not bf16 and DEFER_UNPACK and not DETERMINISTIC and wsink is not None:
+                bias_to = "table"
+            else:
+                bias_to = "permute"         # a padded temporary, then adm_permute_vec into a new [co] for autograd
+        # fp32: the weight-gradient kernel also produces the bias gradient (column sums of dy) on its way
+        fused_b = bias_to is not None and ctx.needs_input_grad[1] and not bf16
         side = None
-        if (SIDE_WGRAD and PROFILE is None and wsink is not None
-                and (not need_b or (bsink is not None and not qkv and cop == co) or b_table)):
+        if SIDE_WGRAD and PROFILE is None and wsink is not None and bias_to in (None, "sink", "table"):    # (nothing goes back through autograd)
             side = _wgrad_stream()
             ev = torch.cuda.Event()
             ev.record()                      # dy (and x) are complete at this point of the main stream
@@ -1018,23 +1037,31 @@ class _Conv(torch.autograd.Function):
 
         def weight_and_bias_grads():
             nonlocal dw, db
-            fused_b = False
+            # dbp: where the kernel (fused_b: it accumulates) or adm_colsum (it stores) leaves the bias gradient, in packed order
+            dbp = None
+            if bias_to == "sink":
+                dbp = bsink
+            elif bias_to == "table":
+                _begin_defer()
+                dbp = _rest_workspace_for(bias, (cop,), dy)
+            elif bias_to is not None:
+                n = co if bias_to == "fresh" else cop
+                dbp = torch.zeros((n,), device=dy.device, dtype=_f32) if fused_b else _new((n,), dy)
+                if bias_to == "fresh":
+                    db = dbp
+
+            def finish_bias():
+                nonlocal db
+                if bias_to == "table":
+                    _defer_unpack(dbp, bsink, co, 1, 1, 1, qkv)
+                elif bias_to == "permute":
+                    db = _new((co,), dy)
+                    call("adm_permute_vec", ptr(dbp), ptr(db), co, co, int(qkv), 1)
+                if bias_to in ("sink", "table"):
+                    _notify(bias)
+
             if ctx.needs_input_grad[1]:
-                # fp32: the weight-gradient kernel also produces the bias gradient (column sums of dy) on its way
-                dbp = None
-                if need_b and not bf16:
-                    fused_b = True
-                    if not qkv and cop == co:
-                        if bsink is not None:
-                            dbp = bsink                       # accumulate straight into the flat gradient buffer
-                        else:
-                            db = torch.zeros((co,), device=dy.device, dtype=_f32)
-                            dbp = db
-                    elif b_table:
-                        _begin_defer()
-                        dbp = _rest_workspace_for(bias, (cop,), dy)
-                    else:
-                        dbp = torch.zeros((cop,), device=dy.device, dtype=_f32)
+                dbk = dbp if fused_b else None      # (what the kernel is given)
                 pow2 = lambda v: v > 0 and (v & (v - 1)) == 0
                 wino_ok = _use_wino(B, Ho, Wo, ks, up, -1) and not qkv and pow2(Ho) and pow2(Wo)
                 # bf16 mode with bf16 activation storage: the split-bf16 Winograd kernel (dy split exactly, x as stored) is faster than the
@@ -1051,7 +1078,7 @@ class _Conv(torch.autograd.Function):
                 x6_w = wino2_w and BF16X6          # f32 products on the bf16 MFMA by exact three-term splitting (conv_wgrad_x6.hip)
                 g6_w = (GEMM_WGRAD_X6 and BF16X6 and (not bf16 or xbf) and ks == 1 and not up
                         and B * Ho * Wo >= GEMM_X6_MIN_M)      # ... 1x1 convs (its MODE 1)
-                splits = 1
+                splits, bws = 1, None
                 if det:        # splits store partial tiles to a workspace; the unpack launch sums them in a fixed order
                     splits = (hip.lib().adm_conv_wgrad_x6_plan(B, Ho, Wo, cip, cop) if x6_w else
                               hip.lib().adm_gemm_wgrad_x6_plan(B * Ho * Wo, cip, cop) if g6_w else
@@ -1059,7 +1086,7 @@ class _Conv(torch.autograd.Function):
                     if splits < 1:
                         raise RuntimeError(f"adm_conv_wgrad_plan failed with code {splits}")
                     dwp = _new((splits, cop, planes * cip), dy)
-                    bws = _new((splits, cop), dy) if dbp is not None else None
+                    bws = _new((splits, cop), dy) if fused_b else None
                 elif defer:
                     _begin_defer()          # (before the kernel: a pass that died may have left this workspace dirty)
                     dwp = _rest_workspace_for(weight, (cop, planes * cip), dy)
@@ -1072,42 +1099,40 @@ class _Conv(torch.autograd.Function):
                 h3_w = amax_dy is not None          # fp16 format (conv_wgrad_x6.hip FMT 1): both operands came with their bounds
                 if h3_w:
                     _check_bound(x, amax_x, "a conv input (weight gradient)")
+                # x, dy, the packed dW tile and the bias gradient's rows (per split under det); then conv-shaped or GEMM-shaped sizes
+                head = (ptr(x), ptr(dy), ptr(dwp), ptr(bws if det else dbk))
+                conv_g = (B, Ho, Wo, cip, cip, cop, cop)
+                gemm_g = (B * Ho * Wo, cip, cip, cop, cop)
+                nsplit = splits if det else auto
                 kind = "wgrad_wino2h3" if (h3_w and x6_w) else "wgrad_gemmh3" if h3_w else "wgrad_wino2x6" if x6_w else "wgrad_gemmx6" if g6_w else "wgrad_wino2" if wino2_w else "wgrad_wino" if wino_w else "wgrad"
                 with _Prof(kind, 2.0 * B * Ho * Wo * co * ci * ks * ks,
                            f"{kind.replace('_', '-')} P={B * Ho * Wo} Co={cop} Ci={cip} ks={ks}"):
-                    if bf16 and x6_w and x.dtype == torch.bfloat16:
-                        call("adm_conv_wgrad_x6_bf16a", ptr(x), ptr(dy), ptr(dwp), ptr(dbp), B, Ho, Wo, cip, cip, cop, cop, auto, int(up))
-                    elif bf16 and g6_w and x.dtype == torch.bfloat16:
-                        call("adm_gemm_wgrad_x6_bf16a", ptr(x), ptr(dy), ptr(dwp), ptr(dbp), B * Ho * Wo, cip, cip, cop, cop, auto)
-                    elif bf16 and not (x6_w or g6_w):
-                        call("adm_conv_wgrad_bf16a" if x.dtype == torch.bfloat16 else "adm_conv_wgrad_bf16", ptr(x), ptr(dy), ptr(dwp), B, Ho,
-                             Wo, cip, cip, cop, cop, ks, int(up), auto)
+                    if bf16 and x6_w and xbf:
+                        call("adm_conv_wgrad_x6_bf16a", *head, *conv_g, auto, int(up))
+                    elif bf16 and g6_w and xbf:
+                        call("adm_gemm_wgrad_x6_bf16a", *head, *gemm_g, auto)
+                    elif bf16 and not (x6_w or g6_w):       # (no bias gradient from the direct bf16 kernels)
+                        call("adm_conv_wgrad_bf16a" if xbf else "adm_conv_wgrad_bf16", *head[:3], *conv_g, ks, int(up), auto)
                     elif h3_w and x6_w:
-                        call("adm_conv_wgrad_x6_h3", ptr(x), ptr(dy), ptr(dwp), ptr(bws if det else dbp), B, Ho, Wo, cip, cip, cop, cop,
-                             splits if det else auto, int(up), int(det), _bptr(amax_x), _bptr(amax_dy))
+                        call("adm_conv_wgrad_x6_h3", *head, *conv_g, nsplit, int(up), int(det), _bptr(amax_x), _bptr(amax_dy))
                     elif h3_w:
-                        call("adm_gemm_wgrad_x6_h3", ptr(x), ptr(dy), ptr(dwp), ptr(bws if det else dbp), B * Ho * Wo, cip, cip, cop, cop,
-                             splits if det else auto, int(det), _bptr(amax_x), _bptr(amax_dy))
+                        call("adm_gemm_wgrad_x6_h3", *head, *gemm_g, nsplit, int(det), _bptr(amax_x), _bptr(amax_dy))
                     elif det and g6_w:
-                        call("adm_gemm_wgrad_x6_ws", ptr(x), ptr(dy), ptr(dwp), ptr(bws), B * Ho * Wo, cip, cip, cop, cop, splits)
+                        call("adm_gemm_wgrad_x6_ws", *head, *gemm_g, splits)
                     elif g6_w:
-                        call("adm_gemm_wgrad_x6", ptr(x), ptr(dy), ptr(dwp), ptr(dbp), B * Ho * Wo, cip, cip, cop, cop, auto)
+                        call("adm_gemm_wgrad_x6", *head, *gemm_g, auto)
                     elif det and x6_w:
-                        call("adm_conv_wgrad_x6_ws", ptr(x), ptr(dy), ptr(dwp), ptr(bws), B, Ho, Wo, cip, cip, cop, cop, splits, int(up))
+                        call("adm_conv_wgrad_x6_ws", *head, *conv_g, splits, int(up))
                     elif det:
-                        call("adm_conv_wgrad_ws", ptr(x), ptr(dy), ptr(dwp), ptr(bws), B, Ho, Wo, cip, cip, cop, cop, ks, int(up),
-                             splits, wmode)
+                        call("adm_conv_wgrad_ws", *head, *conv_g, ks, int(up), splits, wmode)
                     elif x6_w:
-                        call("adm_conv_wgrad_x6_up" if up else "adm_conv_wgrad_x6", ptr(x), ptr(dy), ptr(dwp), ptr(dbp), B, Ho, Wo, cip,
-                             cip, cop, cop, auto)
+                        call("adm_conv_wgrad_x6_up" if up else "adm_conv_wgrad_x6", *head, *conv_g, auto)
                     elif wino2_w:
-                        call("adm_conv_wgrad_wino2d", ptr(x), ptr(dy), ptr(dwp), ptr(dbp), B, Ho, Wo, cip, cip, cop, cop, auto)
+                        call("adm_conv_wgrad_wino2d", *head, *conv_g, auto)
                     elif wino_w:
-                        call("adm_conv_wgrad_wino_up" if up else "adm_conv_wgrad_wino", ptr(x), ptr(dy), ptr(dwp), ptr(dbp), B,
-                             Ho, Wo, cip, cip, cop, cop, auto)
+                        call("adm_conv_wgrad_wino_up" if up else "adm_conv_wgrad_wino", *head, *conv_g, auto)
                     else:
-                        call("adm_conv_wgrad_bias", ptr(x), ptr(dy), ptr(dwp), ptr(dbp), B, Ho, Wo, cip, cip, cop, cop, ks,
-                             int(up), auto)
+                        call("adm_conv_wgrad_bias", *head, *conv_g, ks, int(up), auto)
                 if wsink is not None:
                     dst, acc = wsink, 1
                 else:
@@ -1117,37 +1142,19 @@ class _Conv(torch.autograd.Function):
                     _defer_unpack(dwp, dst, co, ci, 0 if wino2_w else ks * ks, cip, qkv)
                 elif wino2_w:    # the y half of G^T rides in the unpack: dW[ky] = sum_ey Gt[ky][ey] wx[ey]
                     call("adm_unpack_wgrad_wino2d", ptr(dwp), splits, ptr(dst), co, ci, cop, cip, acc, ptr(bws) if det else None,
-                         ptr(dbp) if det else None)
+                         ptr(dbk) if det else None)
                 elif det:
                     call("adm_unpack_wgrad_splits", ptr(dwp), splits, ptr(dst), co, ci, ks, cop, cip, int(qkv), acc, ptr(bws),
-                         ptr(dbp))
+                         ptr(dbk))
                 else:
                     call("adm_unpack_wgrad", ptr(dwp), ptr(dst), co, ci, ks, cop, cip, int(qkv), acc)
                 if fused_b:
-                    if not qkv and cop == co:
-                        if bsink is not None:
-                            _notify(bias)
-                    elif b_table:
-                        _defer_unpack(dbp, bsink, co, 1, 1, 1, qkv)
-                        _notify(bias)
-                    else:
-                        db = _new((co,), dy)
-                        call("adm_permute_vec", ptr(dbp), ptr(db), co, co, int(qkv), 1)
+                    finish_bias()
                 if wsink is not None:
                     _notify(weight)
-            if need_b and not fused_b:
-                if not qkv and cop == co:
-                    if bsink is not None:
-                        call("adm_colsum", ptr(dy), ptr(bsink), B * Ho * Wo, cop, cop, 1)
-                        _notify(bias)
-                    else:
-                        db = _new((co,), dy)
-                        call("adm_colsum", ptr(dy), ptr(db), B * Ho * Wo, cop, cop, 0)
-                else:
-                    dbp = _new((cop,), dy)
-                    call("adm_colsum", ptr(dy), ptr(dbp), B * Ho * Wo, cop, cop, 0)
-                    db = _new((co,), dy)
-                    call("adm_permute_vec", ptr(dbp), ptr(db), co, co, int(qkv), 1)
+            if bias_to is not None and not fused_b:
+                call("adm_colsum", ptr(dy), ptr(dbp), B * Ho * Wo, cop, cop, int(bias_to == "sink"))
+                finish_bias()
 
         if side is not None:
             with torch.cuda.stream(side):
@@ -1157,41 +1164,16 @@ class _Conv(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             pk = packed(weight, bias, ks, qkv)
             dxf = _new((B, Ho, Wo, cip), dy)
-            use_bf16 = bf16 and cop % 64 == 0
-            wino = not use_bf16 and _use_wino(B, Ho, Wo, ks, False, -1) and not qkv
-            wino2 = wino and _use_wino2d(B, Ho, Wo, ks, False, -1)
-            amax_dy = _get_amax(dy) if (wino2 and BF16X6 and FP16X3) else None
-            h3 = amax_dy is not None and _h3_operands(weight, pk, 1) is not None
-            wq2 = _wino2_operands(weight, pk, 1) if (wino2 and not h3) else None
-            wq = _wino_operands(weight, pk)[1] if (wino and not wino2) else None
-            # (a data gradient that sums fewer than 32 real couts stays on the f32 kernel: over so few terms the split formats' truncated
-            #  cross products are not averaged out, and a head's dx over 1 or 3 couts measured 1.05-1.39x of twice the f32 kernel's rms
-            #  error against fp64, tests/test_hip_accuracy.py)
-            g6 = not use_bf16 and co >= 32 and _use_gemm_x6(B * Ho * Wo, ks, up, cip, cop)
-            amax_g = _get_amax(dy) if (g6 and FP16X3 and H3_GEMM) else None
-            g6h = amax_g is not None and _gemm_h3_operand(pk, 1) is not None
-            kind = ("wino2h3" if h3 else "wino2x6" if BF16X6 else "wino2") if wino2 else "wino" if wq is not None else ("gemmh3" if g6h else "gemmx6") if g6 else "igemm"
-            with _Prof(kind, 2.0 * B * Ho * Wo * co * ci * ks * ks,
-                       f"dgrad{'-' + kind if kind != 'igemm' else ''} M={B * Ho * Wo} N={cip} K={ks * ks * cop}"):
-                if h3:
-                    sk = hip.lib().adm_wino2d_x6_splitk(B, Ho, Wo, cop, cip)
-                    wsk = _new((sk * B * Ho * Wo * cip,), dy) if sk > 1 else None
-                    call("adm_conv_fwd_wino2d_h3", ptr(dy), ptr(_h3_operands(weight, pk, 1)), None, None, ptr(dxf), ptr(wsk),
-                         0 if wsk is None else wsk.numel(), B, Ho, Wo, cop, cop, cip, cip, cip, cip, _bptr(amax_dy), H3_WSCALE, 0)
-                elif g6h:       # (the epilogue leaves max |dx|: the attention backward behind a proj conv runs on the fp16 format)
-                    slot_dx = _amax_slot(dy)
-                    call("adm_gemm_x6_h3", ptr(dy), ptr(_gemm_h3_operand(pk, 1)), None, None, ptr(dxf), B * Ho * Wo, cop, cop, cip, cip,
-                         cip, cip, _bptr(amax_g), H3_WSCALE, ptr(slot_dx))
-                    _reg_amax(dxf, slot_dx)
-                elif g6:
-                    call("adm_gemm_x6", ptr(dy), ptr(_gemm_x6_operand(pk, 1)), None, None, ptr(dxf), B * Ho * Wo, cop, cop, cip, cip,
-                         cip, cip)
-                elif use_bf16:
-                    call("adm_conv_fwd_bf16", ptr(dy), ptr(_bf16_operand(pk, "bwd")), None, None, ptr(dxf), B, Ho, Wo,
-                         cop, cop, cip, cip, cip, cip, ks, 0, -1)
-                else:
-                    _conv_f32(dy, pk.bwd, None, None, dxf, B, Ho, Wo, cop, cip, ks, 0, -1, wq, wq2,
-                              wq2 if (BF16X6 and wq2 is not None) else None)
+            # gemm_ok: a data gradient that sums fewer than 32 real couts stays on the f32 kernel: over so few terms the split formats'
+            #  truncated cross products are not averaged out, and a head's dx over 1 or 3 couts measured 1.05-1.39x of twice the f32
+            #  kernel's rms error against fp64, tests/test_hip_accuracy.py
+            #  (and no fused nearest-x2 1x1 conv ever took the split GEMM here)
+            # bound_h3: the epilogue leaves max |dx| (the attention backward behind a proj conv runs on the fp16 format); there is no
+            #  adm_gemm_x6_amax on this side
+            slot_dx = _conv_data_pass("dgrad", dy, None, weight, pk, 1, None, None, dxf, ks, False, -1, qkv, bf16, None, _get_amax,
+                                      gemm_m=B * Ho * Wo, gemm_ok=co >= 32 and not up, h3_nosplit=False, bound_h3=True, bound_x6=False)
+            if slot_dx is not None:
+                _reg_amax(dxf, slot_dx)
             if up:   # gradient of nearest x2 = 2x2 sum
                 dx = _new((B, Ho // 2, Wo // 2, cip), dy)
                 call("adm_resample2x", ptr(dxf), ptr(dx), B, Ho, Wo, cip, 0, 1.0, 0)
@@ -1953,24 +1935,86 @@ def _no_grad_only(*tensors):
                            "call it under torch.no_grad() with parameters that do not require grad")
 
 
-def conv2d_strided(x, weight, bias=None, *, stride=2, pad_lo=0, pad_hi=1):
-    """NHWC conv with a stride and explicit zero padding (pad_lo rows/cols on the top/left, pad_hi on the bottom/right).
-    F.pad(x, (0,1,0,1)) + Conv2d(3x3, stride 2, padding 0) of the autoencoder's Downsample (encoder_decoder.py:78-96)
-    is stride=2, pad_lo=0, pad_hi=1.  Forward-only."""
-    _no_grad_only(x, weight, bias)
-    x = _chk(x, "x")
+# The strided / large-filter convs: ops.conv2d_strided here (forward-only), ops_ae._ConvDown and ops_cond._ConvGeneric with their
+# backwards.  They differ in how the weight operand is made and in the weight-gradient kernel; what they share is below.
+def _conv_fwd_strided(x, weight, wp, bp, stride, pad_lo, pad_hi, label):
+    """y = conv(x) with filter size ks <= 7 from the OIHW `weight`, a stride and explicit zero padding (pad_lo rows/cols on the top/left,
+    pad_hi on the bottom/right), on the packed operand wp and the packed bias bp; x is checked NHWC."""
     B, H, W, cx = x.shape
     co, ci, ks = weight.shape[0], weight.shape[1], weight.shape[-1]
     cop, cip = ceil32(co), ceil32(ci)
     if cx != cip:
         raise RuntimeError(f"conv input has {cx} channels, expected {cip}")
     Ho, Wo = (H + pad_lo + pad_hi - ks) // stride + 1, (W + pad_lo + pad_hi - ks) // stride + 1
-    pk = packed(weight, bias, ks, False)
     y = _new((B, Ho, Wo, cop), x)
-    with _Prof("igemm", 2.0 * B * Ho * Wo * co * ci * ks * ks, f"fwd-s{stride} M={B * Ho * Wo} N={cop} K={ks * ks * cip}"):
-        call("adm_conv_fwd_strided", ptr(x), ptr(pk.fwd), ptr(pk.bias), None, ptr(y), B, H, W, Ho, Wo, cip, cip, cop, cop,
-             cop, cop, ks, stride, pad_lo)
+    with _Prof("igemm", 2.0 * B * Ho * Wo * co * ci * ks * ks, f"{label} M={B * Ho * Wo} N={cop} K={ks * ks * cip}"):
+        call("adm_conv_fwd_strided", ptr(x), ptr(wp), ptr(bp), None, ptr(y), B, H, W, Ho, Wo, cip, cip, cop, cop, cop, cop, ks, stride,
+             pad_lo)
     return y
+
+
+def _conv_dgrad_strided(dy, weight, x_shape, stride, pad_lo):
+    """dx of the conv above as the transposed conv in GEMM form: col = dy x W^T on the 1x1 kernel, then the adm_col2im gather."""
+    B, H, W, cip = x_shape
+    Ho, Wo = dy.shape[1], dy.shape[2]
+    co, ci, ks = weight.shape[0], weight.shape[1], weight.shape[-1]
+    cop = ceil32(co)
+    w = _chk(weight.detach(), "weight")
+    wt = _new((ks * ks * cip, cop), dy)
+    call("adm_pack_weight_tconv", ptr(w), ptr(wt), co, ci, ks, cop, cip)
+    M = B * Ho * Wo
+    col = _new((M, ks * ks * cip), dy)
+    with _Prof("igemm", 2.0 * M * co * ci * ks * ks, f"dgrad-tconv M={M} N={ks * ks * cip} K={cop}"):
+        call("adm_conv_fwd", ptr(dy), ptr(wt), None, None, ptr(col), 1, M, 1, cop, cop, ks * ks * cip, ks * ks * cip,
+             ks * ks * cip, ks * ks * cip, 1, 0, -1)
+    dx = _new((B, H, W, cip), dy)
+    call("adm_col2im", ptr(col), ptr(dx), B, H, W, Ho, Wo, cip, ks, stride, pad_lo)
+    return dx
+
+
+def _hand_over_wgrad(weight, bias, dwp, dbp, splits=0, bws=None):
+    """The tail of a strided conv's weight gradient: unpack the tile dwp (splits > 0: sum that many partial tiles, and the rows bws
+    into dbp, in split order) into the flat gradient buffer or a new tensor, then the padded bias gradient dbp (None: not needed)
+    likewise, and announce what went to the buffer.  Returns (dw, db) for autograd: None where the buffer took it."""
+    co, ci, ks = weight.shape[0], weight.shape[1], weight.shape[-1]
+    cop, cip = ceil32(co), ceil32(ci)
+    sink = _direct_grad(weight)
+    dst = sink if sink is not None else _like(weight)
+    acc = int(sink is not None)
+    if splits:
+        call("adm_unpack_wgrad_splits", ptr(dwp), splits, ptr(dst), co, ci, ks, cop, cip, 0, acc, ptr(bws), ptr(dbp))
+    else:
+        call("adm_unpack_wgrad", ptr(dwp), ptr(dst), co, ci, ks, cop, cip, 0, acc)
+    if sink is not None:
+        _notify(weight)
+    db = None
+    if dbp is not None:
+        bsink = _direct_grad(bias)
+        if bsink is not None:
+            call("adm_add", ptr(bsink), ptr(dbp), ptr(bsink), co)
+            _notify(bias)
+        else:
+            db = dbp[:co].clone()
+    return (None if sink is not None else dst), db
+
+
+def conv2d_strided(x, weight, bias=None, *, stride=2, pad_lo=0, pad_hi=1):
+    """NHWC conv with a stride and explicit zero padding (pad_lo rows/cols on the top/left, pad_hi on the bottom/right).
+    F.pad(x, (0,1,0,1)) + Conv2d(3x3, stride 2, padding 0) of the autoencoder's Downsample (encoder_decoder.py:78-96)
+    is stride=2, pad_lo=0, pad_hi=1.  Forward-only."""
+    _no_grad_only(x, weight, bias)
+    x = _chk(x, "x")
+    pk = packed(weight, bias, weight.shape[-1], False)
+    return _conv_fwd_strided(x, weight, pk.fwd, pk.bias, stride, pad_lo, pad_hi, f"fwd-s{stride}")
+
+
+def _mm_nt(a, b, bias, out):
+    """The launch of matmul_nt, for callers that have checked their operands (ops_ae's attention core, with a backward of its own)."""
+    M, K = a.shape
+    N = b.shape[0]
+    with _Prof("igemm", 2.0 * M * N * K, f"mm M={M} N={N} K={K}"):
+        call("adm_conv_fwd", ptr(a), ptr(b), ptr(bias), None, ptr(out), 1, M, 1, K, K, N, N, N, N, 1, 0, -1)
+    return out
 
 
 def matmul_nt(a, b, bias=None, out=None):
@@ -1978,14 +2022,10 @@ def matmul_nt(a, b, bias=None, out=None):
     weight matrix is b).  K % 32 == 0; rows 16-byte aligned.  Forward-only."""
     _no_grad_only(a, b, bias)
     a, b = _chk(a, "a"), _chk(b, "b")
-    M, K = a.shape
-    N = b.shape[0]
+    K = a.shape[1]
     if b.shape[1] != K or K % 32:
         raise RuntimeError(f"matmul_nt: inner sizes {K} / {b.shape[1]} must match and be a multiple of 32")
-    y = out if out is not None else _new((M, N), a)
-    with _Prof("igemm", 2.0 * M * N * K, f"mm M={M} N={N} K={K}"):
-        call("adm_conv_fwd", ptr(a), ptr(b), ptr(bias), None, ptr(y), 1, M, 1, K, K, N, N, N, N, 1, 0, -1)
-    return y
+    return _mm_nt(a, b, bias, out if out is not None else _new((a.shape[0], b.shape[0]), a))
 
 
 def softmax_rows_(s, scale: float):

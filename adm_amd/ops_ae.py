@@ -10,7 +10,7 @@ import torch
 
 from . import hip, ops
 from .hip import call, ptr
-from .ops import _chk, _direct_grad, _like, _new, _notify, _Prof, ceil32, packed
+from .ops import _chk, _like, _new, _Prof, ceil32, packed
 
 _f32 = torch.float32
 
@@ -28,73 +28,42 @@ class _ConvDown(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, stride, pad_lo, pad_hi):
         x = _chk(x, "x")
-        B, H, W, cx = x.shape
-        co, ci, ks = weight.shape[0], weight.shape[1], weight.shape[-1]
-        cop, cip = ceil32(co), ceil32(ci)
-        if cx != cip:
-            raise RuntimeError(f"conv input has {cx} channels, expected {cip}")
-        Ho, Wo = (H + pad_lo + pad_hi - ks) // stride + 1, (W + pad_lo + pad_hi - ks) // stride + 1
-        pk = packed(weight, bias, ks, False)
-        y = _new((B, Ho, Wo, cop), x)
-        with _Prof("igemm", 2.0 * B * Ho * Wo * co * ci * ks * ks, f"fwd-s{stride} M={B * Ho * Wo} N={cop} K={ks * ks * cip}"):
-            call("adm_conv_fwd_strided", ptr(x), ptr(pk.fwd), ptr(pk.bias), None, ptr(y), B, H, W, Ho, Wo, cip, cip, cop, cop,
-                 cop, cop, ks, stride, pad_lo)
+        pk = packed(weight, bias, weight.shape[-1], False)
+        y = ops._conv_fwd_strided(x, weight, pk.fwd, pk.bias, stride, pad_lo, pad_hi, f"fwd-s{stride}")
         ctx.save_for_backward(x, weight, bias)
-        ctx.meta = (stride, pad_lo, Ho, Wo)
+        ctx.meta = (stride, pad_lo)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, weight, bias = ctx.saved_tensors
-        stride, pad_lo, Ho, Wo = ctx.meta
+        stride, pad_lo = ctx.meta
         dy = _chk(dy, "dy")
         B, H, W, cip = x.shape
+        Ho, Wo = dy.shape[1], dy.shape[2]
         co, ci, ks = weight.shape[0], weight.shape[1], weight.shape[-1]
         cop = ceil32(co)
         dx = dw = db = None
         if ctx.needs_input_grad[1]:
             need_b = bias is not None and ctx.needs_input_grad[2]
             dbp = torch.zeros((cop,), device=dy.device, dtype=_f32) if need_b else None
-            sink = _direct_grad(weight)
-            dst = sink if sink is not None else _like(weight)
-            acc = int(sink is not None)
             with _Prof("wgrad", 2.0 * B * Ho * Wo * co * ci * ks * ks, f"wgrad-k{ks}s{stride} P={B * Ho * Wo} Co={cop} Ci={cip}"):
+                splits, bws = 0, None
                 if ops.DETERMINISTIC:      # pixel-range partials to a workspace, summed in split order (no float atomics)
                     splits = hip.lib().adm_conv_wgrad_plan(B, Ho, Wo, cip, cop, ks, 0, 0)
                     if splits < 1:
                         raise RuntimeError(f"adm_conv_wgrad_plan failed with code {splits}")
-                    ws = _new((splits, cop, ks * ks * cip), dy)
+                    dwp = _new((splits, cop, ks * ks * cip), dy)
                     bws = _new((splits, cop), dy) if need_b else None
-                    call("adm_conv_wgrad_strided_ws", ptr(x), ptr(dy), ptr(ws), ptr(bws), B, H, W, Ho, Wo, cip, cip, cop, cop, ks,
+                    call("adm_conv_wgrad_strided_ws", ptr(x), ptr(dy), ptr(dwp), ptr(bws), B, H, W, Ho, Wo, cip, cip, cop, cop, ks,
                          stride, pad_lo, splits)
-                    call("adm_unpack_wgrad_splits", ptr(ws), splits, ptr(dst), co, ci, ks, cop, cip, 0, acc, ptr(bws), ptr(dbp))
                 else:
                     dwp = _new((cop, ks * ks * cip), dy)
                     call("adm_conv_wgrad_strided", ptr(x), ptr(dy), ptr(dwp), ptr(dbp), B, H, W, Ho, Wo, cip, cip, cop, cop, ks,
                          stride, pad_lo)
-                    call("adm_unpack_wgrad", ptr(dwp), ptr(dst), co, ci, ks, cop, cip, 0, acc)
-            if sink is not None:
-                _notify(weight)
-            else:
-                dw = dst
-            if need_b:
-                bsink = _direct_grad(bias)
-                if bsink is not None:
-                    call("adm_add", ptr(bsink), ptr(dbp), ptr(bsink), co)
-                    _notify(bias)
-                else:
-                    db = dbp[:co].clone()
+                dw, db = ops._hand_over_wgrad(weight, bias, dwp, dbp, splits, bws)
         if ctx.needs_input_grad[0]:
-            w = _chk(weight.detach(), "weight")
-            wt = _new((ks * ks * cip, cop), dy)
-            call("adm_pack_weight_tconv", ptr(w), ptr(wt), co, ci, ks, cop, cip)
-            M = B * Ho * Wo
-            col = _new((M, ks * ks * cip), dy)
-            with _Prof("igemm", 2.0 * M * co * ci * ks * ks, f"dgrad-tconv M={M} N={ks * ks * cip} K={cop}"):
-                call("adm_conv_fwd", ptr(dy), ptr(wt), None, None, ptr(col), 1, M, 1, cop, cop, ks * ks * cip, ks * ks * cip,
-                     ks * ks * cip, ks * ks * cip, 1, 0, -1)
-            dx = _new((B, H, W, cip), dy)
-            call("adm_col2im", ptr(col), ptr(dx), B, H, W, Ho, Wo, cip, ks, stride, pad_lo)
+            dx = ops._conv_dgrad_strided(dy, weight, x.shape, stride, pad_lo)
         return dx, dw, db, None, None, None
 
 
@@ -108,11 +77,7 @@ def conv2d_down(x, weight, bias=None, *, stride=2, pad_lo=0, pad_hi=1):
 # ------------------------------------------------------------------------------------------------ single-head attention core
 def _nt(a, b, out, bias=None):
     """out[M][N] = sum_k a[m][k] b[n][k] (+ bias[n]) on the implicit-GEMM kernel."""
-    M, K = a.shape
-    N = b.shape[0]
-    with _Prof("igemm", 2.0 * M * N * K, f"mm M={M} N={N} K={K}"):
-        call("adm_conv_fwd", ptr(a), ptr(b), ptr(bias), None, ptr(out), 1, M, 1, K, K, N, N, N, N, 1, 0, -1)
-    return out
+    return ops._mm_nt(a, b, bias, out)
 
 
 def _tn(a, b, out):

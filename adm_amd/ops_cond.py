@@ -62,12 +62,8 @@ class _ConvGeneric(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, stride, pad):
         x = _chk(x, "x")
-        B, H, W, cx = x.shape
         co, ci, ks = weight.shape[0], weight.shape[1], weight.shape[-1]
         cop, cip = ceil32(co), ceil32(ci)
-        if cx != cip:
-            raise RuntimeError(f"conv input has {cx} channels, expected {cip}")
-        Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
         w = _chk(weight.detach(), "weight")
         wp = _new((cop, ks * ks * cip), x)
         call("adm_pack_weight", ptr(w), ptr(wp), None, co, ci, ks, cop, cip, 0)
@@ -77,20 +73,18 @@ class _ConvGeneric(torch.autograd.Function):
             if cop != co:
                 bp = torch.zeros((cop,), device=x.device, dtype=_f32)
                 bp[:co] = bias.detach()
-        y = _new((B, Ho, Wo, cop), x)
-        with _Prof("igemm", 2.0 * B * Ho * Wo * co * ci * ks * ks, f"fwd-k{ks}s{stride} M={B * Ho * Wo} N={cop} K={ks * ks * cip}"):
-            call("adm_conv_fwd_strided", ptr(x), ptr(wp), ptr(bp), None, ptr(y), B, H, W, Ho, Wo, cip, cip, cop, cop, cop, cop,
-                 ks, stride, pad)
+        y = ops._conv_fwd_strided(x, weight, wp, bp, stride, pad, pad, f"fwd-k{ks}s{stride}")
         ctx.save_for_backward(x, weight, bias)
-        ctx.meta = (stride, pad, Ho, Wo)
+        ctx.meta = (stride, pad)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, weight, bias = ctx.saved_tensors
-        stride, pad, Ho, Wo = ctx.meta
+        stride, pad = ctx.meta
         dy = _chk(dy, "dy")
         B, H, W, cip = x.shape
+        Ho, Wo = dy.shape[1], dy.shape[2]
         co, ci, ks = weight.shape[0], weight.shape[1], weight.shape[-1]
         cop = ceil32(co)
         dx = dw = db = None
@@ -101,31 +95,9 @@ class _ConvGeneric(torch.autograd.Function):
             with _Prof("wgrad", 2.0 * B * Ho * Wo * co * ci * ks * ks, f"wgrad-k{ks}s{stride} P={B * Ho * Wo} Co={cop} Ci={cip}"):
                 call("adm_conv_wgrad_strided", ptr(x), ptr(dy), ptr(dwp), ptr(dbp), B, H, W, Ho, Wo, cip, cip, cop, cop, ks, stride,
                      pad)
-            sink = _direct_grad(weight)
-            if sink is not None:
-                call("adm_unpack_wgrad", ptr(dwp), ptr(sink), co, ci, ks, cop, cip, 0, 1)
-                _notify(weight)
-            else:
-                dw = _like(weight)
-                call("adm_unpack_wgrad", ptr(dwp), ptr(dw), co, ci, ks, cop, cip, 0, 0)
-            if need_b:
-                bsink = _direct_grad(bias)
-                if bsink is not None:
-                    call("adm_add", ptr(bsink), ptr(dbp), ptr(bsink), co)
-                    _notify(bias)
-                else:
-                    db = dbp[:co].clone()
+            dw, db = ops._hand_over_wgrad(weight, bias, dwp, dbp)
         if ctx.needs_input_grad[0]:
-            w = _chk(weight.detach(), "weight")
-            wt = _new((ks * ks * cip, cop), dy)
-            call("adm_pack_weight_tconv", ptr(w), ptr(wt), co, ci, ks, cop, cip)
-            M = B * Ho * Wo
-            col = _new((M, ks * ks * cip), dy)
-            with _Prof("igemm", 2.0 * M * co * ci * ks * ks, f"dgrad-tconv M={M} N={ks * ks * cip} K={cop}"):
-                call("adm_conv_fwd", ptr(dy), ptr(wt), None, None, ptr(col), 1, M, 1, cop, cop, ks * ks * cip, ks * ks * cip,
-                     ks * ks * cip, ks * ks * cip, 1, 0, -1)
-            dx = _new((B, H, W, cip), dy)
-            call("adm_col2im", ptr(col), ptr(dx), B, H, W, Ho, Wo, cip, ks, stride, pad)
+            dx = ops._conv_dgrad_strided(dy, weight, x.shape, stride, pad)
         return dx, dw, db, None, None
 
 
