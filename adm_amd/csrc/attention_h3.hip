@@ -1,5 +1,5 @@
 // Self-attention forward of UNetBlock (/root/reference/unet/uncond_unet.py:205-208) with the f32 products of both matrix
-// products carried on the 16-bit MFMA by the two-term fp16 split of conv_wino2d_x6.hip (FMT 1): s a = h0 + h1 (round to nearest, s a
+// products carried on the 16-bit MFMA by the two-term fp16 split of split_format.h (format 1): s a = h0 + h1 (round to nearest, s a
 // power of two from a bound of max |qkv|), a b = (h0 h0' + h0 h1' + h1 h0') / (s s'): three v_mfma_f32_32x32x16_f16 (32 cycles
 // for K = 16) in place of eight v_mfma_f32_32x32x2f32 (64 cycles for K = 2) -- 5.3x less matrix-pipe time at f32 accuracy.
 //
@@ -15,38 +15,15 @@
 // L in {32, 64, 128, 256} (the UNet's attention levels) or a multiple of 256 (the latent configs' 32x32 level: 256-key chunks, online
 // softmax); anything else stays on attention.hip.
 #include "common.h"
-#include "../../include/adm_hip.h"
+#include "split_format.h"
 
 namespace {
 
-typedef _Float16 ah_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 ah_f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned ah_u32x4 __attribute__((ext_vector_type(4)));
 constexpr int AH_KROW = 72;        // halves per K row (64 + 8: 144 bytes, 16-byte aligned, conflict-free ds_read_b128)
 
-__device__ inline float ah_scale(float amax) {       // 16000 / max < s <= 32000 / max (= h3_scale of conv_wino2d_x6.hip)
-  if (!(amax > 0.f) || !(amax < 3e38f)) return 1.f;
-  int e;
-  frexpf(16000.f / amax, &e);
-  return ldexpf(1.f, e - 1);
-}
 __device__ __forceinline__ int ah_acc_row(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
 // position of key k (0..15 of its group) in the permuted order: half = bit 2, then (k >> 3, k & 3)
 __device__ __forceinline__ int ah_pos16(int k) { return (((k >> 2) & 1) << 3) | ((k >> 3) << 2) | (k & 3); }
-// 8 values -> two fp16 terms, 4 dwords each
-__device__ __forceinline__ void ah_split8(const float (&v)[8], float s, ah_u32x4& t0, ah_u32x4& t1) {
-  unsigned a[4], b[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float x0 = v[2 * i] * s, x1 = v[2 * i + 1] * s;
-    const _Float16 h00 = (_Float16)x0, h01 = (_Float16)x1;
-    const _Float16 h10 = (_Float16)(x0 - (float)h00), h11 = (_Float16)(x1 - (float)h01);
-    a[i] = __builtin_bit_cast(unsigned, ah_f16x2{h00, h01});
-    b[i] = __builtin_bit_cast(unsigned, ah_f16x2{h10, h11});
-  }
-  t0 = ah_u32x4{a[0], a[1], a[2], a[3]};
-  t1 = ah_u32x4{b[0], b[1], b[2], b[3]};
-}
 
 // MULTI: L is a multiple of 256; gridDim.y = the 256-query chunk this workgroup owns, the keys pass through LDS 256 at a time with a
 // running max / sum per query (online softmax), as attention.hip does for its long sequences
@@ -63,10 +40,10 @@ __global__ __launch_bounds__(64 * NKT) void attn_fwd_h3_kernel(const float* __re
   const int b = blockIdx.x / heads, h = blockIdx.x % heads;
   const long rs = (long)heads * 192;
   const float* base = qkv + (long)b * L * rs + h * 192;
-  const float sc = ah_scale(adm_amax_read(amax));
+  const float sc = split_scale(adm_amax_read(amax));
   // ---- the query fragment of this lane: 4 chunks of 16 d, 8 consecutive d per lane half; pre-scaled by 1/8 (exact)
   const int q = (MULTI ? (int)blockIdx.y * CH : 0) + wid * 32 + lr;
-  ah_u32x4 q0[4], q1[4];
+  u32x4 q0[4], q1[4];
   {
     const float* qrow = base + (long)q * rs;
 #pragma unroll
@@ -74,7 +51,7 @@ __global__ __launch_bounds__(64 * NKT) void attn_fwd_h3_kernel(const float* __re
       const f32x4 lo = *reinterpret_cast<const f32x4*>(qrow + 16 * c + 8 * lh);
       const f32x4 hi = *reinterpret_cast<const f32x4*>(qrow + 16 * c + 8 * lh + 4);
       const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      ah_split8(v, sc * 0.125f, q0[c], q1[c]);
+      split2_oct(v, sc * 0.125f, q0[c], q1[c]);
     }
   }
   const float inv_s = 1.f / (sc * sc);
@@ -96,8 +73,8 @@ __global__ __launch_bounds__(64 * NKT) void attn_fwd_h3_kernel(const float* __re
     for (int j = 0; j < 2; ++j) {
       const float x0 = v[2 * j] * sc, x1 = v[2 * j + 1] * sc;
       const _Float16 h00 = (_Float16)x0, h01 = (_Float16)x1;
-      t0[j] = __builtin_bit_cast(unsigned, ah_f16x2{h00, h01});
-      t1[j] = __builtin_bit_cast(unsigned, ah_f16x2{(_Float16)(x0 - (float)h00), (_Float16)(x1 - (float)h01)});
+      t0[j] = __builtin_bit_cast(unsigned, f16x2{h00, h01});
+      t1[j] = __builtin_bit_cast(unsigned, f16x2{(_Float16)(x0 - (float)h00), (_Float16)(x1 - (float)h01)});
     }
     *reinterpret_cast<uint2*>(Kh + key * AH_KROW + c4 * 4) = make_uint2(t0[0], t0[1]);
     *reinterpret_cast<uint2*>(Kh + (CH + key) * AH_KROW + c4 * 4) = make_uint2(t1[0], t1[1]);
@@ -115,9 +92,9 @@ __global__ __launch_bounds__(64 * NKT) void attn_fwd_h3_kernel(const float* __re
       const float x0 = va[j] * sc, x1 = vb[j] * sc;
       const _Float16 h00 = (_Float16)x0, h01 = (_Float16)x1;
       const int d = c4 * 4 + j;
-      *reinterpret_cast<unsigned*>(Vt + d * VROW + grp * 16 + p0) = __builtin_bit_cast(unsigned, ah_f16x2{h00, h01});
+      *reinterpret_cast<unsigned*>(Vt + d * VROW + grp * 16 + p0) = __builtin_bit_cast(unsigned, f16x2{h00, h01});
       *reinterpret_cast<unsigned*>(Vt + (64 + d) * VROW + grp * 16 + p0) =
-          __builtin_bit_cast(unsigned, ah_f16x2{(_Float16)(x0 - (float)h00), (_Float16)(x1 - (float)h01)});
+          __builtin_bit_cast(unsigned, f16x2{(_Float16)(x0 - (float)h00), (_Float16)(x1 - (float)h01)});
     }
   }
   __syncthreads();
@@ -132,9 +109,9 @@ __global__ __launch_bounds__(64 * NKT) void attn_fwd_h3_kernel(const float* __re
     const unsigned short* krow = Kh + (kt * 32 + lr) * AH_KROW + 8 * lh;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const ah_f16x8 a0 = __builtin_bit_cast(ah_f16x8, *reinterpret_cast<const ah_u32x4*>(krow + 16 * c));
-      const ah_f16x8 a1 = __builtin_bit_cast(ah_f16x8, *reinterpret_cast<const ah_u32x4*>(krow + CH * AH_KROW + 16 * c));
-      const ah_f16x8 b0 = __builtin_bit_cast(ah_f16x8, q0[c]), b1 = __builtin_bit_cast(ah_f16x8, q1[c]);
+      const f16x8 a0 = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(krow + 16 * c));
+      const f16x8 a1 = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(krow + CH * AH_KROW + 16 * c));
+      const f16x8 b0 = __builtin_bit_cast(f16x8, q0[c]), b1 = __builtin_bit_cast(f16x8, q1[c]);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, acc, 0, 0, 0);
@@ -169,14 +146,14 @@ __global__ __launch_bounds__(64 * NKT) void attn_fwd_h3_kernel(const float* __re
     for (int sl = 0; sl < 2; ++sl) {
       const float pv[8] = {s[kt][8 * sl], s[kt][8 * sl + 1], s[kt][8 * sl + 2], s[kt][8 * sl + 3],
                            s[kt][8 * sl + 4], s[kt][8 * sl + 5], s[kt][8 * sl + 6], s[kt][8 * sl + 7]};
-      ah_u32x4 p0, p1;
-      ah_split8(pv, 16384.f, p0, p1);
-      const ah_f16x8 b0 = __builtin_bit_cast(ah_f16x8, p0), b1 = __builtin_bit_cast(ah_f16x8, p1);
+      u32x4 p0, p1;
+      split2_oct(pv, 16384.f, p0, p1);
+      const f16x8 b0 = __builtin_bit_cast(f16x8, p0), b1 = __builtin_bit_cast(f16x8, p1);
 #pragma unroll
       for (int db = 0; db < 2; ++db) {
         const unsigned short* vrow = Vt + (db * 32 + lr) * VROW + kt * 32 + 16 * sl + 8 * lh;
-        const ah_f16x8 a0 = __builtin_bit_cast(ah_f16x8, *reinterpret_cast<const ah_u32x4*>(vrow));
-        const ah_f16x8 a1 = __builtin_bit_cast(ah_f16x8, *reinterpret_cast<const ah_u32x4*>(vrow + 64 * VROW));
+        const f16x8 a0 = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(vrow));
+        const f16x8 a1 = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(vrow + 64 * VROW));
         o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, o[db], 0, 0, 0);
         o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, o[db], 0, 0, 0);
         o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, o[db], 0, 0, 0);
@@ -222,10 +199,10 @@ int launch_fwd_h3(const float* qkv, float* out, float* lse, const float* amax, i
 //     16 in the accumulator layout's order (ah_pos16), as V^T in the forward.
 // LDS holds 128 rows of the other side at a time (three / four images: 108 / 144 KB); dS gets a static scale from the bound
 // |dS| <= |dP| + |delta| <= 128 max|dO| max|qkv| (loose by orders of magnitude: costs nothing but the smallest values' last bits).
-__device__ __forceinline__ f32x16 ah_mfma3(const ah_u32x4 a0, const ah_u32x4 a1, const ah_u32x4 b0, const ah_u32x4 b1, f32x16 c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(ah_f16x8, a0), __builtin_bit_cast(ah_f16x8, b1), c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(ah_f16x8, a1), __builtin_bit_cast(ah_f16x8, b0), c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(ah_f16x8, a0), __builtin_bit_cast(ah_f16x8, b0), c, 0, 0, 0);
+__device__ __forceinline__ f32x16 ah_mfma3(const u32x4 a0, const u32x4 a1, const u32x4 b0, const u32x4 b1, f32x16 c) {
+  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a0), __builtin_bit_cast(f16x8, b1), c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a1), __builtin_bit_cast(f16x8, b0), c, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a0), __builtin_bit_cast(f16x8, b0), c, 0, 0, 0);
 }
 // dst[term][row][AH_KROW] <- two-term split of scale * src[row][0..63] (rows at a stride of `rs` floats), CH rows
 __device__ __forceinline__ void ah_fill_rows(unsigned short* dst, int CH, const float* src, long rs, float scale, int tid, int nthreads) {
@@ -237,8 +214,8 @@ __device__ __forceinline__ void ah_fill_rows(unsigned short* dst, int CH, const 
     for (int j = 0; j < 2; ++j) {
       const float x0 = v[2 * j] * scale, x1 = v[2 * j + 1] * scale;
       const _Float16 h00 = (_Float16)x0, h01 = (_Float16)x1;
-      t0[j] = __builtin_bit_cast(unsigned, ah_f16x2{h00, h01});
-      t1[j] = __builtin_bit_cast(unsigned, ah_f16x2{(_Float16)(x0 - (float)h00), (_Float16)(x1 - (float)h01)});
+      t0[j] = __builtin_bit_cast(unsigned, f16x2{h00, h01});
+      t1[j] = __builtin_bit_cast(unsigned, f16x2{(_Float16)(x0 - (float)h00), (_Float16)(x1 - (float)h01)});
     }
     *reinterpret_cast<uint2*>(dst + row * AH_KROW + c4 * 4) = make_uint2(t0[0], t0[1]);
     *reinterpret_cast<uint2*>(dst + (CH + row) * AH_KROW + c4 * 4) = make_uint2(t1[0], t1[1]);
@@ -261,31 +238,31 @@ __device__ __forceinline__ void ah_fill_both(unsigned short* rimg, unsigned shor
       a0[j] = (_Float16)x0; a1[j] = (_Float16)(x0 - (float)a0[j]);
       b0[j] = (_Float16)x1; b1[j] = (_Float16)(x1 - (float)b0[j]);
       const int d = c4 * 4 + j;
-      *reinterpret_cast<unsigned*>(timg + d * VROW + grp * 16 + p0) = __builtin_bit_cast(unsigned, ah_f16x2{a0[j], b0[j]});
-      *reinterpret_cast<unsigned*>(timg + (64 + d) * VROW + grp * 16 + p0) = __builtin_bit_cast(unsigned, ah_f16x2{a1[j], b1[j]});
+      *reinterpret_cast<unsigned*>(timg + d * VROW + grp * 16 + p0) = __builtin_bit_cast(unsigned, f16x2{a0[j], b0[j]});
+      *reinterpret_cast<unsigned*>(timg + (64 + d) * VROW + grp * 16 + p0) = __builtin_bit_cast(unsigned, f16x2{a1[j], b1[j]});
     }
     *reinterpret_cast<uint2*>(rimg + r0 * AH_KROW + c4 * 4) =
-        make_uint2(__builtin_bit_cast(unsigned, ah_f16x2{a0[0], a0[1]}), __builtin_bit_cast(unsigned, ah_f16x2{a0[2], a0[3]}));
+        make_uint2(__builtin_bit_cast(unsigned, f16x2{a0[0], a0[1]}), __builtin_bit_cast(unsigned, f16x2{a0[2], a0[3]}));
     *reinterpret_cast<uint2*>(rimg + (CH + r0) * AH_KROW + c4 * 4) =
-        make_uint2(__builtin_bit_cast(unsigned, ah_f16x2{a1[0], a1[1]}), __builtin_bit_cast(unsigned, ah_f16x2{a1[2], a1[3]}));
+        make_uint2(__builtin_bit_cast(unsigned, f16x2{a1[0], a1[1]}), __builtin_bit_cast(unsigned, f16x2{a1[2], a1[3]}));
     *reinterpret_cast<uint2*>(rimg + (r0 + 1) * AH_KROW + c4 * 4) =
-        make_uint2(__builtin_bit_cast(unsigned, ah_f16x2{b0[0], b0[1]}), __builtin_bit_cast(unsigned, ah_f16x2{b0[2], b0[3]}));
+        make_uint2(__builtin_bit_cast(unsigned, f16x2{b0[0], b0[1]}), __builtin_bit_cast(unsigned, f16x2{b0[2], b0[3]}));
     *reinterpret_cast<uint2*>(rimg + (CH + r0 + 1) * AH_KROW + c4 * 4) =
-        make_uint2(__builtin_bit_cast(unsigned, ah_f16x2{b1[0], b1[1]}), __builtin_bit_cast(unsigned, ah_f16x2{b1[2], b1[3]}));
+        make_uint2(__builtin_bit_cast(unsigned, f16x2{b1[0], b1[1]}), __builtin_bit_cast(unsigned, f16x2{b1[2], b1[3]}));
   }
 }
 // a lane's fragment of its own row: 4 chunks of 16 d, 8 consecutive d per lane half
-__device__ __forceinline__ void ah_row_frag(const float* row, int lh, float scale, ah_u32x4 (&t0)[4], ah_u32x4 (&t1)[4]) {
+__device__ __forceinline__ void ah_row_frag(const float* row, int lh, float scale, u32x4 (&t0)[4], u32x4 (&t1)[4]) {
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const f32x4 lo = *reinterpret_cast<const f32x4*>(row + 16 * c + 8 * lh);
     const f32x4 hi = *reinterpret_cast<const f32x4*>(row + 16 * c + 8 * lh + 4);
     const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    ah_split8(v, scale, t0[c], t1[c]);
+    split2_oct(v, scale, t0[c], t1[c]);
   }
 }
 // 32 x 32 tile: rows of a row image (A operand, reduction over d) times the lane's fragment
-__device__ __forceinline__ f32x16 ah_rows_times_frag(const unsigned short* img, int CH, int row0, const ah_u32x4 (&f0)[4], const ah_u32x4 (&f1)[4],
+__device__ __forceinline__ f32x16 ah_rows_times_frag(const unsigned short* img, int CH, int row0, const u32x4 (&f0)[4], const u32x4 (&f1)[4],
                                                      int lr, int lh) {
   f32x16 acc;
 #pragma unroll
@@ -293,7 +270,7 @@ __device__ __forceinline__ f32x16 ah_rows_times_frag(const unsigned short* img, 
   const unsigned short* rp = img + (row0 + lr) * AH_KROW + 8 * lh;
 #pragma unroll
   for (int c = 0; c < 4; ++c)
-    acc = ah_mfma3(*reinterpret_cast<const ah_u32x4*>(rp + 16 * c), *reinterpret_cast<const ah_u32x4*>(rp + CH * AH_KROW + 16 * c), f0[c], f1[c], acc);
+    acc = ah_mfma3(*reinterpret_cast<const u32x4*>(rp + 16 * c), *reinterpret_cast<const u32x4*>(rp + CH * AH_KROW + 16 * c), f0[c], f1[c], acc);
   return acc;
 }
 // o^T[d][lane] += sum over the tile's 32 rows of timg[d][row] * t[row] (t in the accumulator layout, scaled by `scale` for the split)
@@ -302,12 +279,12 @@ __device__ __forceinline__ void ah_accum_T(f32x16 (&o)[2], const unsigned short*
 #pragma unroll
   for (int sl = 0; sl < 2; ++sl) {
     const float tv[8] = {t[8 * sl], t[8 * sl + 1], t[8 * sl + 2], t[8 * sl + 3], t[8 * sl + 4], t[8 * sl + 5], t[8 * sl + 6], t[8 * sl + 7]};
-    ah_u32x4 b0, b1;
-    ah_split8(tv, scale, b0, b1);
+    u32x4 b0, b1;
+    split2_oct(tv, scale, b0, b1);
 #pragma unroll
     for (int db = 0; db < 2; ++db) {
       const unsigned short* vp = timg + (db * 32 + lr) * VROW + row0 + 16 * sl + 8 * lh;
-      o[db] = ah_mfma3(*reinterpret_cast<const ah_u32x4*>(vp), *reinterpret_cast<const ah_u32x4*>(vp + 64 * VROW), b0, b1, o[db]);
+      o[db] = ah_mfma3(*reinterpret_cast<const u32x4*>(vp), *reinterpret_cast<const u32x4*>(vp + 64 * VROW), b0, b1, o[db]);
     }
   }
 }
@@ -339,9 +316,9 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_h3_kernel(const float* __
   const long rs = (long)heads * 192, ro = (long)heads * 64;
   const float* base = qkv + (long)b * L * rs + h * 192;
   const float aq = adm_amax_read(amax_qkv), ag = adm_amax_read(amax_g);
-  const float sc = ah_scale(aq), sg = ah_scale(ag), sd = ah_scale(128.f * aq * ag);
+  const float sc = split_scale(aq), sg = split_scale(ag), sd = split_scale(128.f * aq * ag);
   const int q = (int)blockIdx.y * 32 * NW + wid * 32 + lr;      // (gridDim.y = L / 256 for the long sequences)
-  ah_u32x4 q0[4], q1[4], g0[4], g1[4];
+  u32x4 q0[4], q1[4], g0[4], g1[4];
   ah_row_frag(base + (long)q * rs, lh, sc * 0.125f, q0, q1);
   const float* grow = dout + ((long)b * L + q) * ro + h * 64;
   const float* orow = out + ((long)b * L + q) * ro + h * 64;
@@ -401,9 +378,9 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_dkv_h3_kernel(const float* _
   const long rs = (long)heads * 192, ro = (long)heads * 64;
   const float* base = qkv + (long)b * L * rs + h * 192;
   const float aq = adm_amax_read(amax_qkv), ag = adm_amax_read(amax_g);
-  const float sc = ah_scale(aq), sg = ah_scale(ag), sd = ah_scale(128.f * aq * ag);
+  const float sc = split_scale(aq), sg = split_scale(ag), sd = split_scale(128.f * aq * ag);
   const int key = (int)blockIdx.y * 32 * NW + wid * 32 + lr;
-  ah_u32x4 k0f[4], k1f[4], v0f[4], v1f[4];
+  u32x4 k0f[4], k1f[4], v0f[4], v1f[4];
   ah_row_frag(base + (long)key * rs + 64, lh, sc * 0.125f, k0f, k1f);
   ah_row_frag(base + (long)key * rs + 128, lh, sc, v0f, v1f);
   const float inv_s = 1.f / (sc * sc), inv_g = 1.f / (sg * sc);

@@ -13,8 +13,38 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 #include "../../include/adm_hip.h"
+
+// Functions one kernel file defines and another calls, outside the C ABI of include/adm_hip.h.
+// conv_igemm.hip: y = sum of the splitk partial outputs ws[splitk][M][N] (+ bias) (+ res)
+int adm_splitk_reduce(const float* ws, const float* bias, const float* res, float* y, long M, int N, int ldy, int ldr, int splitk,
+                      hipStream_t stream);
+// conv_wgrad_wino.hip; mode 0 / 1 (up) / 2 (2-D)
+int adm_wgrad_wino_plan(int B, int H, int W, int Cin, int Cout, int mode);
+int adm_wgrad_wino_ws(const float* x, const float* dy, float* ws, float* bws, int B, int H, int W, int Cin, int ldx, int Cout,
+                      int lddy, int splits, int mode, hipStream_t stream);
+
 #ifdef __HIPCC__
+// Workgroup -> tile map, XCD-aware: the hardware deals consecutive block ids round-robin over the 8 XCDs, each with its own L2.
+// This bijective remap gives every XCD a CONTIGUOUS chunk of the logical list, so the workgroups resident on one XCD at a time are
+// neighbours in the caller's order (conv_igemm.hip says what that buys).  Placement only affects speed / traffic, never results.
+__device__ __forceinline__ int adm_xcd_remap(int bid, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+// LDS-only workgroup barrier: waits for this wave's LDS traffic (lgkmcnt), NOT for its global loads
+__device__ __forceinline__ void adm_lds_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
 // bound vectors (ADM_AMAX_SLOTS x ADM_AMAX_STRIDE floats: include/adm_hip.h).  Producer side: the wave's maximum goes to the slot of this
 // wave; consumer side: every lane reads one slot, wave maximum (all lanes return it).
 __device__ __forceinline__ void adm_amax_commit(float am, float* amax) {

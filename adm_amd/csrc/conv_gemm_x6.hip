@@ -1,6 +1,6 @@
 // 1x1 convolution / pixel-wise linear map (forward and data gradient) with the f32 products carried on the bf16 MFMA through the exact
-// three-term bf16 split of both operands (the arithmetic of conv_wino2d_x6.hip: a = a0 + a1 + a2 exactly, six bf16 products per f32
-// product, f32 accumulation, error at the f32 MFMA's level):
+// three-term bf16 split of both operands (split_format.h: six bf16 products per f32 product, f32 accumulation, error at the f32
+// MFMA's level; FMT 1: the two-term fp16 split, three products):
 //     y[m][n] = sum_k x[m][k] w[n][k] (+ bias[n]) (+ res[m][n])          m = pixel (NHWC row), k = input channel
 // Structure = conv_wino2d_x6.hip's without the Winograd transforms (512 threads, one workgroup per CU, wave-specialised):
 //   * workgroup tile 128 pixels x 128 couts, K step 32 channels (two 16-channel chunks) per stage and barrier;
@@ -14,7 +14,7 @@
 // Used for 1x1 convs with M >= 8192, N >= 128 (a ragged last 128-cout tile reads zero rows), K % 32 == 0 (ADM_BF16X6=0 keeps them on conv_igemm.hip).
 // Replaces F.conv2d (1x1) of Conv2d.forward and its data gradient (/root/reference/unet/uncond_unet.py:98-110).
 #include "common.h"
-#include "../../include/adm_hip.h"
+#include "split_format.h"
 
 namespace {
 
@@ -26,85 +26,28 @@ struct G6P {
 };
 
 typedef __attribute__((address_space(3))) void g6_lds_void;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int GM = 128, GN = 128, GCH = 2;         // pixels x couts per workgroup, 16-channel chunks per stage
-// FMT 0: three bf16 terms by truncation, six products.  FMT 1: s a = h0 + h1 (two fp16 terms, round to nearest; s a power of two from a
-// bound of max |a|: 16000 / max < s <= 32000 / max -- no Winograd sums here, the factor 4 of conv_wino2d_x6.hip is kept so that one
-// rule serves all kernels), three products; the weights carry the fixed scale of the fp16 images (adm_split2_rows_f16).
+// FMT = the split number format of split_format.h (no Winograd sums here; the scale rule keeps their factor 4 so that one rule serves
+// all kernels); the weights carry the fixed scale of the fp16 images (adm_split2_rows_f16).
 template <int FMT> struct G6Fmt {
-  static constexpr int TERMS = FMT ? 2 : 3;
+  static constexpr int TERMS = split_terms(FMT);
   static constexpr int IMG = GCH * TERMS * 128 * 16;      // 16-bit elements of one operand image of a stage: [chunk][term][128 rows][16] = 24 / 16 KB
   static constexpr int QW = 2 * TERMS;                    // one-KB DMA instructions per consumer wave and stage
 };
-typedef _Float16 g6_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 g6_f16x2 __attribute__((ext_vector_type(2)));
-__device__ inline float g6_scale(float amax) {      // = h3_scale of conv_wino2d_x6.hip
-  if (!(amax > 0.f) || !(amax < 3e38f)) return 1.f;
-  int e;
-  frexpf(16000.f / amax, &e);
-  return ldexpf(1.f, e - 1);
-}
 constexpr int G_RA = 2, G_RB = 4, G_D = 4;         // A slots, B slots, producer prefetch depth in stages
-
-// plain v_sub_f32 (not the packed form): next to the bf16 MFMA of the consumer wave on the same SIMD plain VALU is ~93 % hidden,
-// v_pk_add_f32 not at all (tools/overlap_probe2.hip; conv_wino2d_x6.hip)
-__device__ __forceinline__ f32x4 g6_sub4(f32x4 a, f32x4 b) {
-  f32x4 r;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) asm("v_sub_f32 %0, %1, %2" : "=v"(r[i]) : "v"(a[i]), "v"(b[i]));
-  return r;
-}
-__device__ __forceinline__ void g6_split3(const f32x4 v, u32x2& t0, u32x2& t1, u32x2& t2) {
-  f32x4 h, mh;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) h[i] = __uint_as_float(__float_as_uint(v[i]) & 0xFFFF0000u);
-  const f32x4 r = g6_sub4(v, h);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) mh[i] = __uint_as_float(__float_as_uint(r[i]) & 0xFFFF0000u);
-  const f32x4 r2 = g6_sub4(r, mh);
-  t0 = u32x2{__builtin_amdgcn_perm(__float_as_uint(v[1]), __float_as_uint(v[0]), 0x07060302u),
-             __builtin_amdgcn_perm(__float_as_uint(v[3]), __float_as_uint(v[2]), 0x07060302u)};
-  t1 = u32x2{__builtin_amdgcn_perm(__float_as_uint(r[1]), __float_as_uint(r[0]), 0x07060302u),
-             __builtin_amdgcn_perm(__float_as_uint(r[3]), __float_as_uint(r[2]), 0x07060302u)};
-  t2 = u32x2{__builtin_amdgcn_perm(__float_as_uint(r2[1]), __float_as_uint(r2[0]), 0x07060302u),
-             __builtin_amdgcn_perm(__float_as_uint(r2[3]), __float_as_uint(r2[2]), 0x07060302u)};
-}
-__device__ __forceinline__ void g6_split2(const f32x4 v, float s, u32x2& t0, u32x2& t1) {
-  _Float16 h0[4], h1[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float vs = v[i] * s;
-    h0[i] = (_Float16)vs;
-    h1[i] = (_Float16)(vs - (float)h0[i]);
-  }
-  t0 = u32x2{__builtin_bit_cast(unsigned, g6_f16x2{h0[0], h0[1]}), __builtin_bit_cast(unsigned, g6_f16x2{h0[2], h0[3]})};
-  t1 = u32x2{__builtin_bit_cast(unsigned, g6_f16x2{h1[0], h1[1]}), __builtin_bit_cast(unsigned, g6_f16x2{h1[2], h1[3]})};
-}
-__device__ __forceinline__ void g6_barrier() {     // waits for this wave's LDS traffic only
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 
 template <int FMT>
 __global__ __launch_bounds__(512) void gemm_x6_kernel(G6P p) {
   constexpr int G_IMG = G6Fmt<FMT>::IMG, TERMS = G6Fmt<FMT>::TERMS, QW = G6Fmt<FMT>::QW;
   float sa = 1.f, inv_scale = 1.f;
-  if (FMT) { sa = g6_scale(adm_amax_read(p.amax_x)); inv_scale = 1.f / (sa * p.wscale); }
+  if (FMT) { sa = split_scale(adm_amax_read(p.amax_x)); inv_scale = 1.f / (sa * p.wscale); }
   extern __shared__ __attribute__((aligned(16))) unsigned short smg[];
   unsigned short* As = smg;                        // [G_RA][chunk][term][128 pixels][16]
   unsigned short* Bs = smg + G_RA * G_IMG;         // [G_RB][chunk][term][128 couts][16]
   const int tid = threadIdx.x, lane = tid & 63, hw_wid = tid >> 6;
   const bool producer = hw_wid >= 4;
   const int wid = hw_wid & 3;
-  int bid = blockIdx.x;
-  {   // XCD-aware bijective remap, m-fastest inside an n-tile (see conv_igemm.hip)
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = adm_xcd_remap(blockIdx.x, gridDim.x);
   const int tilesM = gridDim.x / p.tilesN;
   const int tm = bid % tilesM, tn = bid / tilesM;
   const int m0 = tm * GM, n0 = tn * GN;
@@ -144,13 +87,13 @@ __global__ __launch_bounds__(512) void gemm_x6_kernel(G6P p) {
         unsigned short* l = la[j] + slot * G_IMG;
         if (FMT) {
           u32x2 h0, h1;
-          g6_split2(d[set][j], sa, h0, h1);
+          split2_quad(d[set][j], sa, h0, h1);
           *reinterpret_cast<u32x2*>(l) = h0;
           *reinterpret_cast<u32x2*>(l + 128 * 16) = h1;
           continue;
         }
         u32x2 t0, t1, t2;
-        g6_split3(d[set][j], t0, t1, t2);
+        split3_quad(d[set][j], t0, t1, t2);
         *reinterpret_cast<u32x2*>(l) = t0;
         *reinterpret_cast<u32x2*>(l + 128 * 16) = t1;
         *reinterpret_cast<u32x2*>(l + 2 * 128 * 16) = t2;
@@ -168,7 +111,7 @@ __global__ __launch_bounds__(512) void gemm_x6_kernel(G6P p) {
           __builtin_amdgcn_sched_barrier(0);
           issue(k, s0 + k + G_D);
           __builtin_amdgcn_sched_barrier(0);
-          g6_barrier();
+          adm_lds_barrier();
         }
       }
     }
@@ -243,8 +186,8 @@ __global__ __launch_bounds__(512) void gemm_x6_kernel(G6P p) {
         for (int ni = 0; ni < 2; ++ni) {
           f32x16 c;
           if (FMT) {                                 // three fp16 products, small ones first
-            const g6_f16x8 a0 = __builtin_bit_cast(g6_f16x8, a[mi][0]), a1 = __builtin_bit_cast(g6_f16x8, a[mi][1]);
-            const g6_f16x8 b0 = __builtin_bit_cast(g6_f16x8, b[ni][0]), b1 = __builtin_bit_cast(g6_f16x8, b[ni][1]);
+            const f16x8 a0 = __builtin_bit_cast(f16x8, a[mi][0]), a1 = __builtin_bit_cast(f16x8, a[mi][1]);
+            const f16x8 b0 = __builtin_bit_cast(f16x8, b[ni][0]), b1 = __builtin_bit_cast(f16x8, b[ni][1]);
             c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, (first && ch == 0) ? zero : acc[mi][ni], 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, c, 0, 0, 0);
             acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, c, 0, 0, 0);
@@ -302,26 +245,17 @@ __global__ __launch_bounds__(512) void gemm_x6_kernel(G6P p) {
   adm_amax_commit(am, p.amax_y);      // (all four consumer waves arrive here with all lanes)
 }
 
-// dst[k / 16][term][row][16] (bf16 bit patterns) <- the exact three-term split of src[row][k] (f32): the B operand of gemm_x6_kernel
+// dst[k / 16][term][row][16] (rows_image_offset, split_format.h) <- the exact three-term split of src[row][k] (f32): the B operand of
+// gemm_x6_kernel
 __global__ void split3_rows_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, int rows, int cols, int ld) {
   const long total = (long)rows * cols;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int n = (int)(i / cols), c = (int)(i - (long)n * cols);
-    const float a = src[(long)n * ld + c];
-    const unsigned u = __float_as_uint(a);
-    const float r = a - __uint_as_float(u & 0xFFFF0000u);
-    const unsigned m = __float_as_uint(r);
-    const float r2 = r - __uint_as_float(m & 0xFFFF0000u);
-    unsigned short* d = dst + ((((long)(c >> 4) * 3) * rows + n) << 4) + (c & 15);
-    const long term = (long)rows << 4;
-    d[0] = (unsigned short)(u >> 16);
-    d[term] = (unsigned short)(m >> 16);
-    d[2 * term] = (unsigned short)(__float_as_uint(r2) >> 16);
+    split3_store(src[(long)n * ld + c], dst + rows_image_offset(3, rows, n, c), split_term_stride(rows));
   }
 }
 
-// fp16 format: dst[k / 16][term(2)][row][16] <- the two-term round-to-nearest split of scale * src[row][k]; *overflow is raised when a
-// scaled value leaves the fp16 range
+// fp16 format: the two-term split of scale * src[row][k]; *overflow is raised when a scaled value leaves the fp16 range
 __global__ void split2_rows_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, int rows, int cols, int ld, float scale,
                                    int* __restrict__ overflow) {
   const long total = (long)rows * cols;
@@ -329,11 +263,8 @@ __global__ void split2_rows_kernel(const float* __restrict__ src, unsigned short
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int n = (int)(i / cols), c = (int)(i - (long)n * cols);
     const float a = src[(long)n * ld + c] * scale;
-    bad |= !(fabsf(a) < 65000.f);
-    const _Float16 h0 = (_Float16)a, h1 = (_Float16)(a - (float)h0);
-    unsigned short* d = dst + ((((long)(c >> 4) * 2) * rows + n) << 4) + (c & 15);
-    d[0] = __builtin_bit_cast(unsigned short, h0);
-    d[(long)rows << 4] = __builtin_bit_cast(unsigned short, h1);
+    bad |= split_f16_overflow(a);
+    split2_store(a, dst + rows_image_offset(2, rows, n, c), split_term_stride(rows));
   }
   if (bad && overflow) *overflow = 1;
 }

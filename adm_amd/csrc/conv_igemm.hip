@@ -54,11 +54,7 @@ __global__ __launch_bounds__(256) void igemm_f32_kernel(IgemmP p) {
   // L2.  Give every XCD a CONTIGUOUS chunk of the tile list (bijective remap) and order the list m-fastest inside an
   // n-tile, so the workgroups resident on one XCD at a time share the same weight slice (BN x K floats, fits the 4 MB
   // L2) and neighbouring pixel tiles (shared halo rows).  Placement only affects speed / traffic, never results.
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = adm_xcd_remap(blockIdx.x, gridDim.x);
   const int tilesM = gridDim.x / p.tilesN;
   const int tm = bid % tilesM, tn = bid / tilesM;
   const int m0 = tm * BM, n0 = tn * BN;

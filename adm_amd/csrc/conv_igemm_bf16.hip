@@ -15,7 +15,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 
@@ -50,11 +49,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_kernel(IgemmBP p) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN;
   const int lr = lane & 31, lh = lane >> 5;
-  int bid = blockIdx.x;
-  {   // XCD-aware bijective remap, m-fastest inside an n-tile (see conv_igemm.hip)
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = adm_xcd_remap(blockIdx.x, gridDim.x);
   const int tilesM = gridDim.x / p.tilesN;
   const int tm = bid % tilesM, tn = bid / tilesM;
   const int m0 = tm * BM, n0 = tn * BN;

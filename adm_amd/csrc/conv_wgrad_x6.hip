@@ -1,6 +1,6 @@
 // Weight gradient of the 3x3 stride-1 convs: transposed 2-D Winograd F(3x3, 2x2) (conv_wgrad_wino.hip, MODE 2) with the f32 products
-// carried on the bf16 MFMA through the exact three-term bf16 split of BOTH operands (see conv_wino2d_x6.hip for the arithmetic:
-// a = a0 + a1 + a2 exactly, six bf16 products per f32 product, f32 accumulation, error at the f32 MFMA's level).
+// carried on the 16-bit MFMA through the split of BOTH operands (split_format.h: six bf16 or three fp16 products per f32 product,
+// f32 accumulation, error at the f32 MFMA's level).
 //
 //   per 2x2 tile of dY and the 4x4 patch of X around it:  a = A e A^T,  b = B^T d B,  m[ey][ex] = sum_tiles a[ey][ex] (x) b[ey][ex],
 //   dW = G^T m G.   As in the f32 kernel the pass `ey` belongs to the workgroup: it reduces over TILES the y-combined rows
@@ -29,7 +29,7 @@
 // Replaces the autograd weight gradient of Conv2d.forward (/root/reference/unet/uncond_unet.py:98-110).
 #include <algorithm>
 #include "common.h"
-#include "../../include/adm_hip.h"
+#include "split_format.h"
 
 #ifndef XW_D
 #define XW_D (CB == 2 ? 2 : 3)      // producer register sets = stages of loads in flight (sixteen waves: 128 registers, two sets)
@@ -49,53 +49,19 @@ struct WxP {
   const float* amax_x; const float* amax_dy;     // FMT 1 only: device upper bounds of |x| and |dy| (the per-tensor scales come from them)
 };
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 constexpr int XT = 64, XK = 16;                    // 64 x 64 channel tile, 16 tiles (2x2 pixels each) per stage
 constexpr int XROW = 96;                           // bf16 elements per LDS row: 64 channels + 32 of padding (192 bytes)
-// FMT 0: three bf16 terms by truncation, six products.  FMT 1: s v = h0 + h1, two fp16 terms (round to nearest), s a power of two
-// from an upper bound of the tensor's |v| (conv_wino2d_x6.hip: s max|v| <= 16000, the transforms' sums of four stay finite); three
-// products (h0 h0' + h0 h1' + h1 h0'), the scales undone once in the epilogue.  Same accuracy (tools/fp16x3_accuracy.py).
+// FMT = the split number format of split_format.h; FMT 1 takes one scale per tensor from the device bounds of |x| and |dy|, both
+// undone once in the epilogue.
 template <int FMT> struct XFmt {
-  static constexpr int TERMS = FMT ? 2 : 3;
+  static constexpr int TERMS = split_terms(FMT);
   static constexpr int IMG = 4 * TERMS * XK * XROW;     // one operand image of a stage: [4 ex][TERMS][16 tiles][XROW] = 36 / 24 KB
 };
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-__device__ inline float xh3_scale(float amax) {       // = h3_scale of conv_wino2d_x6.hip
-  if (!(amax > 0.f) || !(amax < 3e38f)) return 1.f;
-  int e;
-  frexpf(16000.f / amax, &e);
-  return ldexpf(1.f, e - 1);
-}
 
-// All the arithmetic next to the MFMAs is written with PLAIN (one value per lane) f32 instructions: tools/overlap_probe2.hip
-// measures v_add_f32 / v_and_b32 / v_perm_b32 of another wave 91-96 % hidden behind v_mfma_f32_32x32x16_bf16 on the same SIMD, and
-// the packed forms (v_pk_add_f32, v_pk_fma_f32) not at all -- they share the matrix pipe's data path, so "half the instructions"
-// costs the whole instruction.  The compiler packs every pair of f32 adds it sees, hence the inline assembly.
-__device__ __forceinline__ float x_add(float a, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float x_sub(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ f32x4 add4x(f32x4 a, f32x4 b) { return f32x4{x_add(a[0], b[0]), x_add(a[1], b[1]), x_add(a[2], b[2]), x_add(a[3], b[3])}; }
-__device__ __forceinline__ f32x4 sub4x(f32x4 a, f32x4 b) { return f32x4{x_sub(a[0], b[0]), x_sub(a[1], b[1]), x_sub(a[2], b[2]), x_sub(a[3], b[3])}; }
-// v = v0 + v1 + v2 exactly, each term a bf16 (packed top halves: two dwords per term for the four channels)
-__device__ __forceinline__ void split3x(const f32x4 v, u32x2& t0, u32x2& t1, u32x2& t2) {
-  f32x4 h, mh;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) h[i] = __uint_as_float(__float_as_uint(v[i]) & 0xFFFF0000u);
-  const f32x4 r = sub4x(v, h);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) mh[i] = __uint_as_float(__float_as_uint(r[i]) & 0xFFFF0000u);
-  const f32x4 r2 = sub4x(r, mh);
-  t0 = u32x2{__builtin_amdgcn_perm(__float_as_uint(v[1]), __float_as_uint(v[0]), 0x07060302u),
-             __builtin_amdgcn_perm(__float_as_uint(v[3]), __float_as_uint(v[2]), 0x07060302u)};
-  t1 = u32x2{__builtin_amdgcn_perm(__float_as_uint(r[1]), __float_as_uint(r[0]), 0x07060302u),
-             __builtin_amdgcn_perm(__float_as_uint(r[3]), __float_as_uint(r[2]), 0x07060302u)};
-  t2 = u32x2{__builtin_amdgcn_perm(__float_as_uint(r2[1]), __float_as_uint(r2[0]), 0x07060302u),
-             __builtin_amdgcn_perm(__float_as_uint(r2[3]), __float_as_uint(r2[2]), 0x07060302u)};
-}
+// All the arithmetic next to the MFMAs is written with the PLAIN (one value per lane) f32 helpers of split_format.h.
+
 // a + sgn b, sgn = +-1 uniform (exact; one fma per value -- a uniform "add or subtract" written as a conditional costs a branch per use)
 __device__ __forceinline__ f32x4 fma4s(f32x4 a, f32x4 b, f32x2 sgn) {
   f32x4 r;
@@ -103,24 +69,13 @@ __device__ __forceinline__ f32x4 fma4s(f32x4 a, f32x4 b, f32x2 sgn) {
   for (int i = 0; i < 4; ++i) asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r[i]) : "v"(b[i]), "v"(sgn[0]), "v"(a[i]));
   return r;
 }
-__device__ __forceinline__ void split2x(const f32x4 v, float s, u32x2& t0, u32x2& t1) {
-  _Float16 h0[4], h1[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float vs = v[i] * s;
-    h0[i] = (_Float16)vs;
-    h1[i] = (_Float16)(vs - (float)h0[i]);
-  }
-  t0 = u32x2{__builtin_bit_cast(unsigned, f16x2{h0[0], h0[1]}), __builtin_bit_cast(unsigned, f16x2{h0[2], h0[3]})};
-  t1 = u32x2{__builtin_bit_cast(unsigned, f16x2{h1[0], h1[1]}), __builtin_bit_cast(unsigned, f16x2{h1[2], h1[3]})};
-}
 template <int FMT>
 __device__ __forceinline__ void store_planes(const f32x4 (&v)[4], unsigned short* l, float s) {
   if (FMT) {
 #pragma unroll
     for (int ex = 0; ex < 4; ++ex) {
       u32x2 t0, t1;
-      split2x(v[ex], s, t0, t1);
+      split2_quad(v[ex], s, t0, t1);
       *reinterpret_cast<u32x2*>(l + (ex * 2 + 0) * XK * XROW) = t0;
       *reinterpret_cast<u32x2*>(l + (ex * 2 + 1) * XK * XROW) = t1;
     }
@@ -129,16 +84,11 @@ __device__ __forceinline__ void store_planes(const f32x4 (&v)[4], unsigned short
 #pragma unroll
   for (int ex = 0; ex < 4; ++ex) {
     u32x2 t0, t1, t2;
-    split3x(v[ex], t0, t1, t2);
+    split3_quad(v[ex], t0, t1, t2);
     *reinterpret_cast<u32x2*>(l + (ex * 3 + 0) * XK * XROW) = t0;
     *reinterpret_cast<u32x2*>(l + (ex * 3 + 1) * XK * XROW) = t1;
     *reinterpret_cast<u32x2*>(l + (ex * 3 + 2) * XK * XROW) = t2;
   }
-}
-__device__ __forceinline__ void lds_barrier() {    // waits for this wave's LDS traffic only
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
 // MODE 0: the 3x3 Winograd form above.  MODE 1: the weight gradient of a 1x1 conv, dW[co][ci] = sum_pixels dY[p][co] X[p][ci]: the same
@@ -154,7 +104,7 @@ __global__ __launch_bounds__((4 * CB + 8) * 64) void wgrad_x6_kernel(WxP p) {
   constexpr int X_IMG = XFmt<FMT>::IMG, TERMS = XFmt<FMT>::TERMS;
   constexpr int NCONS = 4 * CB;
   float s_x = 1.f, s_dy = 1.f;
-  if (FMT) { s_x = xh3_scale(adm_amax_read(p.amax_x)); s_dy = xh3_scale(adm_amax_read(p.amax_dy)); }
+  if (FMT) { s_x = split_scale(adm_amax_read(p.amax_x)); s_dy = split_scale(adm_amax_read(p.amax_dy)); }
   extern __shared__ __attribute__((aligned(16))) unsigned short smx[];
   unsigned short* As = smx;                        // [CB][2][X_IMG]  dY side: rows = tiles, columns = couts (one image per 64-cout block)
   unsigned short* Bs = smx + CB * 2 * X_IMG;       // [2][X_IMG]  X side:  rows = tiles, columns = cins
@@ -168,11 +118,7 @@ __global__ __launch_bounds__((4 * CB + 8) * 64) void wgrad_x6_kernel(WxP p) {
   // workgroups of one XCD walk ONE pixel range (and its neighbours) together -- all of a range's (cout tile, cin tile, ey)
   // workgroups read the same x and dy rows.  Dealt round-robin, every XCD streamed every range through its own 4 MB L2
   // (47 % L2 misses, 0.6 GB per launch from the Infinity Cache for 0.2 GB of operands) and the loads, not the SIMDs, set the pace
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = adm_xcd_remap(blockIdx.x, gridDim.x);
   constexpr int NEY = MODE == 1 ? 1 : 4;
   const int bz = bid / (p.tiles * NEY), brem = bid - bz * (p.tiles * NEY);
   const int by = brem / p.tiles, bx = brem - by * p.tiles;
@@ -288,8 +234,8 @@ __global__ __launch_bounds__((4 * CB + 8) * 64) void wgrad_x6_kernel(WxP p) {
     auto store = [&](int d, int slot) {            // y combination, x transforms, split, into slot
       if (XW_ABL & 2) return;
       if (MODE == 1) {
-        if (do_bias) bsum = add4x(bsum, add4x(add4x(u0[d][0], u0[d][1]), add4x(u0[d][2], u0[d][3])));
-        if (do_bias && CB == 2) bsum1 = add4x(bsum1, add4x(add4x(u1[d][0], u1[d][1]), add4x(u1[d][2], u1[d][3])));
+        if (do_bias) bsum = plain_add4(bsum, plain_add4(plain_add4(u0[d][0], u0[d][1]), plain_add4(u0[d][2], u0[d][3])));
+        if (do_bias && CB == 2) bsum1 = plain_add4(bsum1, plain_add4(plain_add4(u1[d][0], u1[d][1]), plain_add4(u1[d][2], u1[d][3])));
         if (!x_side && CB == 2) store_planes<FMT>(u1[d], la + (2 + slot) * X_IMG, s_dy);
         if (x_side && XBF) {
           const f32x4 w[4] = {wide4(u0[d][0]), wide4(u0[d][1]), wide4(u0[d][2]), wide4(u0[d][3])};
@@ -302,13 +248,13 @@ __global__ __launch_bounds__((4 * CB + 8) * 64) void wgrad_x6_kernel(WxP p) {
       if (!x_side) {
         const f32x4 e[2] = {fma4s(u0[d][0], u0[d][2], sgn), fma4s(u0[d][1], u0[d][3], sgn)};     // r0 +- r1 (an unused row was read as zeros)
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-        const f32x4 a[4] = {e[0], add4x(e[0], e[1]), sub4x(e[0], e[1]), sub4x(zero, e[1])};
-        if (do_bias) bsum = add4x(bsum, a[1]);
+        const f32x4 a[4] = {e[0], plain_add4(e[0], e[1]), plain_sub4(e[0], e[1]), plain_sub4(zero, e[1])};
+        if (do_bias) bsum = plain_add4(bsum, a[1]);
         store_planes<FMT>(a, la + slot * X_IMG, s_dy);
         if (CB == 2) {
           const f32x4 f[2] = {fma4s(u1[d][0], u1[d][2], sgn), fma4s(u1[d][1], u1[d][3], sgn)};
-          const f32x4 c[4] = {f[0], add4x(f[0], f[1]), sub4x(f[0], f[1]), sub4x(zero, f[1])};
-          if (do_bias) bsum1 = add4x(bsum1, c[1]);
+          const f32x4 c[4] = {f[0], plain_add4(f[0], f[1]), plain_sub4(f[0], f[1]), plain_sub4(zero, f[1])};
+          if (do_bias) bsum1 = plain_add4(bsum1, c[1]);
           store_planes<FMT>(c, la + (2 + slot) * X_IMG, s_dy);
         }
         return;
@@ -316,7 +262,7 @@ __global__ __launch_bounds__((4 * CB + 8) * 64) void wgrad_x6_kernel(WxP p) {
       f32x4 dd[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) dd[j] = fma4s(wide4(u0[d][j]), wide4(u1[d][j]), sgn);     // rows iA +- iB; the pass ey = 2 wants iB - iA: the epilogue negates
-      const f32x4 b[4] = {sub4x(dd[0], dd[2]), add4x(dd[1], dd[2]), sub4x(dd[2], dd[1]), sub4x(dd[1], dd[3])};
+      const f32x4 b[4] = {plain_sub4(dd[0], dd[2]), plain_add4(dd[1], dd[2]), plain_sub4(dd[2], dd[1]), plain_sub4(dd[1], dd[3])};
       store_planes<FMT>(b, lb + slot * X_IMG, s_x);
     };
 #pragma unroll
@@ -331,7 +277,7 @@ __global__ __launch_bounds__((4 * CB + 8) * 64) void wgrad_x6_kernel(WxP p) {
           __builtin_amdgcn_sched_barrier(0);
           issue(k % D, s0 + k + D);
           __builtin_amdgcn_sched_barrier(0);
-          lds_barrier();
+          adm_lds_barrier();
         }
       }
     }
@@ -343,10 +289,10 @@ __global__ __launch_bounds__((4 * CB + 8) * 64) void wgrad_x6_kernel(WxP p) {
         for (int j = 0; j < 4; ++j) { bsum1[j] += __shfl_xor(bsum1[j], 16, 64); bsum1[j] += __shfl_xor(bsum1[j], 32, 64); }
       }
       float* red = reinterpret_cast<float*>(smx);  // every image has been consumed: the consumers are past the last barrier ...
-      lds_barrier();                               // ... once they arrive here (all waves make the same two extra barriers)
+      adm_lds_barrier();                               // ... once they arrive here (all waves make the same two extra barriers)
       if (do_bias && lane < 16) *reinterpret_cast<f32x4*>(red + (wid * 16 + lane) * 4) = bsum;
       if (do_bias && CB == 2 && lane < 16) *reinterpret_cast<f32x4*>(red + ((4 + wid) * 16 + lane) * 4) = bsum1;
-      lds_barrier();
+      adm_lds_barrier();
 #pragma unroll
       for (int hb = 0; hb < CB; ++hb) {
         if (do_bias && wid == 0 && lane < 16 && (hb ? a_col1 : a_col) != OOB) {
@@ -364,8 +310,8 @@ __global__ __launch_bounds__((4 * CB + 8) * 64) void wgrad_x6_kernel(WxP p) {
     };
     if (hw_wid >= NCONS + 4) produce(std::true_type{});
     else produce(std::false_type{});
-    lds_barrier();                                 // the consumers' plane exchange (two barriers for all twelve waves)
-    lds_barrier();
+    adm_lds_barrier();                                 // the consumers' plane exchange (two barriers for all twelve waves)
+    adm_lds_barrier();
     return;
   }
 
@@ -451,7 +397,7 @@ __global__ __launch_bounds__((4 * CB + 8) * 64) void wgrad_x6_kernel(WxP p) {
         for (int r = 0; r < 16; ++r)
           ex_t[((chalf * 4 + cpl) * XT + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * XT + nb * 32 + lr] = osgn * tot[mb][nb][r];
   }
-  lds_barrier();
+  adm_lds_barrier();
   const int ci = ci0 + lane;                       // wave w: couts 16 w .. 16 w + 15 of the tile, lane = cin (256-byte rows)
   if (ci >= p.Cin) return;
 #pragma unroll 4

@@ -44,11 +44,7 @@ __global__ __launch_bounds__(256) void igemm_wino_kernel(WinoP p) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;
   const int lr = lane & 31, lh = lane >> 5;
-  int bid = blockIdx.x;
-  {   // XCD-aware bijective remap, m-fastest inside an n-tile (see conv_igemm.hip)
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = adm_xcd_remap(blockIdx.x, gridDim.x);
   const int tilesM = gridDim.x / p.tilesN;
   const int tm = bid % tilesM, tn = bid / tilesM;
   const int mp0 = tm * WP, n0 = tn * WN_;

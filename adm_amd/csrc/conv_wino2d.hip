@@ -50,11 +50,7 @@ __global__ __launch_bounds__(256, 2) void igemm_wino2d_kernel(Wino2P p) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;
   const int lr = lane & 31, lh = lane >> 5;
-  int bid = blockIdx.x;
-  {   // XCD-aware bijective remap, m-fastest inside an n-tile (see conv_igemm.hip)
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = adm_xcd_remap(blockIdx.x, gridDim.x);
   const int tilesM = gridDim.x / p.tilesN;
   const int tm = bid % tilesM, tn = bid / tilesM;
   const int mt0 = tm * W2P, n0 = tn * W2N;
@@ -262,12 +258,6 @@ __global__ __launch_bounds__(256, 2) void igemm_wino2d_kernel(Wino2P p) {
 //   * barriers are s_barrier with LDS-scoped fences / explicit counters: global loads stay in flight across them.
 constexpr int WS_RA = 2, WS_RB = 3, WS_D = 4;     // A slots, B slots, producer prefetch depth in stages
 
-__device__ __forceinline__ void ws_barrier_lds() {          // waits for this wave's LDS traffic only
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 __global__ __launch_bounds__(768) void igemm_wino2d_ws_kernel(Wino2P p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* As = smem;                               // [WS_RA][4][W2P][W2K]
@@ -275,11 +265,7 @@ __global__ __launch_bounds__(768) void igemm_wino2d_ws_kernel(Wino2P p) {
   const int tid = threadIdx.x, lane = tid & 63, hw_wid = tid >> 6;
   const bool producer = hw_wid >= 8;              // waves 0-7 consume (two per SIMD), waves 8-11 produce (one per SIMD)
   const int wid = producer ? hw_wid - 8 : hw_wid;
-  int bid = blockIdx.x;
-  {   // XCD-aware bijective remap, m-fastest inside an n-tile (see conv_igemm.hip)
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = adm_xcd_remap(blockIdx.x, gridDim.x);
   const int tilesM = gridDim.x / p.tilesN;
   const int tm = bid % tilesM, tn = bid / tilesM;
   const int mt0 = tm * W2P, n0 = tn * W2N;
@@ -363,7 +349,7 @@ __global__ __launch_bounds__(768) void igemm_wino2d_ws_kernel(Wino2P p) {
         __builtin_amdgcn_sched_barrier(0);
         issue(d);                                 // stages past the end read nothing (all offsets out of range)
         __builtin_amdgcn_sched_barrier(0);
-        ws_barrier_lds();
+        adm_lds_barrier();
       }
     }
     return;
@@ -572,9 +558,6 @@ extern "C" int adm_pack_weight_wino2d(const float* w, float* wf, float* wb, int 
 // y[B][H][W][ldy] = conv3x3(x[B][H][W][ldx], pad 1) (+ bias) (+ res); wq = adm_pack_weight_wino2d operand with `wrows` rows per
 // plane (>= N) and K = Cin columns.  H and W even; Cin % 16 == 0.  ws (may be NULL) = workspace of ws_floats >=
 // adm_wino2d_splitk(...) * B*H*W*N floats: small launches then split K and reduce deterministically (fixed order).
-int adm_splitk_reduce(const float* ws, const float* bias, const float* res, float* y, long M, int N, int ldy, int ldr, int splitk,
-                      hipStream_t stream);       // conv_igemm.hip
-
 // Split count over the input channels for small launches: the 64-tile x 64-cout workgroups of an 8x8 map at batch 128 number
 // 192, for 512 resident slots.  Splits are chosen to fill the slots (whole rounds), keeping >= 4 chunks (64 channels) per split.
 extern "C" int adm_wino2d_splitk(int B, int H, int W, int Cin, int N) {

@@ -1,14 +1,10 @@
 // 3x3 stride-1 convolution (forward and data gradient): 2-D Winograd F(2x2, 3x3) with the f32 products carried on the bf16 MFMA.
 //
-// gfx950 has no reduced-precision fast path for f32 matrix operands: v_mfma_f32_32x32x2_f32 runs at the f32 vector rate, 1/16 of
-// the bf16 MFMA.  An f32 value splits EXACTLY into three bf16 terms, a = a0 + a1 + a2 (8 + 8 + 8 mantissa bits, same exponent
-// range, by truncation: a0 = top 16 bits of a, a1 = top 16 bits of a - a0, a2 = a - a0 - a1), and bf16 x bf16 products are exact in
-// the f32 accumulator, so
-//     a b = a0 b0 + (a0 b1 + a1 b0) + (a1 b1 + a0 b2 + a2 b0) + O(2^-24 |a b|)
-// -- six v_mfma_f32_32x32x16_bf16 (6 x 32 cycles for K = 16) replace eight v_mfma_f32_32x32x2_f32 (8 x 64 cycles): 2.67x less
-// matrix-pipe time at f32 accuracy (tools/bf16x6_probe.hip: the six products in a short accumulator chain started from C = 0
-// and added to the running sum with one f32 add measure BELOW the f32 MFMA's own rounding error against fp64, on zero-mean and
-// on all-positive data; six truncating matrix adds into one long-running accumulator would be 3x worse on the latter).
+// The split number formats are stated in split_format.h.  Specific to this kernel: six v_mfma_f32_32x32x16_bf16 (6 x 32 cycles for
+// K = 16) replace eight v_mfma_f32_32x32x2_f32 (8 x 64 cycles): 2.67x less matrix-pipe time at f32 accuracy (tools/bf16x6_probe.hip:
+// the six products in a short accumulator chain started from C = 0 and added to the running sum with one f32 add measure BELOW the
+// f32 MFMA's own rounding error against fp64, on zero-mean and on all-positive data; six truncating matrix adds into one
+// long-running accumulator would be 3x worse on the latter).
 //
 // The algorithm is conv_wino2d.hip's (same transforms, four ex accumulator tiles per wave, output rows folded in registers);
 // the loop order and the division of labour are not:
@@ -35,7 +31,7 @@
 //     (un-swizzled: 40 % of the LDS cycles were bank conflicts, SQ_LDS_BANK_CONFLICT).
 // Replaces F.conv2d of Conv2d.forward and its autograd data gradient (/root/reference/unet/uncond_unet.py:98-110).
 #include "common.h"
-#include "../../include/adm_hip.h"
+#include "split_format.h"
 #include <type_traits>
 
 #ifndef X6_TL
@@ -60,31 +56,21 @@ struct X6P {
 };
 
 typedef __attribute__((address_space(3))) void x6_lds_void;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int X6P_T = 64, X6N = 64, X6K = 16;      // tiles x couts x K step
 [[maybe_unused]] constexpr int X6_A_STAGE = 4 * 3 * X6P_T * X6K;    // bf16 elements per A sub-stage image (24 KB; the bf16 format)
 [[maybe_unused]] constexpr int X6_B_STAGE = 4 * 3 * X6N * X6K;
-// Number formats of the split (template parameter FMT of the kernel):
-//   0  a = a0 + a1 + a2, three bf16 terms by truncation, exact; a b from SIX products (small ones first, the three below 2^-24 dropped).
-//      Needs nothing but the operands.
-//   1  s a = h0 + h1, two fp16 terms by round-to-nearest, |s a - h0 - h1| <= 2^-24 |s a| while h1 is a normal fp16 number and
-//      <= 2^-25 absolutely below that; a b from THREE products (h1 h1' <= 2^-24 |a b| dropped).  s is a power of two chosen from an
-//      upper bound of max |a| so that the Winograd input transform (sums of four values) stays inside the fp16 range: the caller
-//      passes that bound as a device scalar (the GroupNorm kernel that produced the activation wrote it).  Against fp64 it is as
-//      accurate as format 0 on normal, all-positive, heavy-tailed and single-outlier data (tools/fp16x3_accuracy.py; on the GPU:
-//      tests/test_hip_ops.py::test_conv_h3_error_vs_fp64) and halves the MFMAs, the fragment reads, the split stores and the weight
-//      DMA of a stage: 1.25 -> 1.02 ms on 128 x 32 x 32 x 384 -> 384 (tools/exp_wino2d_h3.hip).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+// FMT (template parameter of the kernel) = the split number format of split_format.h: 0 three bf16 terms, six products; 1 two fp16
+// terms of s a, three products, s from a bound of max |a| that the caller passes as a device vector (the GroupNorm kernel that
+// produced the activation wrote it).  On the GPU: tests/test_hip_ops.py::test_conv_h3_error_vs_fp64; format 1 halves the MFMAs,
+// the fragment reads, the split stores and the weight DMA of a stage: 1.25 -> 1.02 ms on 128 x 32 x 32 x 384 -> 384 (the
+// experiment is tools/exp_wino2d_h3.hip of commit 29b1b0b).
 // NB = 32-cout blocks per workgroup.  2: 64 couts, four consumer waves (512 threads).  4 (the "wide" form, fp16 format only): 128
 // couts, EIGHT consumer waves, two per SIMD, next to the same four producer waves (768 threads, <= 168 registers): one A image
 // (loads from L2, transform, split, LDS stores -- the part of a stage that does not shrink with the format) now feeds twice the
 // MFMAs, and the launch pulls half the activation bytes out of the L2 (every cout tile re-reads the whole input: at Cin = 384 the
 // 64-cout form reads 74 KB per pixel, ~9.5 TB/s over the launch, more than half of what the L2s deliver).
 template <int FMT, int NB = 2> struct X6Fmt {
-  static constexpr int TERMS = FMT ? 2 : 3;
+  static constexpr int TERMS = split_terms(FMT);
   static constexpr int NT = 32 * NB;                 // couts per workgroup
   static constexpr int CONS = 2 * NB;                // consumer waves: (2 tile halves) x (NB cout blocks)
   static constexpr int THREADS = (CONS + 4) * 64;
@@ -94,73 +80,21 @@ template <int FMT, int NB = 2> struct X6Fmt {
   static constexpr int RB = NB > 2 ? 3 : 4;         // weight ring depth (LDS: 2 x 16 + 3 x 32 KB wide; 2 x 16 + 4 x 16 KB fp16, 2 x 24 + 4 x 24 KB bf16)
   static constexpr int PD = NB > 2 ? 3 : 4;         // producer register sets = stages of loads in flight
 };
-// power-of-two scale that puts 4 * amax below the fp16 range (65504): s * amax <= 16000
-__device__ __host__ inline float h3_scale(float amax) {
-  if (!(amax > 0.f) || !(amax < 3e38f)) return 1.f;
-  int e;
-  frexpf(16000.f / amax, &e);                         // 16000 / amax = m 2^e, m in [0.5, 1)
-  return ldexpf(1.f, e - 1);
-}
 constexpr int X6_RA = 2;                           // A ring depth (the weights' is X6Fmt::RB: RB - 1 stages ahead, a DMA queues behind the producers' loads)
 
-// LDS-only workgroup barrier: waits for this wave's LDS traffic (lgkmcnt), NOT for its global loads
-__device__ __forceinline__ void x6_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 // (this file is compiled WITHOUT packed-f32 instruction selection -- csrc/Makefile, NOPK -- so vector adds below are plain v_add_f32 /
-//  v_sub_f32; the explicit helpers keep the producer's arithmetic plain even if that flag is dropped)
+//  v_sub_f32; the PRODUCER's arithmetic uses the explicit plain_add4 / plain_sub4 of split_format.h)
 __device__ __forceinline__ f32x4 sub4(f32x4 a, f32x4 b) { return a - b; }
-// PRODUCER arithmetic: plain (one-lane-one-value) f32 adds.  tools/overlap_probe2.hip: next to v_mfma_f32_32x32x16_bf16 of another
-// wave on the same SIMD, v_add_f32 / v_and_b32 / v_perm_b32 are 91-96 % hidden, the PACKED forms (v_pk_add_f32, v_pk_fma_f32) not at
-// all (0-3 %: they share the matrix pipe's data path) -- the packed form halves the instruction count and doubles the cost.  The
-// compiler packs every f32x2-shaped add it sees, hence the inline assembly.
-__device__ __forceinline__ float p_add(float a, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float p_sub(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ f32x4 p_add4(f32x4 a, f32x4 b) { return f32x4{p_add(a[0], b[0]), p_add(a[1], b[1]), p_add(a[2], b[2]), p_add(a[3], b[3])}; }
-__device__ __forceinline__ f32x4 p_sub4(f32x4 a, f32x4 b) { return f32x4{p_sub(a[0], b[0]), p_sub(a[1], b[1]), p_sub(a[2], b[2]), p_sub(a[3], b[3])}; }
-
 __device__ __forceinline__ f32x16 sub16(f32x16 a, f32x16 b) { return a - b; }
 
-// v = v0 + v1 + v2 exactly, each term a bf16 (packed top halves: two dwords per term for the four channels)
-__device__ __forceinline__ void split3_pack(const f32x4 v, u32x2& t0, u32x2& t1, u32x2& t2) {
-  f32x4 h, mh;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) h[i] = __uint_as_float(__float_as_uint(v[i]) & 0xFFFF0000u);
-  const f32x4 r = p_sub4(v, h);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) mh[i] = __uint_as_float(__float_as_uint(r[i]) & 0xFFFF0000u);
-  const f32x4 r2 = p_sub4(r, mh);
-  t0 = u32x2{__builtin_amdgcn_perm(__float_as_uint(v[1]), __float_as_uint(v[0]), 0x07060302u),
-             __builtin_amdgcn_perm(__float_as_uint(v[3]), __float_as_uint(v[2]), 0x07060302u)};
-  t1 = u32x2{__builtin_amdgcn_perm(__float_as_uint(r[1]), __float_as_uint(r[0]), 0x07060302u),
-             __builtin_amdgcn_perm(__float_as_uint(r[3]), __float_as_uint(r[2]), 0x07060302u)};
-  t2 = u32x2{__builtin_amdgcn_perm(__float_as_uint(r2[1]), __float_as_uint(r2[0]), 0x07060302u),
-             __builtin_amdgcn_perm(__float_as_uint(r2[3]), __float_as_uint(r2[2]), 0x07060302u)};
-}
-
-// v * s = h0 + h1 (two fp16 terms, round to nearest), four channels -> two dwords per term
-__device__ __forceinline__ void split2_pack(const f32x4 v, float s, u32x2& t0, u32x2& t1) {
-  _Float16 h0[4], h1[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float vs = v[i] * s;
-    h0[i] = (_Float16)vs;
-    h1[i] = (_Float16)(vs - (float)h0[i]);
-  }
-  t0 = u32x2{__builtin_bit_cast(unsigned, f16x2{h0[0], h0[1]}), __builtin_bit_cast(unsigned, f16x2{h0[2], h0[3]})};
-  t1 = u32x2{__builtin_bit_cast(unsigned, f16x2{h1[0], h1[1]}), __builtin_bit_cast(unsigned, f16x2{h1[2], h1[3]})};
-}
+// producer, fp16 format: as x6_store below, two-term split of s v
 __device__ __forceinline__ void h3_store(const f32x4 (&e)[4], unsigned short* la, float s) {
   if (X6_ABL & 2) return;
-  const f32x4 v[4] = {p_sub4(e[0], e[2]), p_add4(e[1], e[2]), p_sub4(e[2], e[1]), p_sub4(e[1], e[3])};
+  const f32x4 v[4] = {plain_sub4(e[0], e[2]), plain_add4(e[1], e[2]), plain_sub4(e[2], e[1]), plain_sub4(e[1], e[3])};
 #pragma unroll
   for (int ex = 0; ex < 4; ++ex) {
     u32x2 t0, t1;
-    split2_pack(v[ex], s, t0, t1);
+    split2_quad(v[ex], s, t0, t1);
     *reinterpret_cast<u32x2*>(la + (ex * 2 + 0) * X6P_T * X6K) = t0;
     *reinterpret_cast<u32x2*>(la + (ex * 2 + 1) * X6P_T * X6K) = t1;
   }
@@ -169,11 +103,11 @@ __device__ __forceinline__ void h3_store(const f32x4 (&e)[4], unsigned short* la
 // producer: y-combined rows e[4] (one per pixel of the patch row) -> B^T along x -> three-term split -> the [ex][term] images
 __device__ __forceinline__ void x6_store(const f32x4 (&e)[4], unsigned short* la) {
   if (X6_ABL & 2) return;
-  const f32x4 v[4] = {p_sub4(e[0], e[2]), p_add4(e[1], e[2]), p_sub4(e[2], e[1]), p_sub4(e[1], e[3])};
+  const f32x4 v[4] = {plain_sub4(e[0], e[2]), plain_add4(e[1], e[2]), plain_sub4(e[2], e[1]), plain_sub4(e[1], e[3])};
 #pragma unroll
   for (int ex = 0; ex < 4; ++ex) {
     u32x2 t0, t1, t2;
-    split3_pack(v[ex], t0, t1, t2);
+    split3_quad(v[ex], t0, t1, t2);
     *reinterpret_cast<u32x2*>(la + (ex * 3 + 0) * X6P_T * X6K) = t0;
     *reinterpret_cast<u32x2*>(la + (ex * 3 + 1) * X6P_T * X6K) = t1;
     *reinterpret_cast<u32x2*>(la + (ex * 3 + 2) * X6P_T * X6K) = t2;
@@ -209,18 +143,14 @@ __global__ __launch_bounds__((2 * NB + 4) * 64) void wino2d_x6_kernel(X6P p) {
   using F = X6Fmt<FMT, NB>;
   constexpr int TERMS = F::TERMS;
   float sa = 1.f, inv_scale = 1.f;                     // fp16 format: operand scale and the factor that undoes both scales in the epilogue
-  if (FMT) { sa = h3_scale(adm_amax_read(p.amax_x)); inv_scale = 1.f / (sa * p.wscale); }
+  if (FMT) { sa = split_scale(adm_amax_read(p.amax_x)); inv_scale = 1.f / (sa * p.wscale); }
   extern __shared__ __attribute__((aligned(16))) unsigned short smem6[];
   unsigned short* As = smem6;                          // [X6_RA][4 ex][3 terms][X6P_T][X6K]
   unsigned short* Bs = smem6 + X6_RA * F::A_STAGE;     // [RB][4 ex][3 terms][X6N][X6K]
   const int tid = threadIdx.x, lane = tid & 63, hw_wid = tid >> 6;
   const bool producer = hw_wid >= F::CONS;
   const int wid = producer ? hw_wid - F::CONS : hw_wid;      // role-local wave index
-  int bid = blockIdx.x;
-  {   // XCD-aware bijective remap, m-fastest inside an n-tile (see conv_igemm.hip)
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = adm_xcd_remap(blockIdx.x, gridDim.x);
   const int tilesM = gridDim.x / p.tilesN;
   const int tm = bid % tilesM, tn = bid / tilesM;
   const int mt0 = tm * X6P_T, n0 = tn * F::NT;
@@ -304,13 +234,13 @@ __global__ __launch_bounds__((2 * NB + 4) * 64) void wino2d_x6_kernel(X6P p) {
       f32x4 e[4];
       if (set_ey[d] == 1) {                           // wave-uniform
 #pragma unroll
-        for (int j = 0; j < 4; ++j) e[j] = p_add4(dA[d][j], dB[d][j]);
+        for (int j = 0; j < 4; ++j) e[j] = plain_add4(dA[d][j], dB[d][j]);
       } else if (set_ey[d] == 2) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) e[j] = p_sub4(dB[d][j], dA[d][j]);
+        for (int j = 0; j < 4; ++j) e[j] = plain_sub4(dB[d][j], dA[d][j]);
       } else {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) e[j] = p_sub4(dA[d][j], dB[d][j]);
+        for (int j = 0; j < 4; ++j) e[j] = plain_sub4(dA[d][j], dB[d][j]);
       }
       if (X6_SHARE && !p.up) {                          // (uniform) every lane takes part in the moves
         f32x4 el, er;
@@ -341,7 +271,7 @@ __global__ __launch_bounds__((2 * NB + 4) * 64) void wino2d_x6_kernel(X6P p) {
           issue(d);                                   // stages past the end read nothing (all offsets out of range)
           __builtin_amdgcn_sched_barrier(0);
           if (tl) TL[2] = __builtin_readcyclecounter();
-          x6_barrier();
+          adm_lds_barrier();
           if (tl) TL[3] = __builtin_readcyclecounter();
         }
       }
@@ -551,56 +481,37 @@ __global__ __launch_bounds__((2 * NB + 4) * 64) void wino2d_x6_kernel(X6P p) {
   }
 }
 
-// Operand layout of the kernel: Wq6[ey][chunk][ex][term][n][16] -- the twelve 16-channel images a stage needs for its 64 rows are
-// 64 x 32 contiguous bytes each, so one LDS-DMA instruction reads one whole KB (plane-major rows would be 32-byte pieces of 32
-// different 128-byte lines per instruction).
+// Operand layout of the kernel: wino_image_offset (split_format.h), Wq6[ey][chunk][ex][term][n][16] -- the twelve 16-channel images a
+// stage needs for its 64 rows are 64 x 32 contiguous bytes each, so one LDS-DMA instruction reads one whole KB (plane-major rows
+// would be 32-byte pieces of 32 different 128-byte lines per instruction).
 __global__ void split3_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, int rows, int cols) {
   const long per = (long)rows * cols, total = per * 16;
-  const int chunks = cols >> 4;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int img = (int)(i / per);
     const long rc = i - img * per;
     const int n = (int)(rc / cols), c = (int)(rc - (long)n * cols);
-    const int ey = img >> 2, ex = img & 3;
-    const float a = src[i];
-    const unsigned u = __float_as_uint(a);
-    const float r = a - __uint_as_float(u & 0xFFFF0000u);
-    const unsigned m = __float_as_uint(r);
-    const float r2 = r - __uint_as_float(m & 0xFFFF0000u);
-    unsigned short* d = dst + ((((long)(ey * chunks + (c >> 4)) * 12 + ex * 3) * rows + n) << 4) + (c & 15);
-    const long term = (long)rows << 4;
-    d[0] = (unsigned short)(u >> 16);
-    d[term] = (unsigned short)(m >> 16);
-    d[2 * term] = (unsigned short)(__float_as_uint(r2) >> 16);
+    split3_store(src[i], dst + wino_image_offset(3, img >> 2, img & 3, rows, cols, n, c), split_term_stride(rows));
   }
 }
 
-// fp16 format: dst[ey][cols/16][ex][term(2)][rows][16] <- the two-term round-to-nearest split of scale * src (the sixteen Winograd
-// planes); *overflow is raised when a scaled value leaves the fp16 range (the caller then falls back to the bf16 format)
+// fp16 format: the two-term split of scale * src; *overflow is raised when a scaled value leaves the fp16 range (the caller then
+// falls back to the bf16 format)
 __global__ void split2_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, int rows, int cols, float scale,
                               int* __restrict__ overflow) {
   const long per = (long)rows * cols, total = per * 16;
-  const int chunks = cols >> 4;
   bool bad = false;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int img = (int)(i / per);
     const long rc = i - img * per;
     const int n = (int)(rc / cols), c = (int)(rc - (long)n * cols);
-    const int ey = img >> 2, ex = img & 3;
     const float a = src[i] * scale;
-    bad |= !(fabsf(a) < 65000.f);
-    const _Float16 h0 = (_Float16)a, h1 = (_Float16)(a - (float)h0);
-    unsigned short* d = dst + ((((long)(ey * chunks + (c >> 4)) * 8 + ex * 2) * rows + n) << 4) + (c & 15);
-    d[0] = __builtin_bit_cast(unsigned short, h0);
-    d[(long)rows << 4] = __builtin_bit_cast(unsigned short, h1);
+    bad |= split_f16_overflow(a);
+    split2_store(a, dst + wino_image_offset(2, img >> 2, img & 3, rows, cols, n, c), split_term_stride(rows));
   }
   if (bad && overflow) *overflow = 1;
 }
 
 }  // namespace
-
-int adm_splitk_reduce(const float* ws, const float* bias, const float* res, float* y, long M, int N, int ldy, int ldr, int splitk,
-                      hipStream_t stream);       // conv_igemm.hip
 
 // dst (bf16 bit patterns, 48 * rows * cols of them, layout [ey][cols/16][ex][term][rows][16]) <- the exact three-term split
 // a = a0 + a1 + a2 of the sixteen Winograd planes src[ey * 4 + ex][rows][cols] (f32); cols % 16 == 0

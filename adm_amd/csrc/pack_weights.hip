@@ -3,7 +3,7 @@
 // kernels.  Pure data movement over <= 11 MB per tensor; run once per optimiser step (or once per
 // model for sampling), so simplicity beats tuning here.
 #include "common.h"
-#include "../../include/adm_hip.h"
+#include "split_format.h"
 
 namespace {
 
@@ -138,59 +138,37 @@ __global__ __launch_bounds__(256) void pack_table_kernel(const long* __restrict_
     tile[r][c] = v;
   }
   __syncthreads();
-  // 1x1 layers on conv_gemm_x6.hip: the exact three-term bf16 split of both operands, [k/16][term][rows][16] (PT_G6F, PT_G6B)
+  // 1x1 layers on conv_gemm_x6.hip: both operands in both split formats of split_format.h, rows_image_offset: three bf16 terms
+  // (PT_G6F, PT_G6B) and two fp16 terms of scale * w (PT_G6FH, PT_G6BH)
   unsigned short* __restrict__ g6f = reinterpret_cast<unsigned short*>(t[PT_G6F]);
   unsigned short* __restrict__ g6b = reinterpret_cast<unsigned short*>(t[PT_G6B]);
-  // ... and their two-term fp16 images [k/16][term(2)][rows][16] of scale * w (conv_gemm_x6.hip FMT 1, adm_split2_rows_f16; PT_G6FH, PT_G6BH)
   unsigned short* __restrict__ g6fh = reinterpret_cast<unsigned short*>(t[PT_G6FH]);
   unsigned short* __restrict__ g6bh = reinterpret_cast<unsigned short*>(t[PT_G6BH]);
-  const float gscale = __uint_as_float((unsigned)t[PT_H3_SCALE]);
-  bool gbad = false;
-  auto split2_store = [&](unsigned short* dh, long termh, float v) {
-    const float a = v * gscale;
-    gbad |= !(fabsf(a) < 65000.f);
-    const _Float16 h0 = (_Float16)a, h1 = (_Float16)(a - (float)h0);
-    dh[0] = __builtin_bit_cast(unsigned short, h0);
-    dh[termh] = __builtin_bit_cast(unsigned short, h1);
-  };
-  auto split_store = [](unsigned short* d6, long term6, float v) {
-    const unsigned b0 = __float_as_uint(v);
-    const float r1 = v - __uint_as_float(b0 & 0xFFFF0000u);
-    const unsigned b1 = __float_as_uint(r1);
-    const float r2 = r1 - __uint_as_float(b1 & 0xFFFF0000u);
-    d6[0] = (unsigned short)(b0 >> 16);
-    d6[term6] = (unsigned short)(b1 >> 16);
-    d6[2 * term6] = (unsigned short)(__float_as_uint(r2) >> 16);
+  const float hscale = __uint_as_float((unsigned)t[PT_H3_SCALE]);
+  bool hbad = false;                               // a scaled weight left the fp16 range
+  auto store_rows = [&](unsigned short* d6, unsigned short* dh, int rows, int n, int k, float v) {
+    if (d6) split3_store(v, d6 + rows_image_offset(3, rows, n, k), split_term_stride(rows));
+    if (dh) {
+      hbad |= split_f16_overflow(v * hscale);
+      split2_store(v * hscale, dh + rows_image_offset(2, rows, n, k), split_term_stride(rows));
+    }
   };
   for (int e = threadIdx.x; e < n; e += 256) {     // forward operand [Co_pad][taps][Ci_pad]: ci fastest
     const int ci_l = e & 31, rest = e >> 5;
     const int tap = rest % taps, co_l = rest / taps;
     const float v = tile[co_l][ci_l * taps + tap];
     fwd[((long)(co0 + co_l) * taps + tap) * Ci_pad + ci0 + ci_l] = v;
-    if (g6f && taps == 1) {
-      const int k = ci0 + ci_l;
-      split_store(g6f + ((((long)(k >> 4) * 3) * Co_pad + co0 + co_l) << 4) + (k & 15), (long)Co_pad << 4, v);
-    }
-    if (g6fh && taps == 1) {
-      const int k = ci0 + ci_l;
-      split2_store(g6fh + ((((long)(k >> 4) * 2) * Co_pad + co0 + co_l) << 4) + (k & 15), (long)Co_pad << 4, v);
-    }
+    if (taps == 1) store_rows(g6f, g6fh, Co_pad, co0 + co_l, ci0 + ci_l, v);
   }
   for (int e = threadIdx.x; e < n; e += 256) {     // data-gradient operand [Ci_pad][taps flipped][Co_pad]: co fastest
     const int co_l = e & 31, rest = e >> 5;
     const int tapf = rest % taps, ci_l = rest / taps;
     const float v = tile[co_l][ci_l * taps + (taps - 1 - tapf)];
     bwd[((long)(ci0 + ci_l) * taps + tapf) * Co_pad + co0 + co_l] = v;
-    if (g6b && taps == 1) {
-      const int k = co0 + co_l;
-      split_store(g6b + ((((long)(k >> 4) * 3) * Ci_pad + ci0 + ci_l) << 4) + (k & 15), (long)Ci_pad << 4, v);
-    }
-    if (g6bh && taps == 1) {
-      const int k = co0 + co_l;
-      split2_store(g6bh + ((((long)(k >> 4) * 2) * Ci_pad + ci0 + ci_l) << 4) + (k & 15), (long)Ci_pad << 4, v);
-    }
+    if (taps == 1) store_rows(g6b, g6bh, Ci_pad, ci0 + ci_l, co0 + co_l, v);
   }
-  if (gbad && t[PT_H3_FLAG]) *reinterpret_cast<int*>(t[PT_H3_FLAG]) = 1;      // a scaled 1x1 weight left the fp16 range: the host falls back to the bf16 format
+  int* __restrict__ hflag = reinterpret_cast<int*>(t[PT_H3_FLAG]);
+  if (hbad && hflag) *hflag = 1;                   // the host falls back to the bf16 format
   if (taps != 9) return;
   // Winograd F(2,3) operands (conv_wino.hip): G g per filter row, u = (g0, (g0+g1+g2)/2, (g0-g1+g2)/2, g2)
   if (wf) {                                        // wf[xi][co][ky][ci]: ci fastest
@@ -208,17 +186,14 @@ __global__ __launch_bounds__(256) void pack_table_kernel(const long* __restrict_
     }
   }
   // 2-D Winograd F(2x2, 3x3) operands (conv_wino2d.hip): U = G g G^T, plane ey * 4 + ex
-  // ... and their exact three-term bf16 splits in adm_split3_bf16's K-chunk-tiled layout for conv_wino2d_x6.hip (PT_W2F6, PT_W2B6; 0 when unused)
+  // ... and both split formats of them (split_format.h, wino_image_offset) for conv_wino2d_x6.hip: three bf16 terms (PT_W2F6, PT_W2B6)
+  // and two fp16 terms of scale * U (PT_W2FH, PT_W2BH); 0 when unused
   float* __restrict__ wf2 = reinterpret_cast<float*>(t[PT_W2F]);
   float* __restrict__ wb2 = reinterpret_cast<float*>(t[PT_W2B]);
   unsigned short* __restrict__ wf6 = reinterpret_cast<unsigned short*>(t[PT_W2F6]);
   unsigned short* __restrict__ wb6 = reinterpret_cast<unsigned short*>(t[PT_W2B6]);
-  // ... and their two-term fp16 images [ey][cols/16][ex][term(2)][rows][16] of scale * U (conv_wino2d_x6.hip, X6Fmt<1>)
   unsigned short* __restrict__ wfh = reinterpret_cast<unsigned short*>(t[PT_W2FH]);
   unsigned short* __restrict__ wbh = reinterpret_cast<unsigned short*>(t[PT_W2BH]);
-  const float hscale = __uint_as_float((unsigned)t[PT_H3_SCALE]);
-  int* __restrict__ hflag = reinterpret_cast<int*>(t[PT_H3_FLAG]);
-  bool hbad = false;
   if (wf2 || wb2 || wf6 || wb6 || wfh || wbh) {
     const long plane2 = (long)Co_pad * Ci_pad;
     for (int e = threadIdx.x; e < 32 * 32; e += 256) {
@@ -238,7 +213,10 @@ __global__ __launch_bounds__(256) void pack_table_kernel(const long* __restrict_
           const float g0 = which ? g[ra * 3 + 2] : g[ra * 3], g1 = g[ra * 3 + 1], g2 = which ? g[ra * 3] : g[ra * 3 + 2];
           tr[a][0] = g0; tr[a][1] = (g0 + g1 + g2) * 0.5f; tr[a][2] = (g0 - g1 + g2) * 0.5f; tr[a][3] = g2;
         }
-        const long o = which ? (long)(ci0 + ci_l) * Co_pad + co0 + co_l : (long)(co0 + co_l) * Ci_pad + ci0 + ci_l;
+        // (rows, cols) = (Co_pad, Ci_pad) forward, (Ci_pad, Co_pad) data gradient
+        const int rows = which ? Ci_pad : Co_pad, cols = which ? Co_pad : Ci_pad;
+        const int n = which ? ci0 + ci_l : co0 + co_l, c = which ? co0 + co_l : ci0 + ci_l;
+        const long o = (long)n * cols + c;
 #pragma unroll
         for (int ex = 0; ex < 4; ++ex) {
           const float c0 = tr[0][ex], c1 = tr[1][ex], c2 = tr[2][ex];
@@ -246,29 +224,10 @@ __global__ __launch_bounds__(256) void pack_table_kernel(const long* __restrict_
 #pragma unroll
           for (int ey = 0; ey < 4; ++ey) {
             if (dst) dst[(long)(ey * 4 + ex) * plane2 + o] = u[ey];
-            if (dst6) {                            // a = a0 + a1 + a2 exactly (truncation splits, as adm_split3_bf16)
-              const unsigned b0 = __float_as_uint(u[ey]);
-              const float r1 = u[ey] - __uint_as_float(b0 & 0xFFFF0000u);
-              const unsigned b1 = __float_as_uint(r1);
-              const float r2 = r1 - __uint_as_float(b1 & 0xFFFF0000u);
-              // [ey][cols/16][ex][term][rows][16] with (rows, cols) = (Co_pad, Ci_pad) forward, (Ci_pad, Co_pad) data gradient
-              const int rows6 = which ? Ci_pad : Co_pad, cols6 = which ? Co_pad : Ci_pad;
-              const int n6 = which ? ci0 + ci_l : co0 + co_l, c6 = which ? co0 + co_l : ci0 + ci_l;
-              unsigned short* d6 = dst6 + ((((long)(ey * (cols6 >> 4) + (c6 >> 4)) * 12 + ex * 3) * rows6 + n6) << 4) + (c6 & 15);
-              const long term6 = (long)rows6 << 4;
-              d6[0] = (unsigned short)(b0 >> 16);
-              d6[term6] = (unsigned short)(b1 >> 16);
-              d6[2 * term6] = (unsigned short)(__float_as_uint(r2) >> 16);
-            }
-            if (dsth) {                            // scale * u = h0 + h1, round to nearest (as adm_split2_f16)
-              const float a = u[ey] * hscale;
-              hbad |= !(fabsf(a) < 65000.f);
-              const _Float16 h0 = (_Float16)a, h1 = (_Float16)(a - (float)h0);
-              const int rowsh = which ? Ci_pad : Co_pad, colsh = which ? Co_pad : Ci_pad;
-              const int nh = which ? ci0 + ci_l : co0 + co_l, ch = which ? co0 + co_l : ci0 + ci_l;
-              unsigned short* dh = dsth + ((((long)(ey * (colsh >> 4) + (ch >> 4)) * 8 + ex * 2) * rowsh + nh) << 4) + (ch & 15);
-              dh[0] = __builtin_bit_cast(unsigned short, h0);
-              dh[(long)rowsh << 4] = __builtin_bit_cast(unsigned short, h1);
+            if (dst6) split3_store(u[ey], dst6 + wino_image_offset(3, ey, ex, rows, cols, n, c), split_term_stride(rows));
+            if (dsth) {
+              hbad |= split_f16_overflow(u[ey] * hscale);
+              split2_store(u[ey] * hscale, dsth + wino_image_offset(2, ey, ex, rows, cols, n, c), split_term_stride(rows));
             }
           }
         }

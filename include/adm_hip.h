@@ -253,7 +253,7 @@ int adm_pack_weight(const float* w, float* wp_fwd, float* wp_bwd, int Co, int Ci
  *   14 w2f6, 15 w2b6   their three-term bf16 splits, as adm_split3_bf16
  *   16 g6f, 17 g6b  three-term bf16 splits of the 1x1 operands fwd / bwd, as adm_split3_rows
  *   18 w2fh, 19 w2bh   two-term fp16 images of scale * (2-D Winograd planes), as adm_split2_f16
- *   20 h3_scale     that scale: the bits of a float in the low 32 bits
+ *   20 h3_scale     that scale (a power of two; the formats: adm_amd/csrc/split_format.h): the bits of a float in the low 32 bits
  *   21 h3_flag      int* raised to 1 when a scaled weight of columns 18, 19, 22, 23 leaves the fp16 range; 0 = none
  *   22 g6fh, 23 g6bh   two-term fp16 images of scale * (1x1 operands), as adm_split2_rows_f16
  * Columns 10-19, 22 and 23 are destinations and may be 0 (not derived); 10-15, 18 and 19 are read for 3x3 layers only, 16, 17, 22 and 23

@@ -104,7 +104,7 @@ def test_errors_are_relative_to_mag():
 # ------------------------------------------------------------------------------------------------ the bars have teeth
 def _h3_drop_low_term(t, bound):
     """The fp16 split of the kernels with its LOW term dropped: s a -> fp16(s a) / s, s = the power of two with s * bound <= 16000
-    (h3_scale of conv_wino2d_x6.hip)."""
+    (split_scale of csrc/split_format.h)."""
     s = 2.0 ** math.floor(math.log2(16000.0 / bound))
     return (t * s).to(torch.float16).to(_f64) / s
 

@@ -1,7 +1,7 @@
 """GPU: the fp16 split format where its bounds can fail.
 
 Every fp16-format kernel scales an f32 operand by a power of two taken from a BOUND (a device vector >= max |operand|) and stores the
-scaled value as two fp16 terms (h3_scale, conv_wino2d_x6.hip: s * bound <= 16000, so that the Winograd transforms' sums of four stay
+scaled value as two fp16 terms (split_scale, csrc/split_format.h: s * bound <= 16000, so that the Winograd transforms' sums of four stay
 below 65504).  These tests put operands at the edge of that claim (worst-case sign patterns at an exact bound, bounds where the
 scale changes exponent, zeros, magnitudes far from 1) against fp64, and check the bookkeeping that carries the bounds: a gradient
 summed in place after its bound was registered, every consumer under ADM_AMAX_CHECK semantics on each model family, weights that do

@@ -121,9 +121,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   };
   auto store_ex = [&](const f32x4 (&e)[4], int ex, unsigned short* dst) {   // column ex of B^T along x, split, three ds_write_b64
     if (X6_ABL & 2) return;
-    const f32x4 v = ex == 0 ? p_sub4(e[0], e[2]) : ex == 1 ? p_add4(e[1], e[2]) : ex == 2 ? p_sub4(e[2], e[1]) : p_sub4(e[1], e[3]);
+    const f32x4 v = ex == 0 ? plain_sub4(e[0], e[2]) : ex == 1 ? plain_add4(e[1], e[2]) : ex == 2 ? plain_sub4(e[2], e[1]) : plain_sub4(e[1], e[3]);
     u32x2 t0, t1, t2;
-    split3_pack(v, t0, t1, t2);
+    split3_quad(v, t0, t1, t2);
     *reinterpret_cast<u32x2*>(dst + (ex * 3 + 0) * X6P_T * X6K) = t0;
     *reinterpret_cast<u32x2*>(dst + (ex * 3 + 1) * X6P_T * X6K) = t1;
     *reinterpret_cast<u32x2*>(dst + (ex * 3 + 2) * X6P_T * X6K) = t2;
