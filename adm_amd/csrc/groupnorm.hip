@@ -604,6 +604,9 @@ inline GnPlan gn_fused_plan(int HW, int C, int G, bool backward) {
   return best;
 }
 
+// the register-resident template (rows held per thread) that runs a plan of `rows` rows per thread
+inline int gn_fused_template(int rows) { return rows <= 2 ? 2 : rows <= 8 ? 8 : 14; }
+
 inline bool gn_shape_ok(int B, int HW, int C, int G) {
   return B > 0 && HW > 0 && C > 0 && G > 0 && (C % 4) == 0 && (C % G) == 0 && C / 4 <= 1024;
 }
@@ -613,6 +616,10 @@ inline int gn_threads(int C) { return (C / 4) * gn_rows_par(C); }
 
 int g_gn_fused = 1;       // 0: always the multi-pass kernels (diagnostic; tools only)
 extern "C" int adm_gn_fused(int on) { const int old = g_gn_fused; if (on == 0 || on == 1) g_gn_fused = on; return old; }
+// the plan both directions launch under the current switch (Cc = 0: the multi-pass kernels)
+static GnPlan gn_plan_now(int HW, int C, int G, bool backward) {
+  return g_gn_fused ? gn_fused_plan(HW, C, G, backward) : GnPlan{0, 0, 0};
+}
 
 extern "C" int adm_gn_splits(int HW, int C) {
   (void)C;
@@ -623,6 +630,21 @@ extern "C" int adm_gn_splits(int HW, int C) {
   if (s > 16) s = HW / 256;
   if (s > 1024) s = 1024;
   return s;
+}
+
+// Host query of the launch plan (no launch): out[0..4] = {Cc, threads, rows, MAXR, S}.  One-launch path: slab width, workgroup size,
+// rows per thread, the register-resident template taken, S = 1.  Multi-pass path: Cc = 0, threads per workgroup, rows per split,
+// MAXR = 0, S = adm_gn_splits(HW, C).
+extern "C" int adm_gn_plan(int HW, int C, int G, int* out) {
+  if (!out || !gn_shape_ok(1, HW, C, G)) return ADM_EINVAL;
+  const GnPlan pl = gn_plan_now(HW, C, G, false);
+  if (pl.Cc) {
+    out[0] = pl.Cc; out[1] = pl.threads; out[2] = pl.rows; out[3] = gn_fused_template(pl.rows); out[4] = 1;
+  } else {
+    const int S = adm_gn_splits(HW, C);
+    out[0] = 0; out[1] = gn_threads(C); out[2] = adm_cdiv(HW, S); out[3] = 0; out[4] = S;
+  }
+  return ADM_OK;
 }
 
 extern "C" int adm_gn_stats(const float* x, float* stats, double* ws, int B, int HW, int C, int G, float eps,
@@ -687,7 +709,7 @@ static int gn_fwd_impl(const float* x, float* stats, double* ws, const float* ga
                        int out_bf16, hipStream_t stream, float* amax) {
   if (!x || !stats || !ws || !gamma || !beta || !y || !gn_shape_ok(B, HW, C, G) || drop_p < 0.f || drop_p >= 1.f)
     return ADM_EINVAL;
-  const GnPlan pl = g_gn_fused ? gn_fused_plan(HW, C, G, false) : GnPlan{0, 0, 0};
+  const GnPlan pl = gn_plan_now(HW, C, G, false);
   if (pl.Cc == 0) {
     int rc = adm_gn_stats(x, stats, ws, B, HW, C, G, eps, stream);
     if (rc != ADM_OK) return rc;
@@ -699,9 +721,11 @@ static int gn_fwd_impl(const float* x, float* stats, double* ws, const float* ga
 #define GN_FWD(MAXR, THREADS)                                                                                                 \
   hipLaunchKernelGGL((gn_fused_fwd_kernel<MAXR, THREADS>), grid, block, smem, stream, x, gamma, beta, ss, ss_bstride, y, stats, \
                      HW, C, G, Cc, eps, silu, drop_p, seed, out_bf16, amax)
-  if (pl.rows <= 2) GN_FWD(2, 256);
-  else if (pl.rows <= 8) GN_FWD(8, 256);
-  else GN_FWD(14, 256);
+  switch (gn_fused_template(pl.rows)) {
+    case 2: GN_FWD(2, 256); break;
+    case 8: GN_FWD(8, 256); break;
+    default: GN_FWD(14, 256);
+  }
 #undef GN_FWD
   ADM_CHECK_LAUNCH();
   return ADM_OK;
@@ -731,7 +755,7 @@ static int gn_bwd_add_impl(const float* x, const float* dy, const float* stats, 
   float* part = red;
   float* tot = part + (long)B * S * C * 2;
   float* gm = tot + (long)B * C * 2;
-  const GnPlan pl = g_gn_fused ? gn_fused_plan(HW, C, G, true) : GnPlan{0, 0, 0};
+  const GnPlan pl = gn_plan_now(HW, C, G, true);
   if (pl.Cc) {       // one launch (+ the parameter-gradient reduction over the batch)
     const int Cc = pl.Cc, Rf = pl.threads / (Cc / 4), Gc = Cc / (C / G);
     const size_t smf = ((size_t)Rf * Cc * 2 + (size_t)Cc * 2 + (size_t)Gc * 2) * sizeof(float);
@@ -739,9 +763,11 @@ static int gn_bwd_add_impl(const float* x, const float* dy, const float* stats, 
 #define GN_BWD(MAXR, THREADS)                                                                                                   \
   hipLaunchKernelGGL((gn_fused_bwd_kernel<MAXR, THREADS>), grid, block, smf, stream, x, dy, stats, gamma, beta, ss, ss_bstride, \
                      addend, dx, tot, dss, HW, C, G, Cc, silu, drop_p, seed, amax)
-    if (pl.rows <= 2) GN_BWD(2, 256);
-    else if (pl.rows <= 8) GN_BWD(8, 256);
-    else GN_BWD(14, 256);
+    switch (gn_fused_template(pl.rows)) {
+      case 2: GN_BWD(2, 256); break;
+      case 8: GN_BWD(8, 256); break;
+      default: GN_BWD(14, 256);
+    }
 #undef GN_BWD
     if (dgamma)
       hipLaunchKernelGGL(gn_bwd_param_kernel, dim3(adm_cdiv(C, 32)), dim3(256), 0, stream, tot, ss, ss_bstride, dgamma,

@@ -286,6 +286,11 @@ int adm_colsum(const float* a, float* out, int M, int N, int ld, int accumulate,
 /* 1 (default): one-launch register-resident GroupNorm where a plan exists; 0: always the multi-pass kernels.  Returns the old value. */
 int adm_gn_fused(int on);
 int adm_gn_splits(int HW, int C);
+/* The launch plan of adm_gn_fwd / adm_gn_bwd at (HW, C, G) under the current adm_gn_fused switch, no launch:
+ * out[0..4] = {Cc, threads, rows, MAXR, S}.  One-launch path: slab width in channels, workgroup size, rows per thread, the
+ * register-resident template taken (2 / 8 / 14), S = 1.  Multi-pass path: Cc = 0, threads per workgroup, rows per split, MAXR = 0,
+ * S = adm_gn_splits(HW, C).  ADM_EINVAL for a shape the kernels refuse. */
+int adm_gn_plan(int HW, int C, int G, int* out);
 int adm_gn_stats(const float* x, float* stats, double* ws, int B, int HW, int C, int G, float eps, hipStream_t stream);
 /* y = act( (xhat*gamma + beta) * (1 + scale[b,c]) + shift[b,c] ) * dropmask
  * xhat = (x - mean) * rstd.  ss = [.., 2C] rows of (scale | shift) or NULL (uncond_unet.py:191-196);

@@ -1,4 +1,4 @@
-"""fp64 references of the conv and attention operators, for the accuracy tests (a plain helper like parity.py, not a conftest).
+"""fp64 references of the conv, attention and GroupNorm operators, for the accuracy tests (a plain helper like parity.py, not a conftest).
 
 Layouts are the kernels': activations NHWC [B, H, W, C], weights OIHW [Co, Ci, k, k] (or [Co, Ci] for a Linear), attention qkv
 [B, L, heads * 192] with each head's 192 channels packed as (q[64] | k[64] | v[64]) and its output [B, L, heads * 64].
@@ -95,6 +95,60 @@ def attention(qkv, heads, dout=None):
         grads.append(torch.stack([dq, dk, dv], dim=3).permute(0, 2, 1, 3, 4).reshape(shp))     # [B][L][heads][3][64]
     res["dqkv"] = tuple(grads)
     return res
+
+
+def group_norm(x, gamma, beta, ss, *, groups, eps, silu, keep=None, addend=None, dy=None):
+    """{"y": (ref, mag)} and, given dy, "dx", "dgamma", "dbeta" and (with ss) "dss" of ops.group_norm_act / group_norm_act_fork:
+
+        xhat = (x - mean_g) rstd_g,  z = xhat gamma + beta,  u = (1 + s) z + t,  y = act(u) keep
+
+    x NHWC [B, H, W, C]; group g = channels [g cpg, (g + 1) cpg) of one image, biased variance; ss = [B, 2C] or [1, 2C] rows of
+    (s | t) or None; keep = the dropout mask already divided by 1 - p; addend = the fork's residual gradient, added to dx.  Written
+    from the definition in float64 on x's device; the gradients are autograd's on that graph.  mag: |y|; for the parameter gradients
+    the same sums over |summands|; for dx (= rstd (gamma' du - mean_g(gamma' du) - xhat mean_g(gamma' du xhat)) + addend, gamma' =
+    gamma (1 + s), du = dy keep act'(u)):  rstd (|gamma' du| + mean_g |gamma' du| + |xhat| mean_g |gamma' du xhat|) + |addend|."""
+    need = dy is not None
+    x = x.detach().to(_f64).requires_grad_(need)
+    gamma, beta = (t.detach().to(device=x.device, dtype=_f64).requires_grad_(need) for t in (gamma, beta))
+    B, H, W, C = x.shape
+    cpg = C // groups
+    xg = x.reshape(B, H * W, groups, cpg)
+    mean = xg.mean(dim=(1, 3), keepdim=True)
+    var = (xg - mean).square().mean(dim=(1, 3), keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    xhat = ((xg - mean) * rstd).reshape(B, H, W, C)
+    z = xhat * gamma + beta
+    u, sc1 = z, None
+    if ss is not None:
+        ss = ss.detach().to(device=x.device, dtype=_f64).requires_grad_(need)
+        sc1 = 1.0 + ss[:, :C].reshape(-1, 1, 1, C)
+        u = sc1 * z + ss[:, C:].reshape(-1, 1, 1, C)
+    y = u * torch.sigmoid(u) if silu else u
+    if keep is not None:
+        y = y * keep.to(device=x.device, dtype=_f64)
+    out = {"y": (y.detach(), y.detach().abs())}
+    if not need:
+        return out
+    dy = dy.to(device=x.device, dtype=_f64)
+    wrt = [x, gamma, beta, u] + ([ss] if ss is not None else [])
+    g = torch.autograd.grad(y, wrt, dy)
+    dx, du = g[0], g[3]                                        # du = dy keep act'(u)
+    zd, xh = z.detach(), xhat.detach()
+    dz = du if sc1 is None else du * sc1.detach()              # (1 + s) du
+    gdu = (dz * gamma.detach()).abs()                          # |gamma' du|
+    gmean = lambda t: t.reshape(B, H * W, groups, cpg).mean(dim=(1, 3), keepdim=True).expand(B, H * W, groups, cpg).reshape(B, H, W, C)
+    rs = rstd.detach().expand(B, H * W, groups, cpg).reshape(B, H, W, C)
+    dx_mag = rs * (gdu + gmean(gdu) + xh.abs() * gmean(gdu * xh.abs()))
+    if addend is not None:
+        a = addend.to(device=x.device, dtype=_f64)
+        dx, dx_mag = dx + a, dx_mag + a.abs()
+    out["dx"] = (dx, dx_mag)
+    out["dgamma"] = (g[1], (dz * xh).abs().sum(dim=(0, 1, 2)))
+    out["dbeta"] = (g[2], dz.abs().sum(dim=(0, 1, 2)))
+    if ss is not None:
+        m = torch.cat([(du * zd).abs().sum(dim=(1, 2)), du.abs().sum(dim=(1, 2))], dim=1)        # [B, 2C]
+        out["dss"] = (g[4], m if ss.shape[0] == B else m.sum(dim=0, keepdim=True))
+    return out
 
 
 def errors(got, ref, mag):

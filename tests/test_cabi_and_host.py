@@ -1,6 +1,7 @@
 """CPU-only: the C-ABI library loads and exports every symbol include/adm_hip.h declares; host logic
 (module/state_dict layout, schedules, dotted-path aliases) matches the oracle and golden vectors.
 No compute call is made here (no GPU)."""
+import ctypes
 import os
 import re
 
@@ -27,6 +28,18 @@ def test_library_exports_every_declared_symbol():
     assert sorted(hip.EXPORTS) == declared, set(hip.EXPORTS) ^ set(declared)
     assert lib.adm_version() >= 1
     assert lib.adm_gn_splits(1024, 192) == 16 and lib.adm_gn_splits(16, 384) == 1
+    plan = (ctypes.c_int * 5)()                  # {Cc, threads, rows, MAXR, S} under the current adm_gn_fused switch
+    for (HW, C, G), want in {(16, 192, 32): (96, 240, 2, 2, 1), (256, 32, 8): (32, 256, 8, 8, 1), (140, 192, 32): (96, 240, 14, 14, 1),
+                             (256, 36, 6): (36, 252, 10, 14, 1), (256, 192, 32): (48, 252, 13, 14, 1),
+                             (256, 520, 2): (0, 130, 64, 0, 4), (289, 32, 8): (0, 256, 73, 0, 4), (315, 64, 16): (0, 256, 79, 0, 4), (1056, 128, 32): (0, 256, 66, 0, 16),
+                             (1089, 1280, 32): (0, 320, 273, 0, 4), (4356, 32, 8): (0, 256, 257, 0, 17)}.items():
+        assert lib.adm_gn_plan(HW, C, G, plan) == 0 and tuple(plan) == want, (HW, C, G, tuple(plan))
+    assert lib.adm_gn_fused(0) == 1
+    try:
+        assert lib.adm_gn_plan(16, 192, 32, plan) == 0 and tuple(plan) == (0, 240, 16, 0, 1)
+    finally:
+        lib.adm_gn_fused(1)
+    assert lib.adm_gn_plan(16, 30, 5, plan) == -22 and lib.adm_gn_plan(16, 32, 5, plan) == -22 and lib.adm_gn_plan(16, 32, 8, None) == -22
     # the ctypes argument table has exactly one entry per parameter of the C declaration
     for m in re.finditer(r"^(?:int|long)\s+(adm_\w+)\s*\(([^;]*?)\)\s*;", header, flags=re.M | re.S):
         name, params = m.group(1), m.group(2).strip()

@@ -9,7 +9,9 @@ import torch.nn.functional as F
 from oracle import fill
 
 import fp64ref
+import gn_cases
 from parity import close
+from test_hip_accuracy import BAR_A
 
 _f64 = torch.float64
 
@@ -90,6 +92,45 @@ def test_attention_reference_matches_autograd(heads, L):
     # mag bounds |ref| elementwise (it is the same sums over |terms|)
     assert bool((got["out"][1] >= got["out"][0].abs() - 1e-12).all())
     assert bool((got["dqkv"][1] >= got["dqkv"][0].abs() - 1e-12).all())
+
+
+@pytest.mark.parametrize("row", [gn_cases.GRID[i] for i in (5, 6, 12)], ids=gn_cases.row_id)
+def test_group_norm_reference_matches_autograd(row):
+    """fp64ref.group_norm (written from the definition) against torch.autograd on F.group_norm(double) with the same scale/shift,
+    SiLU, mask and residual gradient, to 1e-12; without scale/shift and SiLU too; every mag bounds |ref|."""
+    H, W, C, _, eps, B, _ = row
+    G = gn_cases.groups_of(row)
+    c = {k: v.double() for k, v in gn_cases.make_case(row, "plain").items()}
+    keep = (fill.hash_tensor((B, H, W, C), "gn.keep", 1.0, _f64) > -0.8).double() / 0.9
+    for silu, ss, kp, add in ((True, c["ss"], keep, c["addend"]), (False, None, None, None), (True, c["ss"][:1], None, None)):
+        got = fp64ref.group_norm(c["x"], c["gamma"], c["beta"], ss, groups=G, eps=eps, silu=silu, keep=kp, addend=add, dy=c["dy"])
+        want = gn_cases.torch_composition(c["x"], c["gamma"], c["beta"], ss, groups=G, eps=eps, silu=silu, keep=kp, addend=add,
+                                          dy=c["dy"])
+        assert set(got) == set(want)
+        for n, t in want.items():
+            ref, mag = got[n]
+            assert ref.shape == t.shape and mag.shape == t.shape, (n, ref.shape, mag.shape, t.shape)
+            assert float((ref - t).abs().max()) <= 1e-12 * max(1.0, float(t.abs().max())), (n, silu)
+            assert bool((mag >= ref.abs() * (1 - 1e-12)).all()), n
+    y_only = fp64ref.group_norm(c["x"], c["gamma"], c["beta"], None, groups=G, eps=eps, silu=True)
+    assert set(y_only) == {"y"}
+
+
+@pytest.mark.parametrize("row", gn_cases.GRID, ids=gn_cases.row_id)
+def test_group_norm_bar_leaves_room_for_fp32(row):
+    """The bar of tests/test_hip_groupnorm.py (BAR_A on every output) against what plain fp32 arithmetic does: the fp32 torch
+    composition on the CPU stays below a quarter of it at every grid shape and data kind (errors printed)."""
+    H, W, C, _, eps, B, _ = row
+    G = gn_cases.groups_of(row)
+    for kind in gn_cases.KINDS:
+        c = gn_cases.make_case(row, kind)
+        kw = dict(groups=G, eps=eps, silu=True, addend=c["addend"], dy=c["dy"])
+        ref = fp64ref.group_norm(c["x"], c["gamma"], c["beta"], c["ss"], **kw)
+        got = gn_cases.torch_composition(c["x"], c["gamma"], c["beta"], c["ss"], **kw)
+        e = {n: fp64ref.errors(got[n], *ref[n])[0] for n in ref}
+        print(f"{gn_cases.row_id(row)} {kind}: " + " ".join(f"{n} {v:.2e}" for n, v in e.items()))
+        for n, v in e.items():
+            assert v <= BAR_A / 4, (kind, n, v)
 
 
 def test_errors_are_relative_to_mag():
