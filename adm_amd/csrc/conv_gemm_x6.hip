@@ -15,6 +15,7 @@
 // Replaces F.conv2d (1x1) of Conv2d.forward and its data gradient (/root/reference/unet/uncond_unet.py:98-110).
 #include "common.h"
 #include "split_format.h"
+#include <type_traits>
 
 namespace {
 
@@ -213,35 +214,76 @@ __global__ __launch_bounds__(512) void gemm_x6_kernel(G6P p) {
   }
 
   // ---- epilogue.  C/D layout col = lane & 31 (cout), row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) (pixel).  Branch-free: residual
-  // loads and stores through buffer descriptors, masked lanes at an out-of-range offset (no residual = an empty descriptor).
+  // loads and stores through buffer descriptors, masked lanes at an out-of-range offset.
   const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.ybytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res), 0, p.res ? p.rbytes : 0, 0x00020000);
+  // One batch of 64 residual loads (into the registers the dead MFMA accumulators leave free), the 64 values, one batch of 64
+  // stores: a buffer load is never moved above an earlier buffer store and vmcnt counts stores too, so alternating groups of loads
+  // and stores are serial memory round trips.  Without a residual there is nothing to load and nothing to wait for: a second body,
+  // chosen by a workgroup-uniform branch.
   float am = 0.f;
+  auto epilogue = [&](auto res_tag) {
+    constexpr bool RES = decltype(res_tag)::value;
+    float bv[2];
 #pragma unroll
-  for (int ni = 0; ni < 2; ++ni) {
-    const int n = n0 + wn * 64 + ni * 32 + lr;
-    const float bv = (p.bias && n < p.N) ? p.bias[n] : 0.f;
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-      const int mb = m0 + wm * 64 + mi * 32 + 4 * lh;
-      float rv[16];
-      unsigned oy[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = mb + (r & 3) + 8 * (r >> 2);
-        const bool ok = m < p.M && n < p.N;
-        oy[r] = ok ? ((unsigned)m * (unsigned)p.ldy + (unsigned)n) * 4u : OOB;
-        const unsigned orr = ok ? ((unsigned)m * (unsigned)p.ldr + (unsigned)n) * 4u : OOB;
-        rv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_r, (int)orr, 0, 0));
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float v = (FMT ? tot[mi][ni][r] * inv_scale : tot[mi][ni][r]) + bv + rv[r];
-        if (oy[r] != OOB) am = fmaxf(am, fabsf(v));
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs_y, (int)oy[r], 0, 0);
-      }
+    for (int ni = 0; ni < 2; ++ni) {
+      const int n = n0 + wn * 64 + ni * 32 + lr;
+      bv[ni] = (p.bias && n < p.N) ? p.bias[n] : 0.f;
     }
-  }
+    float v[2][2][16];                // [ni][mi][r]
+    // offset = row part (m ldy, one register per pixel row, out of range for m >= M) + column part, raised out of range for n >= N
+    unsigned n4[2], cmask[2], oy[2][16];
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+      const int n = n0 + wn * 64 + ni * 32 + lr;
+      n4[ni] = (unsigned)n * 4u;
+      cmask[ni] = n < p.N ? 0u : OOB;
+    }
+    if (RES) {
+      unsigned orr[2][16];
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int m = m0 + wm * 64 + mi * 32 + 4 * lh + (r & 3) + 8 * (r >> 2);
+          orr[mi][r] = m < p.M ? (unsigned)m * (unsigned)p.ldr * 4u : OOB;
+        }
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            v[ni][mi][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_r, (int)max(orr[mi][r] + n4[ni], cmask[ni]), 0, 0));
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = m0 + wm * 64 + mi * 32 + 4 * lh + (r & 3) + 8 * (r >> 2);
+        oy[mi][r] = m < p.M ? (unsigned)m * (unsigned)p.ldy * 4u : OOB;
+      }
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {      // (no residual: "+ 0", what a load through an empty descriptor gives; it turns a -0 into +0)
+          v[ni][mi][r] = (FMT ? tot[mi][ni][r] * inv_scale : tot[mi][ni][r]) + bv[ni] + (RES ? v[ni][mi][r] : 0.f);
+          am = fmaxf(am, (int)(oy[mi][r] | cmask[ni]) >= 0 ? fabsf(v[ni][mi][r]) : 0.f);      // (valid elements only; am >= 0)
+        }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[ni][mi][r]), rs_y, (int)max(oy[mi][r] + n4[ni], cmask[ni]), 0, 0);
+  };
+  if (p.res) epilogue(std::true_type{});             // (workgroup-uniform)
+  else epilogue(std::false_type{});
   adm_amax_commit(am, p.amax_y);      // (all four consumer waves arrive here with all lanes)
 }
 

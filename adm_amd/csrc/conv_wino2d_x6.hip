@@ -431,35 +431,69 @@ __global__ __launch_bounds__((2 * NB + 4) * 64) void wino2d_x6_kernel(X6P p) {
   const float bv = (p.bias && n < p.N) ? p.bias[n] : 0.f;
   const int tb = mt0 + wm * 32 + 4 * lh;
   if (p.ybytes > 0) {
-    // branch-free: residual loads and output stores through buffer descriptors, masked lanes at an out-of-range offset (a missing
-    // residual = an empty descriptor: reads return 0).  With `if`s per element the compiler serialises the 64 residual loads of a
-    // thread, each waiting for the previous one -- tens of microseconds per workgroup.
+    // branch-free: residual loads and output stores through buffer descriptors, masked lanes at an out-of-range offset.  With `if`s
+    // per element the compiler serialises the 64 residual loads of a thread, each waiting for the previous one -- tens of
+    // microseconds per workgroup.
     const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.ybytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res), 0, p.res ? p.rbytes : 0, 0x00020000);
+    // One batch of loads, then one batch of stores.  A buffer load is never moved above an earlier buffer store and vmcnt counts
+    // stores as well as loads, so a load / wait / store round per accumulator register is sixteen serial memory round trips per
+    // wave.  Here: the offsets of pixel (b, 2ty, 2xp) of all sixteen registers (one VGPR each for y and the residual; the 2 x 2
+    // outputs of a tile are reached through four uniform scalar offsets), all 64 residual loads into the registers the dead MFMA
+    // accumulators leave free, the 64 values, all 64 stores with no wait between them.  Without a residual (the split-K partials
+    // too) there is nothing to load and nothing to wait for: a second body, chosen by a workgroup-uniform branch.
+    unsigned so_y[2][2], so_r[2][2];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int t = tb + (r & 3) + 8 * (r >> 2);
-      const bool ok = t < p.Mt && n < p.N;
-      const int xp = t % p.Wh;
-      const int u = t / p.Wh;                      // = b * Hh + ty
-      const unsigned px0 = ((unsigned)u * 2u) * (unsigned)p.W + 2u * (unsigned)xp;     // pixel (b, 2ty, 2xp): (b*H + 2ty) * W + 2xp
-      unsigned oy[2][2], orr[2][2];
-      float rv[2][2];
+    for (int a = 0; a < 2; ++a)
 #pragma unroll
-      for (int a = 0; a < 2; ++a)
+      for (int c = 0; c < 2; ++c) {
+        so_y[a][c] = ((unsigned)a * (unsigned)p.W + (unsigned)c) * (unsigned)p.ldy * 4u;
+        so_r[a][c] = ((unsigned)a * (unsigned)p.W + (unsigned)c) * (unsigned)p.ldr * 4u;
+      }
+    auto epilogue = [&](auto res_tag) {
+      constexpr bool RES = decltype(res_tag)::value;
+      unsigned oy[16], orr[16];
+      float v[16][2][2];
+      const unsigned cmask = n < p.N ? 0u : OOB;
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const unsigned px = px0 + (unsigned)a * (unsigned)p.W + (unsigned)c;
-          oy[a][c] = ok ? (px * (unsigned)p.ldy + (unsigned)n) * 4u : OOB;
-          orr[a][c] = ok ? (px * (unsigned)p.ldr + (unsigned)n) * 4u : OOB;
-          rv[a][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_r, (int)orr[a][c], 0, 0));
-        }
+      for (int r = 0; r < 16; ++r) {
+        const int t = tb + (r & 3) + 8 * (r >> 2);
+        const int xp = t % p.Wh;
+        const int u = t / p.Wh;                    // = b * Hh + ty
+        const unsigned px0 = ((unsigned)u * 2u) * (unsigned)p.W + 2u * (unsigned)xp;   // pixel (b, 2ty, 2xp): (b*H + 2ty) * W + 2xp
+        const unsigned mask = (t < p.Mt ? 0u : OOB) | cmask;                           // masked lanes: an out-of-range offset
+        oy[r] = max((px0 * (unsigned)p.ldy + (unsigned)n) * 4u, mask);
+        orr[r] = max((px0 * (unsigned)p.ldr + (unsigned)n) * 4u, mask);
+      }
+      if (RES) {
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int a = 0; a < 2; ++a)
+        for (int r = 0; r < 16; ++r)
 #pragma unroll
-        for (int c = 0; c < 2; ++c)
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (FMT ? Y[a][c][r] * inv_scale : Y[a][c][r]) + bv + rv[a][c]), rs_y, (int)oy[a][c], 0, 0);
-    }
+          for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+              v[r][a][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_r, (int)orr[r], (int)so_r[a][c], 0));
+        __builtin_amdgcn_sched_barrier(0);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int c = 0; c < 2; ++c)      // (no residual: "+ 0", what a load through an empty descriptor gives; it turns a -0 into +0)
+            v[r][a][c] = (FMT ? Y[a][c][r] * inv_scale : Y[a][c][r]) + bv + (RES ? v[r][a][c] : 0.f);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int c = 0; c < 2; ++c)
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[r][a][c]), rs_y, (int)oy[r], (int)so_y[a][c], 0);
+    };
+    if (p.res) epilogue(std::true_type{});           // (workgroup-uniform)
+    else epilogue(std::false_type{});
     return;
   }
   if (n >= p.N) return;
