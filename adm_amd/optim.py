@@ -215,6 +215,11 @@ def lr_lambda(it: int, lr: float, min_lr: float, train_num_steps: int, warmup: i
     return max((1 - (it - warmup) / train_num_steps) ** 0.96, min_lr / lr)
 
 
+def lr_lambda_cond(it: int, lr: float, min_lr: float, train_num_steps: int) -> float:
+    """LambdaLR ratio of the reference's conditional Trainer (train_cond_ldm.py:150): polynomial decay from step 0, no warm-up."""
+    return max((1 - it / train_num_steps) ** 0.96, min_lr / lr) if it < train_num_steps else min_lr / lr
+
+
 def ema_decay_at(step: int, beta: float = 0.9996, update_after_step: int = 10000, inv_gamma: float = 1.0,
                  power: float = 2 / 3, min_value: float = 0.0) -> float:
     """EMA.get_current_decay (ddm/ema.py:141-152)."""

@@ -15,7 +15,8 @@ the second decoder).
 The condition ENCODER ``init_conv_mask`` (cond_unet_sd.py:637-650): ``cond_encoder="swin_b"`` builds the Swin-B backbone of
 ``adm_amd.unet.swin_transformer`` (frozen by default: the reference's ``fix_bb: True`` state; ``train_cond_encoder=True``, also as
 a key of the YAML's ``unet:`` section, calls its ``enable_training()`` so that it trains with the denoiser as under the reference's
-``fix_bb: False``; its weights come from the checkpoint's ``init_conv_mask.*`` tensors, nothing is fetched).  EfficientNet-B7, ResNet-101 and the single-channel Swin variant
+``fix_bb: False``; its weights come from the checkpoint's ``init_conv_mask.*`` tensors, or for a fresh
+training run from the local file ``cond_encoder_weights`` names; nothing is fetched).  EfficientNet-B7, ResNet-101 and the single-channel Swin variant
 are not built.  With ``cond_encoder=None`` (the default) the encoder's output -- four feature maps of f, 2f, 4f, 8f channels
 (f = 128 for Swin-B) at 1/4, 1/8, 1/16, 1/32 of the condition image -- is what ``forward`` takes as ``mask`` (a list of four NCHW
 tensors); a user-supplied ``cond_encoder`` callable returns it for the condition image.
@@ -30,7 +31,7 @@ import torch.nn as nn
 
 from .. import ops
 from .. import ops_cond as oc
-from .swin_transformer import SwinTransformer, swin_b
+from .swin_transformer import SwinTransformer, load_encoder_weights, swin_b
 
 F_COND = {"swin": 128, "resnet": 256, "effnet": 48}
 
@@ -294,7 +295,7 @@ class Unet(nn.Module):
                  learned_variance=False, learned_sinusoidal_cond=False, random_fourier_features=False, learned_sinusoidal_dim=16,
                  window_sizes1=((16, 16), (8, 8), (4, 4), (2, 2)), window_sizes2=((16, 16), (8, 8), (4, 4), (2, 2)),
                  fourier_scale=16, precondition=True, ckpt_path=None, ignore_keys=(), cfg=None, cond_encoder=None, train_cond_encoder=False,
-                 **kwargs):
+                 cond_encoder_weights=None, **kwargs):
         super().__init__()
         if self_condition or learned_variance or learned_sinusoidal_cond or random_fourier_features or out_mul != 1:
             raise NotImplementedError("self_condition / learned_variance / learned sinusoidal embeddings / out_mul != 1 are not "
@@ -317,12 +318,14 @@ class Unet(nn.Module):
             if kwargs.get("single_channel_cond", False):
                 raise NotImplementedError("single_channel_cond (swin_transformer_for_sci) is not built")
             cond_encoder = swin_b(fix_bb=bool(kwargs.get("fix_bb", False)))
+            if cond_encoder_weights:          # a local file in torchvision's Swin-B layout (the reference fetches these weights)
+                load_encoder_weights(cond_encoder, cond_encoder_weights)
             if train_cond_encoder:
                 if cond_encoder.fix_bb:
                     raise ValueError("train_cond_encoder=True contradicts fix_bb=True (a fixed backbone is not trained)")
                 cond_encoder.enable_training()          # before any FlatParams is built: its tensors join the flat buffer
-        elif train_cond_encoder:
-            raise ValueError("train_cond_encoder=True needs the built-in encoder (cond_encoder='swin_b')")
+        elif train_cond_encoder or cond_encoder_weights:
+            raise ValueError("train_cond_encoder=True / cond_encoder_weights need the built-in encoder (cond_encoder='swin_b')")
         self.init_conv_mask = cond_encoder
         init_dim = init_dim if init_dim is not None else dim
         if dim % 32 or init_dim % 32:

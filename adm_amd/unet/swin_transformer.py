@@ -228,6 +228,47 @@ class SwinTransformer(nn.Module):
         return feats
 
 
+def load_encoder_weights(encoder: SwinTransformer, path: str) -> List[str]:
+    """Start ``encoder`` from a LOCAL state dict (read with ``weights_only=True``; nothing is fetched): the ImageNet weights the
+    reference's ``swin_b(weights=Swin_B_Weights...)`` starts from (swin_transformer.py:452-459).
+
+    Two namings are read.  torchvision's own (``torchvision.models.swin_b().state_dict()``: the patch embedding is ``features.0``,
+    the stages and mergings ``features.1`` ... ``features.7``) is recognised by its ``features.0.0.weight`` and renamed the way
+    the reference pairs the two key lists in order (:455-457): ``features.0.{0,2}`` -> ``first_coonv.{0,2}``, ``features.k`` ->
+    ``features.k-1``.  Otherwise the names are the encoder's own.  After that every ``features.*`` tensor of the encoder must be
+    present with its shape, and no tensor of the file may be unknown or of another shape; ``first_coonv.*``, ``norm.*`` and
+    ``head.*`` may be absent (they keep their initial values; a ``head`` of another class count is ignored).  Returns the names
+    that were absent."""
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(sd, dict) or not all(isinstance(v, torch.Tensor) for v in sd.values()):
+        raise RuntimeError(f"{path}: expected a flat state dict of tensors")
+    if "features.0.0.weight" in sd:          # torchvision's naming
+        renamed = {}
+        for k, v in sd.items():
+            parts = k.split(".")
+            if parts[0] == "features" and parts[1] == "0":
+                k = ".".join(["first_coonv"] + parts[2:])
+            elif parts[0] == "features":
+                k = ".".join(["features", str(int(parts[1]) - 1)] + parts[2:])
+            renamed[k] = v
+        sd = renamed
+    own = encoder.state_dict()
+    unknown = [k for k in sd if k not in own]
+    if unknown:
+        raise RuntimeError(f"{path}: {len(unknown)} tensors the encoder does not have (first: {unknown[0]})")
+    if "head.weight" in sd and sd["head.weight"].shape != own["head.weight"].shape:
+        sd = {k: v for k, v in sd.items() if not k.startswith("head.")}
+    bad = [k for k, v in sd.items() if tuple(v.shape) != tuple(own[k].shape)]
+    if bad:
+        raise RuntimeError(f"{path}: {bad[0]} is {tuple(sd[bad[0]].shape)}, the encoder's is {tuple(own[bad[0]].shape)}")
+    absent = [k for k in own if k not in sd]
+    lost = [k for k in absent if k.startswith("features.")]
+    if lost:
+        raise RuntimeError(f"{path} lacks {len(lost)} of the encoder's features.* tensors (first: {lost[0]})")
+    encoder.load_state_dict(sd, strict=False)
+    return absent
+
+
 def swin_b(**kwargs) -> SwinTransformer:
     """Swin-B: 4x4 patches, width 128, depths [2, 2, 18, 2], heads [4, 8, 16, 32], 7x7 windows.  No ``weights=`` argument: nothing
     is ever fetched, the tensors come from the conditional model's checkpoint."""

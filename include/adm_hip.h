@@ -499,6 +499,25 @@ long adm_aug_workspace_floats(int N, int C, int H, int W);
 int adm_augment_geometric(const float* images, const int* flips, const int* margin, const float* theta, float* ws,
                           float* out, int N, int C, int H, int W, hipStream_t stream);
 
+/* ---------------- super-resolution batches (ddm/data.py:645-658, SRDataset.__getitem__) ----------------
+ * One launch makes a batch from a uint8 image pool in device memory: sample b is the H x W crop at (top[b], left[b]) of image
+ * idx[b]; `image` [B][3][H][W] = (u8 / 255) * 2 - 1 of the crop, `cond` [B][3][h][w] = the same mapping of the crop resized to
+ * h x w with PIL's 8-bit two-pass arithmetic (horizontal pass clip8((2^21 + sum k*px) >> 22) into uint8, vertical pass over that),
+ * `cond_u8` [B][h][w][3] (may be NULL) = the resized bytes.  flip[b] != 0 mirrors the columns of both outputs, after the resize.
+ *   pool: packed HWC uint8 images, 4-byte aligned, pool_bytes a multiple of 4; image n starts at byte img_off[n] and is
+ *   img_hw[2n] x img_hw[2n+1] pixels.  idx / top / left / flip: int32 [B], read on the device (out-of-range draws are clamped).
+ *   hbounds [w][2] / vbounds [h][2] = {window start, window length} in crop coordinates; hcoef [w][kh] / vcoef [h][kv] = int32
+ *   coefficients with 22 fractional bits, kh / kv = the longest window (adm_amd/ddm/sr_data.py resample_table).
+ * A workgroup makes an ADM_SR_TILE_H x ADM_SR_TILE_W tile of `cond` from LDS; ADM_EINVAL, without launching, when the tile's
+ * source rectangle (sized from H/h, W/w, kh, kv) needs more than 64 KiB of LDS.  adm_sr_tile(0 / 1) = the tile's rows / columns. */
+#define ADM_SR_TILE_H 16
+#define ADM_SR_TILE_W 16
+int adm_sr_tile(int axis);
+int adm_sr_batch(const uint8_t* pool, long pool_bytes, const int64_t* img_off, const int* img_hw, int n_images, const int* idx,
+                 const int* top, const int* left, const int* flip, const int* hbounds, const int* hcoef, int kh,
+                 const int* vbounds, const int* vcoef, int kv, float* image, float* cond, uint8_t* cond_u8, int B, int H, int W,
+                 int h, int w, hipStream_t stream);
+
 /* ---------------- optimiser (train_uncond_dpm.py:292-310, ddm/ema.py:158-188) ---------------- */
 
 /* sumsq[0] += sum g^2.  partials = workspace of adm_sumsq_blocks(n) doubles: per-workgroup partial sums combined in a

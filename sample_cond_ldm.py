@@ -107,7 +107,11 @@ def resolve_encoder(spec, f=128):
 class CondStream:
     """Condition / target pairs.  ``data.class_name: synthetic`` draws U(-1,1) high-resolution images and box-downsamples them 4x
     for the condition (the geometry of ddm.data.SRDatasetTest: 'image', 'cond', 'ori_size', 'img_name'); ``data.npy`` may hold
-    uint8 [N,H,W,3] high-resolution images.  Anything else raises (no silent noise for a config that names a real dataset)."""
+    uint8 [N,H,W,3] high-resolution images.  ``data.class_name: ddm.data.SRDatasetTest`` (+ ``data.npy`` or ``img_folder``) makes the
+    condition the reference's test set makes (ddm/data.py:703-722): the image padded with black to multiples of
+    256, resized by ``down`` with PIL's bicubic arithmetic on the kernel that makes the training batches (adm_amd.ddm.sr_data), so a
+    model sees the same condition at sampling time as in training; 'image' is the unpadded image, as there.  Anything else
+    raises (no silent noise for a config that names a real dataset)."""
 
     def __init__(self, data_cfg, n, device, seed):
         import numpy as np
@@ -116,7 +120,24 @@ class CondStream:
         self.images = None
         self.size = tuple(data_cfg.get("image_size") or (512, 512))
         path, cls = data_cfg.get("npy"), data_cfg.get("class_name")
-        if path:
+        self.u8, self.names = None, None
+        self.down, self.filter = int(data_cfg.get("down") or 4), data_cfg.get("inter_type") or "bicubic"
+        if cls in ("ddm.data.SRDatasetTest", "SRDatasetTest"):
+            if self.down != 4:
+                raise NotImplementedError("the sliding-window sampler places its windows at x4 (reference :324-328): data.down must be 4")
+            if path:
+                if not os.path.exists(path):
+                    raise FileNotFoundError(f"data.npy: {path} does not exist")
+                arr = np.load(path, allow_pickle=False)
+                if arr.dtype != np.uint8 or arr.ndim != 4 or arr.shape[-1] != 3:
+                    raise ValueError(f"image array must be uint8 [N,H,W,3], got {arr.dtype} {arr.shape}")
+                self.u8, self.names = list(arr), [f"{i: 010d}.png" for i in range(arr.shape[0])]
+            elif data_cfg.get("img_folder"):
+                from adm_amd.ddm.sr_data import load_image_folder
+                self.u8, self.names = load_image_folder(data_cfg.get("img_folder"))
+            else:
+                raise ValueError("data.class_name ddm.data.SRDatasetTest needs data.npy or data.img_folder")
+        elif path:
             if not os.path.exists(path):
                 raise FileNotFoundError(f"data.npy: {path} does not exist")
             arr = np.load(path, allow_pickle=False)
@@ -126,8 +147,22 @@ class CondStream:
         elif cls != "synthetic":
             raise NotImplementedError(f"data.class_name {cls!r}: only a uint8 data.npy or 'synthetic' are implemented")
 
+    def sr_test_item(self, i):
+        """SRDatasetTest.__getitem__ (data.py:703-722) for image i."""
+        import numpy as np
+        from adm_amd.ddm.sr_data import resample_image
+        img = self.u8[i % len(self.u8)]
+        H, W = img.shape[:2]
+        pad = np.zeros((-(-H // 256) * 256, -(-W // 256) * 256, 3), dtype=np.uint8)
+        pad[:H, :W] = img
+        image, cond, _ = resample_image(pad, self.down, self.filter, self.device)
+        return {"image": image[:, :, :H, :W].contiguous(), "cond": cond, "ori_size": (H, W), "img_name": self.names[i % len(self.u8)]}
+
     def __iter__(self):
         for i in range(self.n):
+            if self.u8 is not None:
+                yield self.sr_test_item(i)
+                continue
             if self.images is not None:
                 img = self.images[i % self.images.shape[0]][None].to(self.device)
             else:
@@ -168,7 +203,8 @@ def main():
         if not os.path.exists(s.ckpt_path):
             raise FileNotFoundError(f"sampler.ckpt_path {s.ckpt_path} does not exist (pass --random-init for a smoke run)")
         missing, _ = load_weights(ldm, s.ckpt_path, s.get("use_ema", True), device)
-        lost = [k for k in missing if ".init_conv_mask." in k]
+        # (norm.* / head.* of the encoder are holders its forward never reads; an EMA copy holds trained tensors only, so lacks them)
+        lost = [k for k in missing if ".init_conv_mask." in k and ".init_conv_mask.norm." not in k and ".init_conv_mask.head." not in k]
         if builtin and lost:
             raise RuntimeError(f"sampler.cond_encoder: swin_b, but {s.ckpt_path} lacks {len(lost)} of the encoder's tensors "
                                f"(first: {lost[0]}): the checkpoint must hold the trained init_conv_mask.* weights")
@@ -187,7 +223,8 @@ def main():
         down = ldm.first_stage_model.down_ratio
         # the encoder runs ONCE per window batch (the reference re-runs it inside every denoising step, cond_unet_sd.py:821)
         fn = lambda c: ldm.sample(cond=list(ldm.model.init_conv_mask(c)), latent_hw=(c.shape[2] * 4 // down, c.shape[3] * 4 // down))
-        pred = slide_sample_sr(fn, cond, image.shape[-2:], crop, stride,
+        # the frame the windows tile is the condition's, x4 (for SRDatasetTest larger than the unpadded image: reference :324-332)
+        pred = slide_sample_sr(fn, cond, (cond.shape[-2] * 4, cond.shape[-1] * 4), crop, stride,
                                out_channels=int(s.get("out_channels", 3)), ori_size=batch["ori_size"],
                                window_batch=int(s.get("window_batch", 0)), flip_test=bool(s.get("flip_test", False)))
         H, W = batch["ori_size"]

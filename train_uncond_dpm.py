@@ -232,6 +232,13 @@ class Trainer:
         from adm_amd import ops
         ops.invalidate_packed()
 
+    def sample_grid(self, milestone, batch):
+        """The periodic sample (train_uncond_dpm.py:315-333); `batch` is the last training micro-batch (conditional drivers)."""
+        self.model.eval()
+        img = self.model.sample(batch_size=16)
+        self.model.train()
+        save_grid(img, os.path.join(self.results, f"sample-{milestone}.png"), 4)
+
     def train(self, max_steps=None):
         last, seen = time.time(), 0
         end = self.train_num_steps if max_steps is None else min(self.train_num_steps, self.step + max_steps)
@@ -274,10 +281,7 @@ class Trainer:
                 milestone = self.step // self.save_every
                 self.save(milestone)
                 if self.rank == 0:
-                    self.model.eval()
-                    img = self.model.sample(batch_size=16)
-                    self.model.train()
-                    save_grid(img, os.path.join(self.results, f"sample-{milestone}.png"), 4)
+                    self.sample_grid(milestone, batch)
         if self.rank == 0:
             print("training complete")
 
