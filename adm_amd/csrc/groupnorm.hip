@@ -33,6 +33,20 @@ __device__ __forceinline__ void gn_amax_commit(float am, float* amax) { adm_amax
 
 __host__ __device__ inline int gn_rows_par(int C) { int r = 256 / (C / 4); return r < 1 ? 1 : r; }
 
+// The concat forms (a decoder block's input): the GroupNorm input is z = (a | scale_b * b) along the channels, C = Ca + Cb.  Forward, the
+// moments pass reads the two halves in place of z -- a thread owns one channel quad, so it owns one source -- and writes z (the 1x1 skip
+// conv reads it) with its bound; backward, the dx pass writes the two halves of the gradient (da = dz[:, :Ca], db = scale_b * dz[:, Ca:])
+// in place of dz.  Values and rounding are those of adm_concat2 / adm_split2 (elementwise.hip).
+struct GnCat { const float* a; const float* b; float* z; float* amax_z; int Ca; float scale_b; };
+struct GnSplit { float* da; float* db; int Ca; float scale_b; };
+
+// scale_b * v rounded as adm_concat2 rounds it: the product is a value of its own (an element of z), so it must not be contracted
+// into the subtractions / multiply-adds that consume it (tests/test_hip_gn_concat.py compares bits at a scale that is no power of two)
+__device__ __forceinline__ f32x4 gn_scaled4(f32x4 v, float s) {
+#pragma clang fp contract(off)
+  return v * s;
+}
+
 // ---------------------------------------------------------------- forward: moments
 // Numerically robust moments ("Welford / two-pass"): every thread accumulates SHIFTED sums
 // s1 = sum(x - K), s2 = sum((x - K)^2) with K = the first value it sees per channel, so s2 - s1^2/n has no catastrophic
@@ -40,8 +54,12 @@ __host__ __device__ inline int gn_rows_par(int C) { int r = 256 / (C / 4); retur
 // per-thread (n, mean, M2) triples are merged exactly in fp64, in a fixed order (deterministic).
 // Exact merge of sub-populations (n_i, mean_i, M2_i):  N = sum n_i,  mean = sum n_i mean_i / N,
 // M2 = sum [M2_i + n_i (mean_i - mean)^2]  -- two passes over the (few) partials, one division.
+// CAT: x is not read; the thread reads its quad from cat_a or cat_b (the members of a GnCat, above, as separate restrict parameters),
+// writes it to cat_z and raises amax_z.
+template <bool CAT>
 __global__ void gn_partial_kernel(const float* __restrict__ x, double* __restrict__ ws, int HW, int C, int G,
-                                  int rows_per_split) {
+                                  int rows_per_split, const float* __restrict__ cat_a, const float* __restrict__ cat_b,
+                                  float* __restrict__ cat_z, float* __restrict__ amax_z, int Ca, float scale_b) {
   extern __shared__ float sm[];          // [R][C][3] : K, s1, s2
   const int C4 = C >> 2, R = blockDim.x / C4;
   const int cq = threadIdx.x % C4, ry = threadIdx.x / C4;
@@ -49,12 +67,44 @@ __global__ void gn_partial_kernel(const float* __restrict__ x, double* __restric
   const int hw0 = s * rows_per_split, hw1 = min(HW, hw0 + rows_per_split);
   const f32x4* xb = reinterpret_cast<const f32x4*>(x + (long)b * HW * C);
   f32x4 s1 = {0, 0, 0, 0}, s2 = {0, 0, 0, 0}, K = {0, 0, 0, 0};
-  if (hw0 + ry < hw1) K = xb[(long)(hw0 + ry) * C4 + cq];
+  if (CAT) {
+    const int Ca4 = Ca >> 2, Cb4 = C4 - Ca4;
+    const bool second = cq >= Ca4;
+    const int ld = second ? Cb4 : Ca4;                 // the thread's source: row stride and first quad
+    const f32x4* src = second ? reinterpret_cast<const f32x4*>(cat_b) + (long)b * HW * Cb4 + (cq - Ca4)
+                              : reinterpret_cast<const f32x4*>(cat_a) + (long)b * HW * Ca4 + cq;
+    f32x4* zb = reinterpret_cast<f32x4*>(cat_z) + (long)b * HW * C4 + cq;
+    float am = 0.f;
+    if (hw0 + ry < hw1) {
+      K = src[(long)(hw0 + ry) * ld];
+      if (second) K = gn_scaled4(K, scale_b);
+    }
+    auto row = [&](int hw, f32x4 t) {                  // rows in ascending order: the summation order of the plain form
+      if (second) t = gn_scaled4(t, scale_b);
+      zb[(long)hw * C4] = t;
+      am = gn_amax4(am, t);
+      f32x4 v = t - K;
+      s1 += v;
+      s2 += v * v;
+    };
+    int hw = hw0 + ry;
+    for (; hw + 3 * R < hw1; hw += 4 * R) {            // four rows' loads in flight before the first store (unrolled by hand: the
+      f32x4 t[4];                                      //  compiler keeps a load behind the store that precedes it in program order)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t[j] = src[(long)(hw + j * R) * ld];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) row(hw + j * R, t[j]);
+    }
+    for (; hw < hw1; hw += R) row(hw, src[(long)hw * ld]);
+    gn_amax_commit(am, amax_z);
+  } else {
+    if (hw0 + ry < hw1) K = xb[(long)(hw0 + ry) * C4 + cq];
 #pragma unroll 4
-  for (int hw = hw0 + ry; hw < hw1; hw += R) {
-    f32x4 v = xb[(long)hw * C4 + cq] - K;
-    s1 += v;
-    s2 += v * v;
+    for (int hw = hw0 + ry; hw < hw1; hw += R) {
+      f32x4 v = xb[(long)hw * C4 + cq] - K;
+      s1 += v;
+      s2 += v * v;
+    }
   }
   float* p1 = sm + (ry * C + cq * 4) * 3;
 #pragma unroll
@@ -302,13 +352,15 @@ __global__ __launch_bounds__(256) void gn_bwd_param_table_kernel(const long* __r
   }
 }
 
-// pass 4: dx = rstd * (gamma' du - m1 - xhat m2)
+// pass 4: dx = rstd * (gamma' du - m1 - xhat m2).  CAT: dx goes to the two halves da, db of a GnSplit (dx itself is not written).
+template <bool CAT>
 __global__ void gn_bwd_dx_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                  const float* __restrict__ stats, const float* __restrict__ gamma,
                                  const float* __restrict__ beta, const float* __restrict__ ss, long ss_bstride,
                                  const float* __restrict__ gm, const float* __restrict__ addend,
                                  float* __restrict__ dx, int HW, int C, int G, int rows_per_split, int silu, float drop_p,
-                                 uint64_t seed, float* __restrict__ amax) {
+                                 uint64_t seed, float* __restrict__ amax, float* __restrict__ da, float* __restrict__ db, int Ca,
+                                 float scale_b) {
   const int C4 = C >> 2, R = blockDim.x / C4;
   const int cq = threadIdx.x % C4, ry = threadIdx.x / C4;
   const int b = blockIdx.x;
@@ -332,6 +384,15 @@ __global__ void gn_bwd_dx_kernel(const float* __restrict__ x, const float* __res
   const f32x4* xb = reinterpret_cast<const f32x4*>(x + (long)b * HW * C);
   const f32x4* gb = reinterpret_cast<const f32x4*>(dy + (long)b * HW * C);
   f32x4* ob = reinterpret_cast<f32x4*>(dx + (long)b * HW * C);
+  int ld = C4;                                          // the thread's destination: row stride (ob then points at its first quad)
+  bool second = false;
+  if (CAT) {
+    const int Ca4 = Ca >> 2, Cb4 = C4 - Ca4;
+    second = cq >= Ca4;
+    ld = second ? Cb4 : Ca4;
+    ob = second ? reinterpret_cast<f32x4*>(db) + (long)b * HW * Cb4 + (cq - Ca4)
+                : reinterpret_cast<f32x4*>(da) + (long)b * HW * Ca4 + cq;
+  }
   const f32x4* ab = addend ? reinterpret_cast<const f32x4*>(addend + (long)b * HW * C) : nullptr;
   const float inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
   float am = 0.f;
@@ -349,7 +410,8 @@ __global__ void gn_bwd_dx_kernel(const float* __restrict__ x, const float* __res
     }
     const f32x4 o = cg * d - c1 - ((v - cm) * cr) * c2 + extra;
     am = gn_amax4(am, o);
-    ob[(long)hw * C4 + cq] = o;
+    if (CAT) ob[(long)hw * ld] = second ? o * scale_b : o;
+    else ob[(long)hw * C4 + cq] = o;
   }
   gn_amax_commit(am, amax);               // max |dx|: the data-gradient conv that consumes dx may run on the fp16 format
 }
@@ -361,25 +423,38 @@ __global__ void gn_bwd_dx_kernel(const float* __restrict__ x, const float* __res
 // Thread map as above restricted to the chunk: Cc4 = Cc/4 quads, R = blockDim / Cc4 rows in flight, each thread owns
 // rows ry, ry + R, ... (<= MAXR of them).  Reductions keep the fixed summation order of the multi-launch path
 // (deterministic), with the same fp64 group combine.
-template <int MAXR, int THREADS>
+// CAT: as gn_partial_kernel<true> -- the slab is loaded from the two sources, and written to cat_z next to y.
+template <int MAXR, int THREADS, bool CAT>
 __global__ __launch_bounds__(THREADS, (MAXR <= 8 ? 4 : 3)) void gn_fused_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, const float* __restrict__ ss,
                                                            long ss_bstride, float* __restrict__ y,
                                                            float* __restrict__ stats, int HW, int C, int G, int Cc,
                                                            float eps, int silu, float drop_p, uint64_t seed, int out_bf16,
-                                                           float* __restrict__ amax) {
+                                                           float* __restrict__ amax, const float* __restrict__ cat_a,
+                                                           const float* __restrict__ cat_b, float* __restrict__ cat_z,
+                                                           float* __restrict__ amax_z, int Ca, float scale_b) {
   extern __shared__ float sm[];                    // [R][Cc][2] partials | [Gc][2] mean, rstd
   const int Cc4 = Cc >> 2, R = blockDim.x / Cc4, C4 = C >> 2;
   const int cq = threadIdx.x % Cc4, ry = threadIdx.x / Cc4;
   const int b = blockIdx.y, c0 = blockIdx.x * Cc;        // slabs of one image are adjacent in launch order: they share cache lines
   const int cpg = C / G, Gc = Cc / cpg, g0 = c0 / cpg;
-  const f32x4* xb = reinterpret_cast<const f32x4*>(x + (long)b * HW * C + c0);
+  const f32x4* xb = reinterpret_cast<const f32x4*>(x + (long)b * HW * C + c0) + cq;
+  int ld = C4;                                      // the thread's source: row stride (xb points at its first quad)
+  bool second = false;
+  if (CAT) {
+    const int Ca4 = Ca >> 2, Cb4 = C4 - Ca4, q = (c0 >> 2) + cq;
+    second = q >= Ca4;
+    ld = second ? Cb4 : Ca4;
+    xb = second ? reinterpret_cast<const f32x4*>(cat_b) + (long)b * HW * Cb4 + (q - Ca4)
+                : reinterpret_cast<const f32x4*>(cat_a) + (long)b * HW * Ca4 + q;
+  }
   f32x4 v[MAXR];
   f32x4 s1 = {0, 0, 0, 0}, s2 = {0, 0, 0, 0};
 #pragma unroll
   for (int i = 0; i < MAXR; ++i) {
     const int hw = ry + i * R;
-    const f32x4 t = xb[(long)min(hw, HW - 1) * C4 + cq];          // unconditional (clamped) load: no branch per row
+    f32x4 t = xb[(long)min(hw, HW - 1) * ld];                     // unconditional (clamped) load: no branch per row
+    if (CAT && second) t = gn_scaled4(t, scale_b);
     v[i] = hw < HW ? t : f32x4{0, 0, 0, 0};
   }
   // the slab is in registers: a true two-pass per thread (own mean first, then squared deviations), merged in fp64
@@ -449,11 +524,15 @@ __global__ __launch_bounds__(THREADS, (MAXR <= 8 ? 4 : 3)) void gn_fused_fwd_ker
   }
   const long ybase = (long)b * HW * C4 + (c0 >> 2);  // in channel quads
   const float inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-  float am = 0.f;
+  float am = 0.f, amz = 0.f;
 #pragma unroll
   for (int i = 0; i < MAXR; ++i) {
     const int hw = ry + i * R;
     if (hw >= HW) continue;
+    if (CAT) {
+      reinterpret_cast<f32x4*>(cat_z)[ybase + (long)hw * C4 + cq] = v[i];
+      amz = gn_amax4(amz, v[i]);
+    }
     f32x4 u = v[i] * ca + cb;
     if (silu) {
 #pragma unroll
@@ -465,18 +544,21 @@ __global__ __launch_bounds__(THREADS, (MAXR <= 8 ? 4 : 3)) void gn_fused_fwd_ker
     __builtin_amdgcn_sched_barrier(0);            // one row at a time: interleaving the rows' hashes / exponentials costs registers
   }
   gn_amax_commit(am, amax);
+  if (CAT) gn_amax_commit(amz, amax_z);
 }
 
 // (second launch bound = waves per SIMD: left alone the compiler hoists the dropout hashes and SiLU derivatives of all rows and
 // takes 186-256 registers, i.e. one or two waves per SIMD for a bandwidth-bound kernel)
-template <int MAXR, int THREADS>
+// CAT: as gn_bwd_dx_kernel<true>.
+template <int MAXR, int THREADS, bool CAT>
 __global__ __launch_bounds__(THREADS, (MAXR <= 8 ? 4 : 2)) void gn_fused_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                            const float* __restrict__ stats, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, const float* __restrict__ ss,
                                                            long ss_bstride, const float* __restrict__ addend,
                                                            float* __restrict__ dx, float* __restrict__ tot,
                                                            float* __restrict__ dss, int HW, int C, int G, int Cc, int silu,
-                                                           float drop_p, uint64_t seed, float* __restrict__ amax) {
+                                                           float drop_p, uint64_t seed, float* __restrict__ amax,
+                                                           float* __restrict__ da, float* __restrict__ db, int Ca, float scale_b) {
   extern __shared__ float sm[];                    // [R][Cc][2] partials | [Cc][2] gamma' R1, gamma' R2 | [Gc][2] m1, m2
   const int Cc4 = Cc >> 2, R = blockDim.x / Cc4, C4 = C >> 2;
   const int cq = threadIdx.x % Cc4, ry = threadIdx.x / Cc4;
@@ -564,7 +646,16 @@ __global__ __launch_bounds__(THREADS, (MAXR <= 8 ? 4 : 2)) void gn_fused_bwd_ker
     c2[k] = cr[k] * gmv[2 * g + 1];
   }
   (void)g0;
-  f32x4* ob = reinterpret_cast<f32x4*>(dx + (long)b * HW * C + c0);
+  f32x4* ob = reinterpret_cast<f32x4*>(dx + (long)b * HW * C + c0) + cq;
+  int ld = C4;                                      // the thread's destination: row stride (ob points at its first quad)
+  bool second = false;
+  if (CAT) {
+    const int Ca4 = Ca >> 2, Cb4 = C4 - Ca4, q = (c0 >> 2) + cq;
+    second = q >= Ca4;
+    ld = second ? Cb4 : Ca4;
+    ob = second ? reinterpret_cast<f32x4*>(db) + (long)b * HW * Cb4 + (q - Ca4)
+                : reinterpret_cast<f32x4*>(da) + (long)b * HW * Ca4 + q;
+  }
   const f32x4* ab = addend ? reinterpret_cast<const f32x4*>(addend + (long)b * HW * C + c0) : nullptr;
   float am = 0.f;
 #pragma unroll
@@ -574,7 +665,7 @@ __global__ __launch_bounds__(THREADS, (MAXR <= 8 ? 4 : 2)) void gn_fused_bwd_ker
     f32x4 o = ca * d[i] - c1 - xh[i] * c2;
     if (ab) o += ab[(long)hw * C4 + cq];
     am = gn_amax4(am, o);
-    ob[(long)hw * C4 + cq] = o;
+    ob[(long)hw * ld] = (CAT && second) ? o * scale_b : o;
   }
   gn_amax_commit(am, amax);
 }
@@ -647,16 +738,33 @@ extern "C" int adm_gn_plan(int HW, int C, int G, int* out) {
   return ADM_OK;
 }
 
-extern "C" int adm_gn_stats(const float* x, float* stats, double* ws, int B, int HW, int C, int G, float eps,
-                            hipStream_t stream) {
-  if (!x || !stats || !ws || !gn_shape_ok(B, HW, C, G)) return ADM_EINVAL;
+#define GN_NO_CAT static_cast<const float*>(nullptr), static_cast<const float*>(nullptr), static_cast<float*>(nullptr), \
+                  static_cast<float*>(nullptr), 0, 1.f
+#define GN_NO_SPLIT static_cast<float*>(nullptr), static_cast<float*>(nullptr), 0, 1.f
+// a concat form's halves: whole channel quads on both sides, every pointer there (the bound of z may be missing)
+static bool gn_cat_ok(const GnCat& c, int C) {
+  return c.a && c.b && c.z && c.Ca > 0 && c.Ca < C && (c.Ca & 3) == 0 && ((C - c.Ca) & 3) == 0;
+}
+
+static int gn_stats_impl(const float* x, float* stats, double* ws, int B, int HW, int C, int G, float eps, hipStream_t stream,
+                         const GnCat* cat = nullptr) {
+  if ((!x && !cat) || !stats || !ws || !gn_shape_ok(B, HW, C, G)) return ADM_EINVAL;
   int S = adm_gn_splits(HW, C), rows = adm_cdiv(HW, S), R = gn_rows_par(C);
   size_t smem = (size_t)R * C * 3 * sizeof(float);
-  hipLaunchKernelGGL(gn_partial_kernel, dim3(B, S), dim3(gn_threads(C)), smem, stream, x, ws, HW, C, G, rows);
+  if (cat)
+    hipLaunchKernelGGL(gn_partial_kernel<true>, dim3(B, S), dim3(gn_threads(C)), smem, stream, x, ws, HW, C, G, rows, cat->a, cat->b,
+                       cat->z, cat->amax_z, cat->Ca, cat->scale_b);
+  else
+    hipLaunchKernelGGL(gn_partial_kernel<false>, dim3(B, S), dim3(gn_threads(C)), smem, stream, x, ws, HW, C, G, rows, GN_NO_CAT);
   hipLaunchKernelGGL(gn_finalize_kernel, dim3(adm_cdiv(B * G, 256)), dim3(256), 0, stream, ws, stats, B * G, G, S, HW,
                      rows, C / G, eps);
   ADM_CHECK_LAUNCH();
   return ADM_OK;
+}
+
+extern "C" int adm_gn_stats(const float* x, float* stats, double* ws, int B, int HW, int C, int G, float eps,
+                            hipStream_t stream) {
+  return gn_stats_impl(x, stats, ws, B, HW, C, G, eps, stream);
 }
 
 static int gn_apply_impl(const float* x, const float* stats, const float* gamma, const float* beta, const float* ss, long ss_bstride,
@@ -679,7 +787,7 @@ extern "C" int adm_gn_apply(const float* x, const float* stats, const float* gam
 
 static int gn_fwd_impl(const float* x, float* stats, double* ws, const float* gamma, const float* beta, const float* ss,
                        long ss_bstride, float* y, int B, int HW, int C, int G, float eps, int silu, float drop_p, uint64_t seed,
-                       int out_bf16, hipStream_t stream, float* amax = nullptr);
+                       int out_bf16, hipStream_t stream, float* amax = nullptr, const GnCat* cat = nullptr);
 
 // adm_gn_fwd that also raises *amax (a device float the caller zeroed) to max |y|: the scale basis of the fp16-format conv that
 // consumes y (adm_conv_fwd_wino2d_h3)
@@ -704,27 +812,48 @@ extern "C" int adm_gn_fwd_bf16out(const float* x, float* stats, double* ws, cons
                      stream);
 }
 
+// adm_gn_fwd_amax on z = (a | scale_b * b) [B][HW][Ca + Cb] without a copy pass in front of it: the moments pass (the one launch, where
+// the map is small) reads a and b, writes z and raises amax_z (may be NULL) to max |z| -- z and its bound exactly as adm_concat2
+// leaves them; y, stats and amax (may be NULL) exactly as adm_gn_fwd_amax on that z leaves them.
+extern "C" int adm_gn_fwd_cat_amax(const float* a, int Ca, const float* b, int Cb, float scale_b, float* z, float* amax_z, float* stats,
+                                   double* ws, const float* gamma, const float* beta, const float* ss, long ss_bstride, float* y,
+                                   float* amax, int B, int HW, int G, float eps, int silu, float drop_p, uint64_t seed,
+                                   hipStream_t stream) {
+  if (Ca <= 0 || Cb <= 0) return ADM_EINVAL;
+  const GnCat cat{a, b, z, amax_z, Ca, scale_b};
+  return gn_fwd_impl(z, stats, ws, gamma, beta, ss, ss_bstride, y, B, HW, Ca + Cb, G, eps, silu, drop_p, seed, 0, stream, amax, &cat);
+}
+
 static int gn_fwd_impl(const float* x, float* stats, double* ws, const float* gamma, const float* beta, const float* ss,
                        long ss_bstride, float* y, int B, int HW, int C, int G, float eps, int silu, float drop_p, uint64_t seed,
-                       int out_bf16, hipStream_t stream, float* amax) {
+                       int out_bf16, hipStream_t stream, float* amax, const GnCat* cat) {
   if (!x || !stats || !ws || !gamma || !beta || !y || !gn_shape_ok(B, HW, C, G) || drop_p < 0.f || drop_p >= 1.f)
     return ADM_EINVAL;
+  if (cat && !gn_cat_ok(*cat, C)) return ADM_EINVAL;
   const GnPlan pl = gn_plan_now(HW, C, G, false);
-  if (pl.Cc == 0) {
-    int rc = adm_gn_stats(x, stats, ws, B, HW, C, G, eps, stream);
+  if (pl.Cc == 0) {          // (concat form: x is z, which the moments pass has written when the apply pass reads it)
+    int rc = gn_stats_impl(x, stats, ws, B, HW, C, G, eps, stream, cat);
     if (rc != ADM_OK) return rc;
     return gn_apply_impl(x, stats, gamma, beta, ss, ss_bstride, y, B, HW, C, G, silu, drop_p, seed, out_bf16, stream, amax);
   }
   const int Cc = pl.Cc, R = pl.threads / (Cc / 4), Gc = Cc / (C / G);
   const size_t smem = ((size_t)R * Cc * 2 + (size_t)((Gc * 2 + 1) & ~1)) * sizeof(float) + (size_t)Cc * sizeof(double);
   const dim3 grid(C / Cc, B), block(pl.threads);
-#define GN_FWD(MAXR, THREADS)                                                                                                 \
-  hipLaunchKernelGGL((gn_fused_fwd_kernel<MAXR, THREADS>), grid, block, smem, stream, x, gamma, beta, ss, ss_bstride, y, stats, \
-                     HW, C, G, Cc, eps, silu, drop_p, seed, out_bf16, amax)
-  switch (gn_fused_template(pl.rows)) {
-    case 2: GN_FWD(2, 256); break;
-    case 8: GN_FWD(8, 256); break;
-    default: GN_FWD(14, 256);
+#define GN_FWD(MAXR, THREADS, CAT, ...)                                                                                         \
+  hipLaunchKernelGGL((gn_fused_fwd_kernel<MAXR, THREADS, CAT>), grid, block, smem, stream, x, gamma, beta, ss, ss_bstride, y, stats, \
+                     HW, C, G, Cc, eps, silu, drop_p, seed, out_bf16, amax, __VA_ARGS__)
+  if (cat) {
+    switch (gn_fused_template(pl.rows)) {
+      case 2: GN_FWD(2, 256, true, cat->a, cat->b, cat->z, cat->amax_z, cat->Ca, cat->scale_b); break;
+      case 8: GN_FWD(8, 256, true, cat->a, cat->b, cat->z, cat->amax_z, cat->Ca, cat->scale_b); break;
+      default: GN_FWD(14, 256, true, cat->a, cat->b, cat->z, cat->amax_z, cat->Ca, cat->scale_b);
+    }
+  } else {
+    switch (gn_fused_template(pl.rows)) {
+      case 2: GN_FWD(2, 256, false, GN_NO_CAT); break;
+      case 8: GN_FWD(8, 256, false, GN_NO_CAT); break;
+      default: GN_FWD(14, 256, false, GN_NO_CAT);
+    }
   }
 #undef GN_FWD
   ADM_CHECK_LAUNCH();
@@ -747,9 +876,10 @@ extern "C" int adm_gn_bwd(const float* x, const float* dy, const float* stats, c
 static int gn_bwd_add_impl(const float* x, const float* dy, const float* stats, const float* gamma, const float* beta,
                            const float* ss, long ss_bstride, const float* addend, float* dx, float* dss, float* dgamma,
                            float* dbeta, float* red, int B, int HW, int C, int G, int silu, float drop_p, uint64_t seed,
-                           hipStream_t stream, float* amax) {
+                           hipStream_t stream, float* amax, const GnSplit* sp = nullptr) {
 
-  if (!x || !dy || !stats || !gamma || !beta || !dx || !red || !gn_shape_ok(B, HW, C, G)) return ADM_EINVAL;
+  if (!x || !dy || !stats || !gamma || !beta || (!dx && !sp) || !red || !gn_shape_ok(B, HW, C, G)) return ADM_EINVAL;
+  if (sp && (!sp->da || !sp->db || sp->Ca <= 0 || sp->Ca >= C || (sp->Ca & 3) || ((C - sp->Ca) & 3))) return ADM_EINVAL;
   if ((dgamma == nullptr) != (dbeta == nullptr)) return ADM_EINVAL;
   int S = adm_gn_splits(HW, C), rows = adm_cdiv(HW, S), R = gn_rows_par(C);
   float* part = red;
@@ -760,13 +890,21 @@ static int gn_bwd_add_impl(const float* x, const float* dy, const float* stats, 
     const int Cc = pl.Cc, Rf = pl.threads / (Cc / 4), Gc = Cc / (C / G);
     const size_t smf = ((size_t)Rf * Cc * 2 + (size_t)Cc * 2 + (size_t)Gc * 2) * sizeof(float);
     const dim3 grid(C / Cc, B), block(pl.threads);
-#define GN_BWD(MAXR, THREADS)                                                                                                   \
-  hipLaunchKernelGGL((gn_fused_bwd_kernel<MAXR, THREADS>), grid, block, smf, stream, x, dy, stats, gamma, beta, ss, ss_bstride, \
-                     addend, dx, tot, dss, HW, C, G, Cc, silu, drop_p, seed, amax)
-    switch (gn_fused_template(pl.rows)) {
-      case 2: GN_BWD(2, 256); break;
-      case 8: GN_BWD(8, 256); break;
-      default: GN_BWD(14, 256);
+#define GN_BWD(MAXR, THREADS, CAT, ...)                                                                                           \
+  hipLaunchKernelGGL((gn_fused_bwd_kernel<MAXR, THREADS, CAT>), grid, block, smf, stream, x, dy, stats, gamma, beta, ss, ss_bstride, \
+                     addend, dx, tot, dss, HW, C, G, Cc, silu, drop_p, seed, amax, __VA_ARGS__)
+    if (sp) {
+      switch (gn_fused_template(pl.rows)) {
+        case 2: GN_BWD(2, 256, true, sp->da, sp->db, sp->Ca, sp->scale_b); break;
+        case 8: GN_BWD(8, 256, true, sp->da, sp->db, sp->Ca, sp->scale_b); break;
+        default: GN_BWD(14, 256, true, sp->da, sp->db, sp->Ca, sp->scale_b);
+      }
+    } else {
+      switch (gn_fused_template(pl.rows)) {
+        case 2: GN_BWD(2, 256, false, GN_NO_SPLIT); break;
+        case 8: GN_BWD(8, 256, false, GN_NO_SPLIT); break;
+        default: GN_BWD(14, 256, false, GN_NO_SPLIT);
+      }
     }
 #undef GN_BWD
     if (dgamma)
@@ -783,8 +921,12 @@ static int gn_bwd_add_impl(const float* x, const float* dy, const float* stats, 
   if (dgamma)
     hipLaunchKernelGGL(gn_bwd_param_kernel, dim3(adm_cdiv(C, 32)), dim3(256), 0, stream, tot, ss, ss_bstride, dgamma,
                        dbeta, B, C);
-  hipLaunchKernelGGL(gn_bwd_dx_kernel, dim3(B, S), dim3(gn_threads(C)), 0, stream, x, dy, stats, gamma, beta, ss,
-                     ss_bstride, gm, addend, dx, HW, C, G, rows, silu, drop_p, seed, amax);
+  if (sp)
+    hipLaunchKernelGGL(gn_bwd_dx_kernel<true>, dim3(B, S), dim3(gn_threads(C)), 0, stream, x, dy, stats, gamma, beta, ss,
+                       ss_bstride, gm, addend, dx, HW, C, G, rows, silu, drop_p, seed, amax, sp->da, sp->db, sp->Ca, sp->scale_b);
+  else
+    hipLaunchKernelGGL(gn_bwd_dx_kernel<false>, dim3(B, S), dim3(gn_threads(C)), 0, stream, x, dy, stats, gamma, beta, ss,
+                       ss_bstride, gm, addend, dx, HW, C, G, rows, silu, drop_p, seed, amax, GN_NO_SPLIT);
   ADM_CHECK_LAUNCH();
   return ADM_OK;
 }
@@ -803,6 +945,19 @@ extern "C" int adm_gn_bwd_add_amax(const float* x, const float* dy, const float*
                                    uint64_t seed, hipStream_t stream) {
   return gn_bwd_add_impl(x, dy, stats, gamma, beta, ss, ss_bstride, addend, dx, dss, dgamma, dbeta, red, B, HW, C, G, silu, drop_p, seed,
                          stream, amax);
+}
+
+// adm_gn_bwd_add_amax of a concat form (x = z of adm_gn_fwd_cat_amax, C = Ca + Cb): the gradient of z is not written -- the dx pass
+// stores da[B][HW][Ca] = dz[:, :Ca] and db[B][HW][Cb] = scale_b * dz[:, Ca:] (the values adm_split2 makes of dz); amax (may be NULL) is
+// raised to max |dz|, before the scaling, as adm_gn_bwd_add_amax raises it.
+extern "C" int adm_gn_bwd_add_cat_amax(const float* x, const float* dy, const float* stats, const float* gamma, const float* beta,
+                                       const float* ss, long ss_bstride, const float* addend, float* da, int Ca, float* db, int Cb,
+                                       float scale_b, float* dss, float* dgamma, float* dbeta, float* red, float* amax, int B, int HW,
+                                       int G, int silu, float drop_p, uint64_t seed, hipStream_t stream) {
+  if (Ca <= 0 || Cb <= 0) return ADM_EINVAL;
+  const GnSplit sp{da, db, Ca, scale_b};
+  return gn_bwd_add_impl(x, dy, stats, gamma, beta, ss, ss_bstride, addend, nullptr, dss, dgamma, dbeta, red, B, HW, Ca + Cb, G, silu,
+                         drop_p, seed, stream, amax, &sp);
 }
 
 // The batch reduction of d(gamma) / d(beta) for every GroupNorm layer of a backward pass in ONE launch (adm_gn_bwd / adm_gn_bwd_add

@@ -9,6 +9,7 @@ Each Function's backward is hand-written HIP as well -- autograd is only the tap
 """
 from __future__ import annotations
 
+import ctypes
 import itertools
 import os
 import weakref
@@ -1344,6 +1345,111 @@ def group_norm_act_fork(x, gamma, beta, scale_shift=None, *, silu=True, drop_p=0
     if a is not None:
         xo._adm_amax = a             # (xo is x: the skip / residual branch keeps its bound; an input that is returned does not keep attributes)
     return y, xo
+
+
+# A decoder block's input is z = cat(x, scale * skip), and the first thing the block does is norm0.fork(z).  The GroupNorm kernels sit
+# on both sides of that copy with one thread per channel quad, so they pick a source (forward) or destination (backward) per thread:
+# adm_gn_fwd_cat_amax reads the two halves in its moments pass and writes z (the 1x1 skip conv and its weight gradient still read it) as
+# a side output, adm_gn_bwd_add_cat_amax writes the two gradient halves in place of dz.  Against concat_channels + group_norm_act_fork
+# that is one read of z less forward, one write and one read of dz less backward, and two launches less; the results are bit-identical.
+# ADM_GN_CONCAT=0 keeps the two-step path.
+GN_CONCAT = os.environ.get("ADM_GN_CONCAT", "1") != "0"
+
+
+class _GroupNormActCat(torch.autograd.Function):
+    """(a, b) -> (act(norm(z)), z) with z = cat(a, scale_b * b): _Concat + _GroupNormAct(fork=True) without the copy passes."""
+
+    @staticmethod
+    def forward(ctx, a, b, scale_b, gamma, beta, silu, groups, eps, want_amax):
+        a, b = _chk(a, "a"), _chk(b, "b")
+        B, H, W, ca = a.shape
+        cb = b.shape[-1]
+        C, HW = ca + cb, H * W
+        G = groups if groups else min(32, C // 4)
+        g, bt = _chk(gamma.detach(), "gamma"), _chk(beta.detach(), "beta")
+        S = hip.lib().adm_gn_splits(HW, C)
+        z = _new((B, H, W, C), a)
+        y = _like(z)
+        stats = _new((B, G, 2), a)
+        ws = _new((B * S * G * 2,), a, torch.float64)
+        slot_z = _amax_slot(a) if (_fp16_format() and H3_GEMM) else None      # as _Concat: the 1x1 skip conv reads z
+        slot_y = _amax_slot(a) if want_amax else None                        # as _GroupNormAct: conv0 reads y
+        # (the `gn` record keeps its minimal-bytes convention, one read and one write of the map: the z store is not counted)
+        with _Prof("gn", 8.0 * z.numel(), f"gn-fwd-cat B={B} HW={HW} C={ca}+{cb} drop=0 (TB/s)"):
+            call("adm_gn_fwd_cat_amax", ptr(a), ca, ptr(b), cb, float(scale_b), ptr(z), ptr(slot_z), ptr(stats), ptr(ws), ptr(g), ptr(bt),
+                 None, 0, ptr(y), ptr(slot_y), B, HW, G, float(eps), int(silu), 0.0, 0)
+        if slot_z is not None:
+            z._adm_amax = slot_z
+        if slot_y is not None:
+            y._adm_amax = slot_y
+        ctx.save_for_backward(z, gamma, beta, stats)
+        ctx.meta = (G, S, silu, ca, cb, scale_b)
+        _mark_uses(ctx, (3, gamma), (4, beta))
+        return y, z
+
+    @staticmethod
+    def backward(ctx, dy, dz):
+        z, gamma, beta, stats = ctx.saved_tensors
+        G, S, silu, ca, cb, scale_b = ctx.meta
+        B, H, W, C = z.shape
+        HW = H * W
+        da, db = _new((B, H, W, ca), z), _new((B, H, W, cb), z)
+        if dy is None:    # only z was used: what is left is _Concat.backward
+            dz = _chk(dz, "dz")
+            call("adm_split2", ptr(dz), ptr(da), ca, ptr(db), cb, B * HW, float(scale_b))
+            bound = _get_amax(dz)
+            if bound is not None:
+                _reg_amax(da, bound)
+                if abs(scale_b) <= 1.0:
+                    _reg_amax(db, bound)
+            return da, db, None, None, None, None, None, None, None
+        dy = _chk(dy, "dy")
+        add = None if dz is None else _chk(dz, "residual gradient")
+        sg, sb = _direct_grad(gamma), _direct_grad(beta)
+        direct = sg is not None and sb is not None
+        dgamma = sg if direct else torch.zeros_like(gamma)
+        dbeta = sb if direct else torch.zeros_like(beta)
+        red = _new((B * S * C * 2 + B * C * 2 + B * G * 2,), z)
+        defer = direct and DEFER_UNPACK and not DETERMINISTIC      # the batch reduction joins the end-of-backward table launch
+        if defer:
+            _begin_defer()
+        slot_a = _amax_slot(z) if _fp16_format() else None      # max |dz|: bounds da, and db where |scale_b| <= 1 (as _Concat.backward)
+        with _Prof("gn", (12.0 if add is None else 16.0) * z.numel(), f"gn-bwd-cat B={B} HW={HW} C={ca}+{cb} drop=0 (TB/s)"):
+            call("adm_gn_bwd_add_cat_amax", ptr(z), ptr(dy), ptr(stats), ptr(gamma.detach()), ptr(beta.detach()), None, 0, ptr(add),
+                 ptr(da), ca, ptr(db), cb, float(scale_b), None, None if defer else ptr(dgamma), None if defer else ptr(dbeta), ptr(red),
+                 ptr(slot_a), B, HW, G, int(silu), 0.0, 0)
+        _reg_amax(da, slot_a)
+        if abs(scale_b) <= 1.0:
+            _reg_amax(db, slot_a)
+        if defer:
+            _defer_gn_param(red, B * S * C * 2, None, 0, dgamma, dbeta, B, C)
+        if direct:
+            _notify(gamma); _notify(beta)
+            return da, db, None, None, None, None, None, None, None
+        return da, db, None, dgamma, dbeta, None, None, None, None
+
+
+def _gn_cat_ok(a, b, groups) -> bool:
+    """The fused concat form applies: f32 NHWC tensors on the GPU, whole channel quads on both sides, a shape the GroupNorm kernels take."""
+    if not (GN_CONCAT and a.is_cuda and b.is_cuda and a.dim() == 4 and a.shape[:-1] == b.shape[:-1] and a.dtype == _f32 and b.dtype == _f32):
+        return False
+    if bf16_storage():
+        return False
+    ca, cb = a.shape[-1], b.shape[-1]
+    C = ca + cb
+    if ca <= 0 or cb <= 0 or ca % 4 or cb % 4:
+        return False
+    plan = (ctypes.c_int * 5)()
+    return hip.lib().adm_gn_plan(a.shape[1] * a.shape[2], C, groups if groups else min(32, C // 4), plan) == 0
+
+
+def group_norm_act_cat(a, b, scale_b, gamma, beta, *, silu=True, groups=0, eps=1e-5, to_conv=False, bound=False):
+    """(group_norm_act(z), z) for z = cat(a, scale_b * b) along the channels: concat_channels + group_norm_act_fork as one op (see
+    GN_CONCAT above); the two-step path where the fused kernels do not apply."""
+    if not _gn_cat_ok(a, b, groups):
+        z = concat_channels(a, b, scale_b)
+        return group_norm_act_fork(z, gamma, beta, None, silu=silu, groups=groups, eps=eps, to_conv=to_conv, bound=bound)
+    return _GroupNormActCat.apply(a, b, float(scale_b), gamma, beta, bool(silu), int(groups), float(eps), _want_amax(to_conv or bound))
 
 
 # ------------------------------------------------------------------------------------------------

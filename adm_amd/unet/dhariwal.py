@@ -104,6 +104,11 @@ class GroupNorm(nn.Module):
         backward kernel (ops.group_norm_act_fork).  bound: also leave max |norm(x)| for a conv further down (ops.group_norm_act)."""
         return ops.group_norm_act_fork(x, self.weight, self.bias, None, silu=silu, to_conv=to_conv, bound=bound)
 
+    def fork_cat(self, x, skip, ratio=1.0, silu=False, to_conv=False, bound=False):
+        """fork(z) for z = cat(x, ratio * skip), which comes back as the second result: the concatenation is written by the GroupNorm
+        kernel that reads its halves (ops.group_norm_act_cat)."""
+        return ops.group_norm_act_cat(x, skip, ratio, self.weight, self.bias, silu=silu, to_conv=to_conv, bound=bound)
+
 
 _AFFINE_GROUPS = weakref.WeakKeyDictionary()      # DhariwalUNet -> (ops.AffineGroup over its blocks' `affine` Linears, the blocks)
 
@@ -134,10 +139,14 @@ class UNetBlock(nn.Module):
             self.qkv = Conv2d(out_channels, out_channels * 3, 1, qkv=True, **(init_attn if init_attn is not None else init))
             self.proj = Conv2d(out_channels, out_channels, 1, **init_zero)
 
-    def forward(self, x, emb, ss=None):
-        """ss: this block's scale/shift when the caller computed all blocks' `affine` Linears as one GEMM (ops.affine_group)."""
+    def forward(self, x, emb, ss=None, cat=None):
+        """ss: this block's scale/shift when the caller computed all blocks' `affine` Linears as one GEMM (ops.affine_group).
+        cat = (skip, ratio): the block's input is cat(x, ratio * skip) (a decoder block)."""
         # (to_conv: these normalised tensors go straight into a conv -- conv0 resamples first when it down-samples)
-        n0, x = self.norm0.fork(x, silu=True, to_conv=not self.conv0.down, bound=True)    # x feeds the normalised branch AND the residual / skip branch
+        if cat is not None:
+            n0, x = self.norm0.fork_cat(x, cat[0], cat[1], silu=True, to_conv=not self.conv0.down, bound=True)
+        else:
+            n0, x = self.norm0.fork(x, silu=True, to_conv=not self.conv0.down, bound=True)    # x feeds the normalised branch AND the residual / skip branch
         h = self.conv0(n0)
         p = self.dropout if self.training else 0.0
         h = self.norm1(h, self.affine(emb) if ss is None else ss, silu=True, drop_p=p, to_conv=True)
@@ -268,10 +277,10 @@ class DhariwalUNet(nn.Module):
         stack = list(skips)
         ratios = list(ratios) if ratios is not None else None
         for block in dec.values():
-            if x.shape[-1] != block.in_channels:
-                r = ratios.pop() if ratios is not None else 1.0
-                x = ops.concat_channels(x, stack.pop(), r)
-            x = block(x, emb, None if ss is None else ss[block])
+            cat = None
+            if x.shape[-1] != block.in_channels:      # the block's norm0 reads the two halves and writes the concatenation (fork_cat)
+                cat = (stack.pop(), ratios.pop() if ratios is not None else 1.0)
+            x = block(x, emb, None if ss is None else ss[block], cat)
         return out_conv(out_norm(x, silu=True, to_conv=True))
 
     def _scale_shifts(self, emb):

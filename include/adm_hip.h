@@ -337,6 +337,19 @@ int adm_gn_bwd_add_amax(const float* x, const float* dy, const float* stats, con
                         const float* ss, long ss_bstride, const float* addend, float* dx, float* dss, float* dgamma, float* dbeta,
                         float* red, float* amax, int B, int HW, int C, int G, int silu, float drop_p, uint64_t seed,
                         hipStream_t stream);
+/* The concat forms, for a block whose input is z = (a | scale_b * b) along the channels (adm_concat2: a[M][Ca], b[M][Cb], M = B HW,
+ * Ca and Cb multiples of 4, C = Ca + Cb): the GroupNorm kernels sit on both sides of that copy and pick a source / destination per thread.
+ * adm_gn_fwd_cat_amax = adm_concat2(a, b -> z, amax_z) + adm_gn_fwd_amax(z -> y, amax) without the copy pass: the moments pass (the one
+ * launch of a small map) reads a and b in place of z and writes z and its bound.  adm_gn_bwd_add_cat_amax = adm_gn_bwd_add_amax(x = z ->
+ * dz, amax) + adm_split2(dz -> da, db) without dz: the dx pass stores da = dz[:, :Ca] and db = scale_b * dz[:, Ca:]; amax bounds |dz|
+ * (so |da|, and |db| when |scale_b| <= 1).  amax_z and amax may be NULL.  Results are bit-identical to the two-call forms. */
+int adm_gn_fwd_cat_amax(const float* a, int Ca, const float* b, int Cb, float scale_b, float* z, float* amax_z, float* stats, double* ws,
+                        const float* gamma, const float* beta, const float* ss, long ss_bstride, float* y, float* amax, int B, int HW,
+                        int G, float eps, int silu, float drop_p, uint64_t seed, hipStream_t stream);
+int adm_gn_bwd_add_cat_amax(const float* x, const float* dy, const float* stats, const float* gamma, const float* beta, const float* ss,
+                            long ss_bstride, const float* addend, float* da, int Ca, float* db, int Cb, float scale_b, float* dss,
+                            float* dgamma, float* dbeta, float* red, float* amax, int B, int HW, int G, int silu, float drop_p,
+                            uint64_t seed, hipStream_t stream);
 
 /* ---------------- KL autoencoder (first stage) helpers ---------------------------------------- */
 
