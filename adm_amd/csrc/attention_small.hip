@@ -16,6 +16,12 @@ namespace {
 
 // ================================================================================================ generic MHA
 // q[b][i][h*D + d] with row stride ldq (likewise k, v, o, dO); one thread per query (fwd, dq) or per key (dk, dv).
+// The logit s_ij = sum_d (scale q_id) k_jd is taken by the SAME chain of fmaf, d ascending, in all three kernels, so the backward
+// recomputes the forward's s bit for bit and p = exp(s - max - log l) sums to one over a row.  Written as s += q[d] * k[d], the
+// compiler fused a different number of leading terms in each kernel (gfx950 assembly at D = 16: v_fma / v_fmac for the first 4 terms in
+// the forward, for the first 8 in the two backward kernels, v_pk_mul_f32 + v_add_f32 for the rest), so the key-major kernel's s
+// differed from the forward's by an ulp of s: with logits of a few hundred (RelationNet has no 1 / sqrt(d)) that is a relative error
+// of 3e-5 in every p of dv and dk.
 template <int D>
 __global__ __launch_bounds__(64) void mha_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                      const float* __restrict__ v, float* __restrict__ o, float* __restrict__ lse,
@@ -46,7 +52,7 @@ __global__ __launch_bounds__(64) void mha_fwd_kernel(const float* __restrict__ q
     for (int j = 0; j < jn; ++j) {
       float s = 0.f;
 #pragma unroll
-      for (int d = 0; d < D; ++d) s += qv[d] * Ks[j][d];
+      for (int d = 0; d < D; ++d) s = fmaf(qv[d], Ks[j][d], s);      // (the one rounding sequence of all three kernels: see above)
       const float mn = fmaxf(m, s);
       const float corr = __expf(m - mn), p = __expf(s - mn);
       l = l * corr + p;
@@ -60,7 +66,8 @@ __global__ __launch_bounds__(64) void mha_fwd_kernel(const float* __restrict__ q
     float* op = o + ((long)b * Lq + i) * ldo + h * D;
 #pragma unroll
     for (int d = 0; d < D; ++d) op[d] = acc[d] * inv;
-    if (lse) lse[(long)bh * Lq + i] = m + __logf(l);
+    // (m, log l) apart: their sum would round a row maximum of a few hundred to 3e-5, a relative error of every p the backward takes
+    if (lse) { lse[2 * ((long)bh * Lq + i)] = m; lse[2 * ((long)bh * Lq + i) + 1] = __logf(l); }
   }
 }
 
@@ -85,7 +92,7 @@ __global__ __launch_bounds__(64) void mha_bwd_dq_kernel(const float* __restrict_
     dl += dov[d] * o[row * ldo + h * D + d];
     acc[d] = 0.f;
   }
-  const float ls = act ? lse[(long)bh * Lq + i] : 0.f;
+  const float lm = act ? lse[2 * ((long)bh * Lq + i)] : 0.f, ll = act ? lse[2 * ((long)bh * Lq + i) + 1] : 0.f;
   for (int j0 = 0; j0 < Lk; j0 += 64) {
     __syncthreads();
     for (int e = threadIdx.x; e < 64 * (D / 4); e += 64) {
@@ -103,8 +110,8 @@ __global__ __launch_bounds__(64) void mha_bwd_dq_kernel(const float* __restrict_
     for (int j = 0; j < jn; ++j) {
       float s = 0.f, dp = 0.f;
 #pragma unroll
-      for (int d = 0; d < D; ++d) { s += qv[d] * Ks[j][d]; dp += dov[d] * Vs[j][d]; }
-      const float ds = __expf(s - ls) * (dp - dl);
+      for (int d = 0; d < D; ++d) { s = fmaf(qv[d], Ks[j][d], s); dp += dov[d] * Vs[j][d]; }
+      const float ds = __expf((s - lm) - ll) * (dp - dl);
 #pragma unroll
       for (int d = 0; d < D; ++d) acc[d] += ds * Ks[j][d];
     }
@@ -125,7 +132,7 @@ __global__ __launch_bounds__(64) void mha_bwd_dkv_kernel(const float* __restrict
                                                          float* __restrict__ dk, float* __restrict__ dv, int Lq, int Lk, int H,
                                                          int ldq, int ldk, int ldv, int ldo, int lddk, int lddv, float scale) {
   __shared__ __attribute__((aligned(16))) float Qs[64][D], Os[64][D];
-  __shared__ float Ls[64], Ds[64];
+  __shared__ float Lm[64], Ll[64], Ds[64];
   const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
   const int j = blockIdx.y * 64 + threadIdx.x;
   const bool act = j < Lk;
@@ -150,7 +157,8 @@ __global__ __launch_bounds__(64) void mha_bwd_dkv_kernel(const float* __restrict
       *reinterpret_cast<f32x4*>(&Os[i][c4 * 4]) = ov;
     }
     if (i0 + (int)threadIdx.x < Lq) {
-      Ls[threadIdx.x] = lse[(long)bh * Lq + i0 + threadIdx.x];
+      Lm[threadIdx.x] = lse[2 * ((long)bh * Lq + i0 + threadIdx.x)];
+      Ll[threadIdx.x] = lse[2 * ((long)bh * Lq + i0 + threadIdx.x) + 1];
       Ds[threadIdx.x] = delta[(long)bh * Lq + i0 + threadIdx.x];
     }
     __syncthreads();
@@ -158,8 +166,8 @@ __global__ __launch_bounds__(64) void mha_bwd_dkv_kernel(const float* __restrict
     for (int i = 0; i < in; ++i) {
       float s = 0.f, dp = 0.f;
 #pragma unroll
-      for (int d = 0; d < D; ++d) { s += Qs[i][d] * kv[d]; dp += Os[i][d] * vv[d]; }
-      const float p = __expf(s - Ls[i]);
+      for (int d = 0; d < D; ++d) { s = fmaf(Qs[i][d], kv[d], s); dp += Os[i][d] * vv[d]; }
+      const float p = __expf((s - Lm[i]) - Ll[i]);
       const float ds = p * (dp - Ds[i]);
 #pragma unroll
       for (int d = 0; d < D; ++d) { av[d] += p * Os[i][d]; ak[d] += ds * Qs[i][d]; }       // Qs already carries `scale`
@@ -426,7 +434,8 @@ inline bool mha_ok(int B, int Lq, int Lk, int H, int D, int a, int b, int c, int
 }  // namespace
 
 // softmax(scale * q k^T) v per (image, head): q[B][Lq][ldq], k[B][Lk][ldk], v[B][Lk][ldv] -> o[B][Lq][ldo]; head h uses
-// columns [h*D, (h+1)*D) of each row.  lse[B*H][Lq] (may be NULL when no backward follows).  D in {4, 8, 16, 32, 64} (4 / 8 occur only in reduced-width test models).
+// columns [h*D, (h+1)*D) of each row.  lse[B*H][Lq][2] = (row maximum, log of the sum of exp(s - maximum)): the softmax statistics
+// for adm_mha_bwd (may be NULL when no backward follows).  D in {4, 8, 16, 32, 64} (4 / 8 occur only in reduced-width test models).
 extern "C" int adm_mha_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int Lq, int Lk, int H,
                            int D, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t stream) {
   if (!q || !k || !v || !o || !mha_ok(B, Lq, Lk, H, D, ldq, ldk, ldv, ldo)) return ADM_EINVAL;

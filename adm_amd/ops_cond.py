@@ -340,7 +340,7 @@ class _MHA(torch.autograd.Function):
         Lk = k.shape[1]
         D = C // heads
         o = _like(q)
-        lse = _new((B * heads, Lq), q)
+        lse = _new((B * heads, Lq, 2), q)
         call("adm_mha_fwd", ptr(q), ptr(k), ptr(v), ptr(o), ptr(lse), B, Lq, Lk, heads, D, C, C, C, C, float(scale))
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.meta = (heads, scale)
@@ -354,7 +354,7 @@ class _MHA(torch.autograd.Function):
         B, Lq, C = q.shape
         Lk = k.shape[1]
         dq, dk, dv = _like(q), _like(k), _like(v)
-        delta = _like(lse)
+        delta = _new((B * heads, Lq), q)
         call("adm_mha_bwd", ptr(q), ptr(k), ptr(v), ptr(o), ptr(do), ptr(lse), ptr(dq), ptr(dk), ptr(dv), ptr(delta), B, Lq, Lk,
              heads, C // heads, C, C, C, C, C, C, C, float(scale))
         return dq, dk, dv, None, None
@@ -373,7 +373,7 @@ class _SelfAttnPacked(torch.autograd.Function):
         B, L, C3 = qkv.shape
         C = C3 // 3
         o = _new((B, L, C), qkv)
-        lse = _new((B * heads, L), qkv)
+        lse = _new((B * heads, L, 2), qkv)
         base = qkv.data_ptr()
         P = hip.c_void_p
         call("adm_mha_fwd", P(base), P(base + 4 * C), P(base + 8 * C), ptr(o), ptr(lse), B, L, L, heads, C // heads, C3, C3, C3, C,
@@ -390,7 +390,7 @@ class _SelfAttnPacked(torch.autograd.Function):
         B, L, C3 = qkv.shape
         C = C3 // 3
         dqkv = _like(qkv)
-        delta = _like(lse)
+        delta = _new((B * heads, L), qkv)
         base, dbase = qkv.data_ptr(), dqkv.data_ptr()
         P = hip.c_void_p
         call("adm_mha_bwd", P(base), P(base + 4 * C), P(base + 8 * C), ptr(o), ptr(do), ptr(lse), P(dbase), P(dbase + 4 * C),

@@ -609,7 +609,8 @@ int adm_spatial_att_big_bwd(const float* att, int ldatt, const float* qk, const 
 
 /* softmax(scale q k^T) v per (image, head) with separate query / key lengths; head h = columns [h*D, (h+1)*D) of rows with
  * strides ldq / ldk / ldv / ldo; D in {4, 8, 16, 32, 64}.  RelationNet's windowed cross-attention (cond_unet_sd.py:221-231,
- * scale 1) and the bottleneck Attention (:532-554, scale 32^-0.5).  lse [B*H][Lq]; delta = workspace [B*H][Lq]. */
+ * scale 1) and the bottleneck Attention (:532-554, scale 32^-0.5).  lse [B*H][Lq][2] = (row maximum,
+ * log sum exp(s - maximum)), kept apart so that a maximum of a few hundred does not round the sum; delta = workspace [B*H][Lq]. */
 int adm_mha_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int Lq, int Lk, int H, int D, int ldq,
                 int ldk, int ldv, int ldo, float scale, hipStream_t stream);
 int adm_mha_bwd(const float* q, const float* k, const float* v, const float* o, const float* dO, const float* lse, float* dq,

@@ -1,4 +1,6 @@
-"""fp64 references of the conv, attention and GroupNorm operators, for the accuracy tests (a plain helper like parity.py, not a conftest).
+"""fp64 references of the conv, attention and GroupNorm operators and of the SR denoiser's own family (weight standardisation, channel
+LayerNorm, BatchNorm, bilinear resize, the generic multi-head and the linear attention, SpatialAtt, activations, Fourier features,
+col2im), for the accuracy tests (a plain helper like parity.py, not a conftest).
 
 Layouts are the kernels': activations NHWC [B, H, W, C], weights OIHW [Co, Ci, k, k] (or [Co, Ci] for a Linear), attention qkv
 [B, L, heads * 192] with each head's 192 channels packed as (q[64] | k[64] | v[64]) and its output [B, L, heads * 64].
@@ -149,6 +151,295 @@ def group_norm(x, gamma, beta, ss, *, groups, eps, silu, keep=None, addend=None,
         m = torch.cat([(du * zd).abs().sum(dim=(1, 2)), du.abs().sum(dim=(1, 2))], dim=1)        # [B, 2C]
         out["dss"] = (g[4], m if ss.shape[0] == B else m.sum(dim=0, keepdim=True))
     return out
+
+
+# ------------------------------------------------------------------------------------------------ the SR denoiser's family
+def _d(t, like=None):
+    return t.detach().to(device=t.device if like is None else like.device, dtype=_f64)
+
+
+def weight_std(w, eps=1e-5, dy=None):
+    """{"y": (ref, mag)} and, given dy, "dw" of ops_cond.weight_standardize: per row o of w [O, ...] (K values),
+    y = (w - mean_o) rstd_o, rstd = (biased var + eps)^-1/2.  mag: |y|;  dw = rstd (dy - mean(dy) - y mean(dy y)) -> rstd (|dy| +
+    mean |dy| + |y| mean |dy y|)."""
+    w = _d(w)
+    r = w.reshape(w.shape[0], -1)
+    mean = r.mean(dim=1, keepdim=True)
+    var = (r - mean).square().mean(dim=1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    y = (r - mean) * rstd
+    out = {"y": (y.reshape(w.shape), y.abs().reshape(w.shape))}
+    if dy is not None:
+        g = _d(dy, w).reshape(r.shape)
+        m = lambda t: t.mean(dim=1, keepdim=True)
+        dw = rstd * (g - m(g) - y * m(g * y))
+        dm = rstd * (g.abs() + m(g.abs()) + y.abs() * m((g * y).abs()))
+        out["dw"] = (dw.reshape(w.shape), dm.reshape(w.shape))
+    return out
+
+
+def layer_norm_c(x, g, eps=1e-5, dy=None):
+    """{"y"} and, given dy, "dx", "dg" of ops_cond.layer_norm_c: per pixel of x [..., C], y = (x - mean_c) rstd g (gain only, biased
+    variance).  mag: |y|; dx = rstd (g dy - mean(g dy) - xhat mean(g dy xhat)) -> the same sum over |terms|; dg = sum_pixels dy xhat
+    -> sum |dy xhat|."""
+    x = _d(x)
+    C = x.shape[-1]
+    g = _d(g, x).reshape(C)
+    mean = x.mean(dim=-1, keepdim=True)
+    var = (x - mean).square().mean(dim=-1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    xh = (x - mean) * rstd
+    y = xh * g
+    out = {"y": (y, y.abs())}
+    if dy is not None:
+        d = _d(dy, x)
+        gd = d * g
+        m = lambda t: t.mean(dim=-1, keepdim=True)
+        out["dx"] = (rstd * (gd - m(gd) - xh * m(gd * xh)), rstd * (gd.abs() + m(gd.abs()) + xh.abs() * m((gd * xh).abs())))
+        out["dg"] = ((d * xh).reshape(-1, C).sum(dim=0), (d * xh).abs().reshape(-1, C).sum(dim=0))
+    return out
+
+
+def batch_norm(x, gamma, beta, run_mean, run_var, *, training, momentum, eps, dy=None):
+    """{"y", "running_mean", "running_var"} and, given dy, "dx", "dgamma", "dbeta" of ops_cond.batch_norm on x [..., C] (M rows).
+    training: batch mean and biased variance normalise, the running statistics move by `momentum` towards the batch mean and the
+    UNBIASED variance; eval: the running statistics normalise and stay, and they are constants of the backward (dx = gamma rstd dy).
+    mag: y -> |xhat gamma| + |beta|; running_mean -> (1 - m) |run_mean| + m mean |x|; running_var -> itself (a sum of squares);
+    dx = gamma rstd (dy - mean(dy) - xhat mean(dy xhat)) -> the sum over |terms|; dgamma = sum dy xhat, dbeta = sum dy -> sums of
+    |summands|."""
+    x = _d(x)
+    C = x.shape[-1]
+    r = x.reshape(-1, C)
+    M = r.shape[0]
+    gamma, beta, rm, rv = (_d(t, x).reshape(C) for t in (gamma, beta, run_mean, run_var))
+    if training:
+        mean = r.mean(dim=0)
+        var = (r - mean).square().mean(dim=0)
+        new_rm = (1 - momentum) * rm + momentum * mean
+        new_rv = (1 - momentum) * rv + momentum * var * (M / max(M - 1, 1))
+        rm_mag = (1 - momentum) * rm.abs() + momentum * r.abs().mean(dim=0)
+    else:
+        mean, var, new_rm, new_rv, rm_mag = rm, rv, rm, rv, rm.abs()
+    rstd = 1.0 / torch.sqrt(var + eps)
+    xh = (r - mean) * rstd
+    y = xh * gamma + beta
+    out = {"y": (y.reshape(x.shape), ((xh * gamma).abs() + beta.abs()).reshape(x.shape)),
+           "running_mean": (new_rm, rm_mag), "running_var": (new_rv, new_rv.abs())}
+    if dy is not None:
+        d = _d(dy, x).reshape(-1, C)
+        m = lambda t: t.mean(dim=0, keepdim=True)
+        if training:
+            dx = gamma * rstd * (d - m(d) - xh * m(d * xh))
+            dm = gamma.abs() * rstd * (d.abs() + m(d.abs()) + xh.abs() * m((d * xh).abs()))
+        else:
+            dx = gamma * rstd * d
+            dm = dx.abs()
+        out["dx"] = (dx.reshape(x.shape), dm.reshape(x.shape))
+        out["dgamma"] = ((d * xh).sum(dim=0), (d * xh).abs().sum(dim=0))
+        out["dbeta"] = (d.sum(dim=0), d.abs().sum(dim=0))
+    return out
+
+
+def bilinear_matrix(n_in, n_out, align_corners, device=None):
+    """[n_out, n_in] fp64 interpolation matrix of one axis from explicit source coordinates: align_corners: s = d (in - 1) / (out - 1)
+    (0 for out = 1); else s = max(0, (d + 1/2) in / out - 1/2); i0 = floor(s), i1 = min(i0 + 1, in - 1), weights 1 - (s - i0), s - i0."""
+    d = torch.arange(n_out, dtype=_f64, device=device)
+    if align_corners:
+        s = d * ((n_in - 1) / (n_out - 1)) if n_out > 1 else torch.zeros_like(d)
+    else:
+        s = ((d + 0.5) * (n_in / n_out) - 0.5).clamp_min(0.0)
+    i0 = s.floor().clamp_max(n_in - 1)
+    i1 = (i0 + 1).clamp_max(n_in - 1)
+    lam = s - i0
+    R = torch.zeros(n_out, n_in, dtype=_f64, device=device)
+    rows = torch.arange(n_out, device=device)
+    R.index_put_((rows, i0.long()), 1.0 - lam, accumulate=True)
+    R.index_put_((rows, i1.long()), lam, accumulate=True)
+    return R
+
+
+def bilinear(x, Ho, Wo, align_corners, dy=None):
+    """{"y"} and, given dy, "dx" of ops_cond.bilinear on NHWC x: y = Ry x Rx^T with the two axis matrices of bilinear_matrix, dx =
+    Ry^T dy Rx.  The weights are non-negative: mag is the same map applied to |x| (|dy|)."""
+    x = _d(x)
+    Ry = bilinear_matrix(x.shape[1], Ho, align_corners, x.device)
+    Rx = bilinear_matrix(x.shape[2], Wo, align_corners, x.device)
+    f = lambda t: torch.einsum("oh,bhwc,pw->bopc", Ry, t, Rx)
+    out = {"y": (f(x), f(x.abs()))}
+    if dy is not None:
+        d = _d(dy, x)
+        b = lambda t: torch.einsum("oh,bopc,pw->bhwc", Ry, t, Rx)
+        out["dx"] = (b(d), b(d.abs()))
+    return out
+
+
+def mha(q, k, v, heads, scale, dout=None):
+    """{"out": (ref, mag)} and, given dout, "dq", "dk", "dv" of ops_cond.mha: softmax(scale q k^T) v per head; q [B, Lq, heads D],
+    k, v [B, Lk, heads D], head h in columns [h D, (h + 1) D).  mag as in attention(): the softmax weights P kept, every product on
+    |operands|."""
+    B, Lq, C = q.shape
+    Lk, D = k.shape[1], C // heads
+    hd = lambda t, L: _d(t, q).reshape(B, L, heads, D).permute(0, 2, 1, 3)
+    un = lambda t, L: t.permute(0, 2, 1, 3).reshape(B, L, C)
+    qq, kk, vv = hd(q, Lq), hd(k, Lk), hd(v, Lk)
+    P = torch.softmax(torch.matmul(qq, kk.transpose(-1, -2)) * scale, dim=-1)
+    res = {"out": (un(torch.matmul(P, vv), Lq), un(torch.matmul(P, vv.abs()), Lq))}
+    if dout is None:
+        return res
+    do = hd(dout, Lq)
+    dP = torch.matmul(do, vv.transpose(-1, -2))
+    dS = P * (dP - (dP * P).sum(-1, keepdim=True))
+    dPm = torch.matmul(do.abs(), vv.abs().transpose(-1, -2))
+    dSm = P * (dPm + (dPm * P).sum(-1, keepdim=True))
+    res["dq"] = (un(torch.matmul(dS, kk) * scale, Lq), un(torch.matmul(dSm, kk.abs()) * abs(scale), Lq))
+    res["dk"] = (un(torch.matmul(dS.transpose(-1, -2), qq) * scale, Lk), un(torch.matmul(dSm.transpose(-1, -2), qq.abs()) * abs(scale), Lk))
+    res["dv"] = (un(torch.matmul(P.transpose(-1, -2), do), Lk), un(torch.matmul(P.transpose(-1, -2), do.abs()), Lk))
+    return res
+
+
+def mha_packed(qkv, heads, scale, dout=None):
+    """mha() on the packed layout of ops_cond.self_attention_packed: qkv [B, L, 3 C] = (q | k | v), row stride 3 C; {"out"} and,
+    given dout, "dqkv" in the same layout."""
+    C = qkv.shape[-1] // 3
+    r = mha(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], heads, scale, dout)
+    res = {"out": r["out"]}
+    if dout is not None:
+        res["dqkv"] = tuple(torch.cat([r[n][i] for n in ("dq", "dk", "dv")], dim=-1) for i in (0, 1))
+    return res
+
+
+def linear_attention(qkv, dout=None, heads=4):
+    """{"out"} and, given dout, "dqkv" of ops_cond.linear_attention on qkv [B, N, 3 heads D] = (q | k | v):
+
+        qs = softmax_d(q) D^-1/2,  ks = softmax_n(k),  ctx[d][e] = sum_n ks[n][d] v[n][e] / N,  out[n][e] = sum_d ctx[d][e] qs[n][d]
+
+    The softmax weights qs, ks (non-negative) stay as they are in mag; every other product is taken on |operands|:
+    dctx = qs^T dout; dqs = dout ctx^T; dq = qs (dqs - sum_d dqs softmax_d(q)) -> qs (|dqs| + sum ...);  dv = ks dctx / N;
+    dks = v dctx^T / N;  dk = ks (dks - sum_n ks dks) -> ks (|dks| + sum_n ks |dks|)."""
+    B, N, C3 = qkv.shape
+    C = C3 // 3
+    D = C // heads
+    t = _d(qkv).reshape(B, N, 3, heads, D).permute(2, 0, 3, 1, 4)                # [3][B][heads][N][D]
+    q, k, v = t[0], t[1], t[2]
+    qsm = torch.softmax(q, dim=-1)
+    qs = qsm * D ** -0.5
+    ks = torch.softmax(k, dim=-2)
+    un = lambda u: u.permute(0, 2, 1, 3).reshape(B, N, C)
+    T = lambda u: u.transpose(-1, -2)
+    ctx, ctxm = torch.matmul(T(ks), v) / N, torch.matmul(T(ks), v.abs()) / N      # [B][heads][D][D]
+    res = {"out": (un(torch.matmul(qs, ctx)), un(torch.matmul(qs, ctxm)))}
+    if dout is None:
+        return res
+    do = _d(dout, qkv).reshape(B, N, heads, D).permute(0, 2, 1, 3)
+    grads = []
+    for mag in (False, True):
+        a = (lambda u: u.abs()) if mag else (lambda u: u)
+        sg = 1.0 if mag else -1.0
+        dctx = torch.matmul(T(qs), a(do))
+        dqs = torch.matmul(a(do), T(ctxm if mag else ctx))
+        dq = qs * (a(dqs) + sg * (a(dqs) * qsm).sum(-1, keepdim=True))
+        dv = torch.matmul(ks, dctx) / N
+        dks = torch.matmul(a(v), T(dctx)) / N
+        dk = ks * (a(dks) + sg * (ks * a(dks)).sum(-2, keepdim=True))
+        grads.append(torch.cat([un(dq), un(dk), un(dv)], dim=-1))
+    res["dqkv"] = tuple(grads)
+    return res
+
+
+def spatial_att_gate(att, qk, h, xres, dy=None):
+    """{"y"} and, given dy, "dh", "datt", "dqk" of ops_cond.spatial_att_gate.  a = channel 0 of att [B, H, W, ld]; qk = (qw, qb, kw,
+    kb); q_i = qw a_i + qb, k_j = kw a_j + kb, P = softmax_j(q_i k_j), av = P a, g = av / (1 + |av|), y = g h + xres.
+    datt is [B, H, W, ld] with channels 1.. zero.  mag keeps P: y -> |g h| + |xres|; dg_i = sum_c dy h -> sum |dy h|;
+    dav = dg / (1 + |av|)^2; dS_ij = P_ij dav_i (a_j - av_i) -> P |dav| (|a_j| + P |a|); dq = dS k, dk = dS^T q,
+    datt = P^T dav + qw dq + kw dk, dqk = (dq . a, sum dq, dk . a, sum dk): each on |terms|."""
+    h = _d(h)
+    B, H, W, C = h.shape
+    HW = H * W
+    a = _d(att, h).reshape(B, HW, -1)[:, :, 0]
+    qw, qb, kw, kb = (float(t) for t in qk.detach().double().reshape(-1))
+    q, k = qw * a + qb, kw * a + kb
+    P = torch.softmax(q[:, :, None] * k[:, None, :], dim=-1)
+    av = torch.matmul(P, a[:, :, None])[:, :, 0]
+    g = av / (1 + av.abs())
+    hh, xr = h.reshape(B, HW, C), _d(xres, h).reshape(B, HW, C)
+    y = g[:, :, None] * hh + xr
+    out = {"y": (y.reshape(h.shape), ((g[:, :, None] * hh).abs() + xr.abs()).reshape(h.shape))}
+    if dy is None:
+        return out
+    d = _d(dy, h).reshape(B, HW, C)
+    out["dh"] = ((g[:, :, None] * d).reshape(h.shape), (g[:, :, None] * d).abs().reshape(h.shape))
+    datt, dqk = [], []
+    for mag in (False, True):
+        f = (lambda u: u.abs()) if mag else (lambda u: u)
+        dg = f(d * hh).sum(-1)
+        dav = dg / (1 + av.abs()).square()
+        if mag:
+            avm = torch.matmul(P, a.abs()[:, :, None])[:, :, 0]
+            dS = P * dav[:, :, None] * (a.abs()[:, None, :] + avm[:, :, None])
+        else:
+            dS = P * dav[:, :, None] * (a[:, None, :] - av[:, :, None])
+        dq = torch.matmul(dS, f(k)[:, :, None])[:, :, 0]
+        dk = torch.matmul(dS.transpose(-1, -2), f(q)[:, :, None])[:, :, 0]
+        da = torch.matmul(P.transpose(-1, -2), dav[:, :, None])[:, :, 0] + (abs(qw) if mag else qw) * dq + (abs(kw) if mag else kw) * dk
+        full = torch.zeros(B, HW, att.shape[-1], dtype=_f64, device=h.device)
+        full[:, :, 0] = da
+        datt.append(full.reshape(att.shape))
+        dqk.append(torch.stack([(dq * f(a)).sum(), dq.sum(), (dk * f(a)).sum(), dk.sum()]))
+    out["datt"], out["dqk"] = tuple(datt), tuple(dqk)
+    return out
+
+
+def recover_keep(y, y0):
+    """The dropout mask a kernel applied, from its output y and the undropped fp64 output y0: an element was dropped where y is 0 and
+    y0 is not (an element whose undropped value is 0 counts as kept: it is 0 either way)."""
+    return ((y.detach().to(y0.device) != 0) | (y0 == 0)).to(_f64)
+
+
+def act(x, kind, keep=None, dy=None):
+    """{"y"} and, given dy, "dx" of ops_cond.relu_dropout / gelu / dropout: y = f(x) keep, dx = dy f'(x) keep; kind "relu", "gelu"
+    (the exact erf form) or "id"; keep = the dropout mask already divided by 1 - p (recover_keep(...) / (1 - p)).  mag: |y|, |dx|."""
+    x = _d(x)
+    if kind == "relu":
+        y, dv = x.clamp_min(0.0), (x > 0).to(_f64)
+    elif kind == "gelu":
+        cdf = 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0)))
+        y, dv = x * cdf, cdf + x * torch.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi)
+    else:
+        assert kind == "id"
+        y, dv = x, torch.ones_like(x)
+    kp = 1.0 if keep is None else _d(keep, x)
+    y = y * kp
+    out = {"y": (y, y.abs())}
+    if dy is not None:
+        dx = _d(dy, x) * dv * kp
+        out["dx"] = (dx, dx.abs())
+    return out
+
+
+def fourier_features(x, W):
+    """{"y"} of ops_cond.fourier_features: [sin(2 pi x_b W_d) | cos(2 pi x_b W_d)], [B, 2 D].  No sums: mag is |y| (its maximum, which
+    errors() divides by, is 1 for all practical inputs)."""
+    p = _d(x).reshape(-1, 1) * _d(W, x).reshape(1, -1) * (2.0 * math.pi)
+    y = torch.cat([torch.sin(p), torch.cos(p)], dim=-1)
+    return {"y": (y, y.abs())}
+
+
+def col2im(col, B, Hin, Win, ks, stride, pad):
+    """{"dx"} of adm_col2im: the adjoint of the strided gather col[b][oy][ox][ky ks + kx][c] = xpad[b][stride oy + ky - pad][stride ox
+    + kx - pad][c] (zero outside the map), i.e. every col entry added to the pixel it was gathered from.  col [B, Ho, Wo, ks ks, C].
+    mag: the same sums over |col|."""
+    col = _d(col)
+    Ho, Wo, C = col.shape[1], col.shape[2], col.shape[-1]
+    Hp, Wp = max(Hin + 2 * pad, stride * (Ho - 1) + ks), max(Win + 2 * pad, stride * (Wo - 1) + ks)
+    res = []
+    for c in (col, col.abs()):
+        c = c.reshape(B, Ho, Wo, ks, ks, C)
+        xp = torch.zeros(B, Hp, Wp, C, dtype=_f64, device=col.device)
+        for ky in range(ks):
+            for kx in range(ks):
+                xp[:, ky:ky + stride * (Ho - 1) + 1:stride, kx:kx + stride * (Wo - 1) + 1:stride, :] += c[:, :, :, ky, kx, :]
+        res.append(xp[:, pad:pad + Hin, pad:pad + Win, :].contiguous())
+    return {"dx": tuple(res)}
 
 
 def errors(got, ref, mag):
