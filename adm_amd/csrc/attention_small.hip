@@ -1,6 +1,6 @@
 // Attention variants of the conditional super-resolution denoiser, forward and backward:
 //
-//   * generic multi-head softmax attention with SEPARATE query / key lengths and head dims 16 / 32 / 64: the windowed
+//   * generic multi-head softmax attention with SEPARATE query / key lengths and head dims 12 ... 96: the windowed
 //     cross-attention of RelationNet (/root/reference/unet/cond_unet_sd.py:221-231: 8 heads of C/8 channels, 16 pooled
 //     condition windows attending to up to 1024 pooled feature windows, NO 1/sqrt(d) factor) and the bottleneck's
 //     Attention (:532-554: 4 heads x 32, q scaled by 32^-0.5, L = 256);
@@ -125,7 +125,11 @@ __global__ __launch_bounds__(64) void mha_bwd_dq_kernel(const float* __restrict_
 }
 
 // dv_j = sum_i p_ij dO_i ;  dk_j = scale * sum_i p_ij (dO_i . v_j - delta_i) q_i
-template <int D>
+// PART 0 writes both, 1 only dv, 2 only dk.  At D = 96 the four D-float arrays of one pass (k, v, dk, dv: 384 floats per thread) do
+// not fit the register file; the compiler spilled to scratch memory and dk / dv came out wrong by 17 % against float64 on the
+// device, while the kernels without scratch were right.  Two passes of three arrays each need none (checked with
+// -Rpass-analysis=kernel-resource-usage: ScratchSize 0); both recompute s by the chain of fmaf the forward used.
+template <int D, int PART>
 __global__ __launch_bounds__(64) void mha_bwd_dkv_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                          const float* __restrict__ v, const float* __restrict__ dO,
                                                          const float* __restrict__ lse, const float* __restrict__ delta,
@@ -137,12 +141,13 @@ __global__ __launch_bounds__(64) void mha_bwd_dkv_kernel(const float* __restrict
   const int j = blockIdx.y * 64 + threadIdx.x;
   const bool act = j < Lk;
   const long row = (long)b * Lk + (act ? j : 0);
-  float kv[D], vv[D], ak[D], av[D];
+  constexpr bool DK = PART != 1, DV = PART != 2;
+  float kv[D], vv[DK ? D : 1], ak[DK ? D : 1], av[DV ? D : 1];
 #pragma unroll
   for (int d = 0; d < D; ++d) {
     kv[d] = k[row * ldk + h * D + d];
-    vv[d] = v[row * ldv + h * D + d];
-    ak[d] = 0.f; av[d] = 0.f;
+    if (DK) { vv[d] = v[row * ldv + h * D + d]; ak[d] = 0.f; }
+    if (DV) av[d] = 0.f;
   }
   for (int i0 = 0; i0 < Lq; i0 += 64) {
     __syncthreads();
@@ -166,16 +171,25 @@ __global__ __launch_bounds__(64) void mha_bwd_dkv_kernel(const float* __restrict
     for (int i = 0; i < in; ++i) {
       float s = 0.f, dp = 0.f;
 #pragma unroll
-      for (int d = 0; d < D; ++d) { s = fmaf(Qs[i][d], kv[d], s); dp += Os[i][d] * vv[d]; }
+      for (int d = 0; d < D; ++d) {
+        s = fmaf(Qs[i][d], kv[d], s);
+        if (DK) dp += Os[i][d] * vv[d];
+      }
       const float p = __expf((s - Lm[i]) - Ll[i]);
       const float ds = p * (dp - Ds[i]);
 #pragma unroll
-      for (int d = 0; d < D; ++d) { av[d] += p * Os[i][d]; ak[d] += ds * Qs[i][d]; }       // Qs already carries `scale`
+      for (int d = 0; d < D; ++d) {
+        if (DV) av[d] += p * Os[i][d];
+        if (DK) ak[d] += ds * Qs[i][d];       // Qs already carries `scale`
+      }
     }
   }
   if (act) {
 #pragma unroll
-    for (int d = 0; d < D; ++d) { dk[row * lddk + h * D + d] = ak[d]; dv[row * lddv + h * D + d] = av[d]; }
+    for (int d = 0; d < D; ++d) {
+      if (DK) dk[row * lddk + h * D + d] = ak[d];
+      if (DV) dv[row * lddv + h * D + d] = av[d];
+    }
   }
 }
 
@@ -422,29 +436,42 @@ int mha_bwd_launch(const float* q, const float* k, const float* v, const float* 
                    int lddk, int lddv, float scale, hipStream_t st) {
   hipLaunchKernelGGL((mha_bwd_dq_kernel<D>), dim3(B * H, (Lq + 63) / 64), dim3(64), 0, st, q, k, v, o, dO, lse, dq, delta, Lq, Lk, H,
                      ldq, ldk, ldv, ldo, lddq, scale);
-  hipLaunchKernelGGL((mha_bwd_dkv_kernel<D>), dim3(B * H, (Lk + 63) / 64), dim3(64), 0, st, q, k, v, dO, lse, delta, dk, dv, Lq, Lk,
-                     H, ldq, ldk, ldv, ldo, lddk, lddv, scale);
+  if constexpr (D <= 64) {
+    hipLaunchKernelGGL((mha_bwd_dkv_kernel<D, 0>), dim3(B * H, (Lk + 63) / 64), dim3(64), 0, st, q, k, v, dO, lse, delta, dk, dv, Lq,
+                       Lk, H, ldq, ldk, ldv, ldo, lddk, lddv, scale);
+  } else {
+    hipLaunchKernelGGL((mha_bwd_dkv_kernel<D, 1>), dim3(B * H, (Lk + 63) / 64), dim3(64), 0, st, q, k, v, dO, lse, delta, dk, dv, Lq,
+                       Lk, H, ldq, ldk, ldv, ldo, lddk, lddv, scale);
+    hipLaunchKernelGGL((mha_bwd_dkv_kernel<D, 2>), dim3(B * H, (Lk + 63) / 64), dim3(64), 0, st, q, k, v, dO, lse, delta, dk, dv, Lq,
+                       Lk, H, ldq, ldk, ldv, ldo, lddk, lddv, scale);
+  }
   ADM_CHECK_LAUNCH();
   return ADM_OK;
 }
+// head dims C / 8 of RelationNet at the widths the configs reach: 128 * {1, 2, 4} -> 16 / 32 / 64 (DIV2K), 96 * {1, 2, 4, 8} -> 12 / 24 /
+// 48 / 96 (in-painting), 32 * {1, 2, 4, 8} and 64 in reduced test models.  Any multiple of 4 would compile (rows are moved as
+// float4); each value is a kernel of its own, with D floats per array in registers, so only these are built.
+inline bool mha_head_dim_ok(int D) {
+  return D == 4 || D == 8 || D == 12 || D == 16 || D == 24 || D == 32 || D == 48 || D == 64 || D == 96;
+}
 inline bool mha_ok(int B, int Lq, int Lk, int H, int D, int a, int b, int c, int d) {
-  return B > 0 && Lq > 0 && Lk > 0 && H > 0 && (D == 4 || D == 8 || D == 16 || D == 32 || D == 64) && !((a | b | c | d) & 3) && a >= H * D && b >= H * D &&
+  return B > 0 && Lq > 0 && Lk > 0 && H > 0 && mha_head_dim_ok(D) && !((a | b | c | d) & 3) && a >= H * D && b >= H * D &&
          c >= H * D && d >= H * D;
 }
 }  // namespace
 
 // softmax(scale * q k^T) v per (image, head): q[B][Lq][ldq], k[B][Lk][ldk], v[B][Lk][ldv] -> o[B][Lq][ldo]; head h uses
 // columns [h*D, (h+1)*D) of each row.  lse[B*H][Lq][2] = (row maximum, log of the sum of exp(s - maximum)): the softmax statistics
-// for adm_mha_bwd (may be NULL when no backward follows).  D in {4, 8, 16, 32, 64} (4 / 8 occur only in reduced-width test models).
+// for adm_mha_bwd (may be NULL when no backward follows).  D in {4, 8, 12, 16, 24, 32, 48, 64, 96} (mha_head_dim_ok).
 extern "C" int adm_mha_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int Lq, int Lk, int H,
                            int D, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t stream) {
   if (!q || !k || !v || !o || !mha_ok(B, Lq, Lk, H, D, ldq, ldk, ldv, ldo)) return ADM_EINVAL;
   if (((uintptr_t)k | (uintptr_t)v) & 15) return ADM_EINVAL;
-  if (D == 4) return mha_fwd_launch<4>(q, k, v, o, lse, B, Lq, Lk, H, ldq, ldk, ldv, ldo, scale, stream);
-  if (D == 8) return mha_fwd_launch<8>(q, k, v, o, lse, B, Lq, Lk, H, ldq, ldk, ldv, ldo, scale, stream);
-  if (D == 16) return mha_fwd_launch<16>(q, k, v, o, lse, B, Lq, Lk, H, ldq, ldk, ldv, ldo, scale, stream);
-  if (D == 32) return mha_fwd_launch<32>(q, k, v, o, lse, B, Lq, Lk, H, ldq, ldk, ldv, ldo, scale, stream);
-  return mha_fwd_launch<64>(q, k, v, o, lse, B, Lq, Lk, H, ldq, ldk, ldv, ldo, scale, stream);
+#define ADM_MHA_FWD(d) if (D == d) return mha_fwd_launch<d>(q, k, v, o, lse, B, Lq, Lk, H, ldq, ldk, ldv, ldo, scale, stream)
+  ADM_MHA_FWD(4); ADM_MHA_FWD(8); ADM_MHA_FWD(12); ADM_MHA_FWD(16); ADM_MHA_FWD(24); ADM_MHA_FWD(32); ADM_MHA_FWD(48); ADM_MHA_FWD(64);
+  ADM_MHA_FWD(96);
+#undef ADM_MHA_FWD
+  return ADM_EINVAL;
 }
 
 // delta = workspace [B*H][Lq]
@@ -455,11 +482,13 @@ extern "C" int adm_mha_bwd(const float* q, const float* k, const float* v, const
     return ADM_EINVAL;
   if (((lddq | lddk | lddv) & 3) || lddq < H * D || lddk < H * D || lddv < H * D) return ADM_EINVAL;
   if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dO) & 15) return ADM_EINVAL;
-  if (D == 4) return mha_bwd_launch<4>(q, k, v, o, dO, lse, dq, dk, dv, delta, B, Lq, Lk, H, ldq, ldk, ldv, ldo, lddq, lddk, lddv, scale, stream);
-  if (D == 8) return mha_bwd_launch<8>(q, k, v, o, dO, lse, dq, dk, dv, delta, B, Lq, Lk, H, ldq, ldk, ldv, ldo, lddq, lddk, lddv, scale, stream);
-  if (D == 16) return mha_bwd_launch<16>(q, k, v, o, dO, lse, dq, dk, dv, delta, B, Lq, Lk, H, ldq, ldk, ldv, ldo, lddq, lddk, lddv, scale, stream);
-  if (D == 32) return mha_bwd_launch<32>(q, k, v, o, dO, lse, dq, dk, dv, delta, B, Lq, Lk, H, ldq, ldk, ldv, ldo, lddq, lddk, lddv, scale, stream);
-  return mha_bwd_launch<64>(q, k, v, o, dO, lse, dq, dk, dv, delta, B, Lq, Lk, H, ldq, ldk, ldv, ldo, lddq, lddk, lddv, scale, stream);
+#define ADM_MHA_BWD(d)                                                                                                           \
+  if (D == d)                                                                                                                    \
+  return mha_bwd_launch<d>(q, k, v, o, dO, lse, dq, dk, dv, delta, B, Lq, Lk, H, ldq, ldk, ldv, ldo, lddq, lddk, lddv, scale, stream)
+  ADM_MHA_BWD(4); ADM_MHA_BWD(8); ADM_MHA_BWD(12); ADM_MHA_BWD(16); ADM_MHA_BWD(24); ADM_MHA_BWD(32); ADM_MHA_BWD(48); ADM_MHA_BWD(64);
+  ADM_MHA_BWD(96);
+#undef ADM_MHA_BWD
+  return ADM_EINVAL;
 }
 
 // workspace floats of the linear attention calls for N pixels per image

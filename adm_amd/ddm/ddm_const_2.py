@@ -132,9 +132,16 @@ class LatentDiffusion(DDPM):
 
     # ------------------------------------------------------------------ sampling
     @torch.no_grad()
-    def sample(self, batch_size=16, up_scale=1, cond=None, mask=None, denoise=True, x_T=None, epsilons=None, latent_hw=None):
-        if mask is not None:
-            raise NotImplementedError("masked (in-painting) sampling is not implemented")
+    def sample(self, batch_size=16, up_scale=1, cond=None, mask=None, denoise=True, x_T=None, epsilons=None, latent_hw=None,
+               cond_image=None):
+        """With ``mask`` (in-painting, [B,1,H,W], keep = 1): the result is mask * (cond + 1) / 2 + (1 - mask) * x_rec
+        (ddm_const_2.py:628-629), the kept pixels taken from the condition IMAGE -- ``cond_image`` if given, else ``cond`` when that is
+        a tensor; a list of encoder features cannot stand for it."""
+        if mask is not None and cond_image is None:
+            if not isinstance(cond, torch.Tensor):
+                raise ValueError("sample(mask=...) composes with the condition image: pass cond_image= when cond is "
+                                 f"{'a list of encoder features' if isinstance(cond, (list, tuple)) else 'None'}")
+            cond_image = cond
         if cond is not None:       # ddm_const_2.py:599-601: the condition sets the batch size
             batch_size = cond[0].shape[0] if isinstance(cond, (list, tuple)) else cond.shape[0]
         down = self.first_stage_model.down_ratio
@@ -153,7 +160,11 @@ class LatentDiffusion(DDPM):
         elif self.scale_by_softsign:
             z = z / (1 - z.abs())
         x_rec = self.first_stage_model.decode(z.to(torch.float32))
-        return torch.clamp((x_rec + 1) * 0.5, min=0., max=1.)
+        x_rec = torch.clamp((x_rec + 1) * 0.5, min=0., max=1.)
+        if mask is not None:
+            from .inpaint_data import inpaint_compose
+            x_rec = inpaint_compose(mask, cond_image, x_rec)
+        return x_rec
 
     @torch.no_grad()
     def sample_fn_s(self, shape, up_scale=1, unnormalize=True, cond=None, denoise=False, x_T=None, epsilons=None):

@@ -193,7 +193,44 @@ def resample_image(img: np.ndarray, down: int, filter: str, device, want_u8: boo
     return sr_batch(pool, rs, z, z, z, z, want_u8)
 
 
-class SRBatchStream:
+def load_u8_array(path: str) -> np.ndarray:
+    """``data.npy``: a uint8 [N,H,W,3] image array."""
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"data.npy: {path} does not exist")
+    arr = np.load(path, allow_pickle=False)
+    if arr.dtype != np.uint8 or arr.ndim != 4:
+        raise ValueError(f"image array must be uint8 [N,H,W,3], got {arr.dtype} {arr.shape}")
+    return arr
+
+
+class PoolStream:
+    """What the batch streams over an ImagePool share: the device generator, the running permutation of the image order and the
+    horizontal-flip draw.  A subclass sets ``self.pool``."""
+
+    def __init__(self, batch, device, seed, flip: bool):
+        self.batch, self.device, self.flip = int(batch), device, bool(flip)
+        self.gen = torch.Generator(device=device).manual_seed(seed)
+        self._order = torch.empty(0, dtype=torch.int64, device=device)      # what is left of the running permutation(s)
+        self._zeros = torch.zeros(self.batch, dtype=torch.int32, device=device)
+
+    def take_indices(self) -> torch.Tensor:
+        """The next ``batch`` image indices (int64): a fresh permutation per epoch, continued across the epoch boundary."""
+        while self._order.numel() < self.batch:          # (sizes are host integers: no synchronisation)
+            self._order = torch.cat([self._order, torch.randperm(self.pool.n, device=self.device, generator=self.gen)])
+        idx, self._order = self._order[:self.batch], self._order[self.batch:]
+        return idx
+
+    def draw_flip(self) -> torch.Tensor:
+        """int32 [B]: p = 0.5 with ``augment_horizontal_flip``, else zeros (no draw is consumed)."""
+        if self.flip:
+            return (torch.rand(self.batch, device=self.device, generator=self.gen) < 0.5).to(torch.int32)
+        return self._zeros
+
+    def __iter__(self):
+        return self
+
+
+class SRBatchStream(PoolStream):
     """Infinite iterator of {'image': [B,3,H,W], 'cond': [B,3,H/down,W/down]} in [-1, 1] on the GPU, keyed as ddm.data.SRDataset
     keys them (data.py:658).
 
@@ -211,23 +248,17 @@ class SRBatchStream:
 
     def __init__(self, data_cfg, batch, image_size, device, seed):
         data_cfg = data_cfg or {}
-        self.batch, self.size, self.device = int(batch), (int(image_size[0]), int(image_size[1])), device
-        self.gen = torch.Generator(device=device).manual_seed(seed)
+        super().__init__(batch, device, seed, bool(data_cfg.get("augment_horizontal_flip", False)))          # data.py:601
+        self.size = (int(image_size[0]), int(image_size[1]))
         self.down = int(data_cfg.get("down") or 4)
         self.filter = data_cfg.get("inter_type") or "bicubic"
-        self.flip = bool(data_cfg.get("augment_horizontal_flip", False))          # data.py:601
         H, W = self.size
         if H % self.down or W % self.down:
             raise ValueError(f"image_size {self.size} is not a multiple of down = {self.down}")
         self.rs = Resampler(self.size, (H // self.down, W // self.down), self.filter, device)
         path, cls = data_cfg.get("npy"), data_cfg.get("class_name")
         if path:
-            if not os.path.exists(path):
-                raise FileNotFoundError(f"data.npy: {path} does not exist")
-            arr = np.load(path, allow_pickle=False)
-            if arr.dtype != np.uint8 or arr.ndim != 4:
-                raise ValueError(f"image array must be uint8 [N,H,W,3], got {arr.dtype} {arr.shape}")
-            self.pool = ImagePool.from_uniform(torch.from_numpy(np.ascontiguousarray(arr)).to(device), self.size)
+            self.pool = ImagePool.from_uniform(torch.from_numpy(np.ascontiguousarray(load_u8_array(path))).to(device), self.size)
         elif cls in ("ddm.data.SRDataset", "SRDataset"):
             if not data_cfg.get("img_folder"):
                 raise ValueError("data.class_name ddm.data.SRDataset needs data.img_folder")
@@ -240,23 +271,15 @@ class SRBatchStream:
         else:
             raise NotImplementedError(f"data.class_name {cls!r}: only ddm.data.SRDataset + img_folder, a uint8 data.npy, or "
                                       "'synthetic' (U(0,255) images, benchmarking only) are implemented")
-        self._order = torch.empty(0, dtype=torch.int64, device=device)      # what is left of the running permutation(s)
-        self._zeros = torch.zeros(self.batch, dtype=torch.int32, device=device)
         self._size = torch.tensor(self.size, dtype=torch.int64, device=device)
 
     def draw(self):
         """(idx, top, left, flip) of one batch, int32 device tensors."""
-        while self._order.numel() < self.batch:          # (sizes are host integers: no synchronisation)
-            self._order = torch.cat([self._order, torch.randperm(self.pool.n, device=self.device, generator=self.gen)])
-        idx, self._order = self._order[:self.batch], self._order[self.batch:]
+        idx = self.take_indices()
         r = torch.randint(0, 2 ** 31 - 1, (2, self.batch), device=self.device, generator=self.gen)
         span = self.pool.hw[idx].to(torch.int64) - self._size + 1          # [B, 2] valid offsets
         top, left = r[0] % span[:, 0], r[1] % span[:, 1]
-        if self.flip:
-            flip = (torch.rand(self.batch, device=self.device, generator=self.gen) < 0.5).to(torch.int32)
-        else:
-            flip = self._zeros
-        return idx.to(torch.int32), top.to(torch.int32), left.to(torch.int32), flip
+        return idx.to(torch.int32), top.to(torch.int32), left.to(torch.int32), self.draw_flip()
 
     def next_batch(self, idx=None, top=None, left=None, flip=None, want_u8: bool = False):
         if idx is None or top is None or left is None or flip is None:
@@ -267,9 +290,6 @@ class SRBatchStream:
         if want_u8:
             out["cond_u8"] = u8
         return out
-
-    def __iter__(self):
-        return self
 
     def __next__(self):
         return self.next_batch()

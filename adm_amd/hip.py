@@ -182,6 +182,9 @@ _SIGS = {
     "adm_rowscale_add": [P, P, P, P, I, L, P],
     "adm_sr_tile": [I],
     "adm_sr_batch": [P, L, P, P, I, P, P, P, P, P, P, I, P, P, I, P, P, P, I, I, I, I, I, P],
+    "adm_inpaint_masks": [P, P, P, P, P, P, P, P, P, I, I, P],
+    "adm_inpaint_batch": [P, L, P, P, I, P, P, P, P, P, P, P, P, P, P, I, I, P],
+    "adm_inpaint_compose": [P, P, P, P, I, I, L, P],
 }
 EXPORTS = tuple(_SIGS)
 

@@ -531,6 +531,58 @@ int adm_sr_batch(const uint8_t* pool, long pool_bytes, const int64_t* img_off, c
                  const int* vbounds, const int* vcoef, int kv, float* image, float* cond, uint8_t* cond_u8, int B, int H, int W,
                  int h, int w, hipStream_t stream);
 
+/* ---------------- in-painting batches (ddm/data.py:384-476, InpaintDataset.__getitem__ / random_mask / RandomBrush) ----------------
+ * A mask is hole = 0 / keep = 1 on integer pixel coordinates of an S x S image, defined in integers: a pixel is a
+ * hole when a clipped rectangle, a stroke segment (butt-ended band: 0 <= dot <= L2 and 4 cross^2 <= w^2 L2, int64) or a stroke
+ * vertex (disc: 4 d^2 <= (2 (w / 2) + 1)^2) covers it; the two flip bits mirror the STROKES along axis 0 / axis 1 (RandomBrush flips
+ * the mask it returns, data.py:472-475), never the rectangles.
+ *
+ * Draws: per sample ADM_INP_CANDIDATES candidate slabs of ADM_INP_NU uniform and ADM_INP_NZ normal float32 draws, consumed by the
+ * reference's calls in FIXED slots (a slot belongs to one call whether or not that call happens):
+ *   u[ADM_INP_U_NRECT_SMALL]                    count of rectangles of max_size S/2 (0..3)
+ *   u[ADM_INP_U_RECT + 4 j + {0,1,2,3}]         w, h, x, y of rectangle j (j = 0..2 small, j = 3 the one of max_size S)
+ *   u[ADM_INP_U_NRECT_BIG]                      count of rectangles of max_size S (0..1)
+ *   u[ADM_INP_U_NSTROKE]                        count of strokes (0..7)
+ *   u[ADM_INP_U_STROKE + ADM_INP_STROKE_U k + ...]   stroke k: +0 num_vertex, +1 / +2 angle_min / angle_max, +3 .. +19 the angles,
+ *                                               +20 / +21 the first vertex x / y, +22 the width, +23 / +24 two discarded draws
+ *   u[ADM_INP_U_FLIP + {0,1}]                   the flips along axis 0 / axis 1
+ *   z[ADM_INP_SEGMENTS k + i]                   the radius draw of segment i of stroke k
+ * adm_inpaint_masks (B threads, fp64 without contraction) turns them into primitive lists and keeps, per sample, the first
+ * candidate that covers a pixel (decided from the parameters); if none does it keeps the last, whose mask is all ones, and adds
+ * one to fallback[0].  rects int32 [B][4][4] = {x0, y0, x1, y1} clipped to the image (x0 >= x1: empty); verts int32
+ * [B][7][18][2] = {x, y} in [0, S]; nverts / widths int32 [B][7] (nverts 0: no stroke); flips int32 [B][2]; chosen int32 [B].
+ *
+ * adm_inpaint_batch: one launch, a workgroup per ADM_INP_TILE_H x ADM_INP_TILE_W tile of one sample, the sample's primitives
+ * staged in LDS and culled against the tile.  Image idx[b] of the pool (adm_sr_batch's layout; it must be S x S) gives `image`
+ * [B][3][S][S] = u8 / 255 * 2 - 1 (columns mirrored when img_flip[b] != 0), `cond` = (mask * (u8 / 255)) * 2 - 1 of the same
+ * pixels, `ori_mask` [B][1][S][S]; each float is rounded once per operation (no fma), as the host expression is.
+ *
+ * adm_inpaint_compose: out[b][c][p] = mask[b][p] * ((cond + 1) / 2) + (1 - mask[b][p]) * x[b][c][p], each operation rounded
+ * (ddm_const_2.py:629); hw = pixels of a plane. */
+#define ADM_INP_CANDIDATES 4
+#define ADM_INP_RECTS 4
+#define ADM_INP_STROKES 7
+#define ADM_INP_VERTS 18
+#define ADM_INP_SEGMENTS 17
+#define ADM_INP_U_NRECT_SMALL 0
+#define ADM_INP_U_RECT 1
+#define ADM_INP_U_NRECT_BIG 17
+#define ADM_INP_U_NSTROKE 18
+#define ADM_INP_U_STROKE 19
+#define ADM_INP_STROKE_U 25
+#define ADM_INP_U_FLIP 194
+#define ADM_INP_NU 196
+#define ADM_INP_NZ 119
+#define ADM_INP_TILE_H 8
+#define ADM_INP_TILE_W 32
+int adm_inpaint_masks(const float* u, const float* z, int* rects, int* verts, int* nverts, int* widths, int* flips, int* chosen,
+                      int* fallback, int B, int S, hipStream_t stream);
+int adm_inpaint_batch(const uint8_t* pool, long pool_bytes, const int64_t* img_off, const int* img_hw, int n_images, const int* idx,
+                      const int* img_flip, const int* rects, const int* verts, const int* nverts, const int* widths,
+                      const int* flips, float* image, float* cond, float* ori_mask, int B, int S, hipStream_t stream);
+int adm_inpaint_compose(const float* mask, const float* cond, const float* x, float* out, int B, int C, long hw,
+                        hipStream_t stream);
+
 /* ---------------- optimiser (train_uncond_dpm.py:292-310, ddm/ema.py:158-188) ---------------- */
 
 /* sumsq[0] += sum g^2.  partials = workspace of adm_sumsq_blocks(n) doubles: per-workgroup partial sums combined in a
@@ -608,7 +660,7 @@ int adm_spatial_att_big_bwd(const float* att, int ldatt, const float* qk, const 
                             float* dh, float* datt, float* dqk, float* dqk_part, int B, int HW, int C, hipStream_t stream);
 
 /* softmax(scale q k^T) v per (image, head) with separate query / key lengths; head h = columns [h*D, (h+1)*D) of rows with
- * strides ldq / ldk / ldv / ldo; D in {4, 8, 16, 32, 64}.  RelationNet's windowed cross-attention (cond_unet_sd.py:221-231,
+ * strides ldq / ldk / ldv / ldo; D in {4, 8, 12, 16, 24, 32, 48, 64, 96}.  RelationNet's windowed cross-attention (cond_unet_sd.py:221-231,
  * scale 1) and the bottleneck Attention (:532-554, scale 32^-0.5).  lse [B*H][Lq][2] = (row maximum,
  * log sum exp(s - maximum)), kept apart so that a maximum of a few hundred does not round the sum; delta = workspace [B*H][Lq]. */
 int adm_mha_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int Lq, int Lk, int H, int D, int ldq,

@@ -18,6 +18,11 @@ What differs from the reference:
     ``sampler.cond_encoder`` names a callable ``module:attr`` that maps a condition crop [B,3,h,w] to the four feature maps
     the denoiser consumes; ``synthetic`` selects a parameter-free pooled pyramid (smoke runs / benchmarking only);
   * every rank handles a disjoint share of the images; no collectives.
+
+With ``data.class_name: ddm.data.InpaintDataset`` (in-painting, configs/inpainting/celebahq_cond_ddm_const_ldm_sample.yaml) there is no
+window: each image gets a mask drawn on the device (adm_amd.ddm.inpaint_data), the model is sampled once on the masked image with
+``mask=`` / ``cond_image=``, and the composite -- kept pixels from the image, holes from the sample -- is written under the image's
+name; ``sampler.save_masks: True`` also writes ``masks/<name>``.  PSNR is printed as the reference's sampler prints it (:195, 217).
 """
 import argparse
 import importlib
@@ -173,6 +178,29 @@ class CondStream:
             yield {"image": pad, "cond": torch.nn.functional.avg_pool2d(pad, 4), "ori_size": (H, W), "img_name": f"{i: 010d}.png"}
 
 
+INPAINT_CLASSES = ("ddm.data.InpaintDataset", "InpaintDataset")
+
+
+class InpaintCondStream:
+    """``data.class_name: ddm.data.InpaintDataset`` at sampling time (``split: test`` of ``img_folder``, or ``data.npy``): image i of
+    the pool with a mask drawn for it on the device, as the reference's test set draws one per item (ddm/data.py:395); the test
+    transform has no flip (:377-379).  Items are keyed as CondStream's."""
+
+    def __init__(self, data_cfg, n, image_size, device, seed):
+        from adm_amd.ddm.inpaint_data import InpaintBatchStream
+        self.n = n
+        self.stream = InpaintBatchStream(dict(data_cfg, augment_horizontal_flip=False), 1, image_size, device, seed)
+
+    def __iter__(self):
+        s = self.stream
+        for i in range(self.n):
+            k = i % s.pool.n
+            batch = s.next_batch(idx=[k], flip=[0])
+            batch["ori_size"] = (s.size, s.size)
+            batch["img_name"] = s.names[k][:-4] + ".png" if s.names else f"{i: 010d}.png"          # reference :217: the name, as png
+            yield batch
+
+
 def main():
     ap = argparse.ArgumentParser(description="sliding-window conditional latent sampler (MI355X hot path)")
     ap.add_argument("--cfg", required=True)
@@ -215,12 +243,34 @@ def main():
     from PIL import Image
     n_total = int(s.sample_num) if args.max_images is None else min(int(s.sample_num), args.max_images)
     per_rank = n_total // world
-    stream = CondStream(cfg.data, per_rank, device, seed=2000 + rank)
-    crop, stride = tuple(s.crop_size), tuple(s.stride)
+    inpaint = cfg.data.get("class_name") in INPAINT_CLASSES
+    if inpaint:
+        size = tuple(cfg.data.get("image_size") or mc.image_size)
+        stream = InpaintCondStream(cfg.data, per_rank, size, device, seed=2000 + rank)
+        # the reference's in-painting sample YAML has neither key: one window, the image
+        crop, stride = tuple(s.get("crop_size") or size), tuple(s.get("stride") or size)
+        if crop != size:
+            raise NotImplementedError(f"in-painting samples the whole image in one window: sampler.crop_size {crop} must equal image_size {size}")
+        if bool(s.get("save_masks", False)):
+            os.makedirs(os.path.join(out_dir, "masks"), exist_ok=True)
+    else:
+        stream = CondStream(cfg.data, per_rank, device, seed=2000 + rank)
+        crop, stride = tuple(s.crop_size), tuple(s.stride)
     psnr, done, t0 = 0.0, 0, time.time()
     for batch in stream:
         cond, image = batch["cond"], (batch["image"] + 1) * 0.5
         down = ldm.first_stage_model.down_ratio
+        if inpaint:          # the composite: kept pixels from the masked image, holes from the sample (reference :175-186, ddm_const_2.py:629)
+            mask = batch["ori_mask"]
+            pred = ldm.sample(cond=list(ldm.model.init_conv_mask(cond)), mask=mask, cond_image=cond).to(torch.float32)
+            psnr += float(-10.0 * torch.log10(torch.mean((pred - image) ** 2)))
+            arr = (pred[0].clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0).cpu().numpy()
+            name = batch["img_name"] if world == 1 else f"{rank * per_rank + done: 010d}.png"
+            Image.fromarray(arr).save(os.path.join(out_dir, name))
+            if bool(s.get("save_masks", False)):
+                Image.fromarray((mask[0, 0] * 255).to(torch.uint8).cpu().numpy()).save(os.path.join(out_dir, "masks", name))
+            done += 1
+            continue
         # the encoder runs ONCE per window batch (the reference re-runs it inside every denoising step, cond_unet_sd.py:821)
         fn = lambda c: ldm.sample(cond=list(ldm.model.init_conv_mask(c)), latent_hw=(c.shape[2] * 4 // down, c.shape[3] * 4 // down))
         # the frame the windows tile is the condition's, x4 (for SRDatasetTest larger than the unpadded image: reference :324-332)

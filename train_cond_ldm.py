@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """MI355X counterpart of the reference's conditional LATENT trainer (its train_cond_ldm.py): the 4x super-resolution
-recipe (configs/super-resolution/div2k_cond_ddm_const_ldm_train.yaml).
+recipe (configs/super-resolution/div2k_cond_ddm_const_ldm_train.yaml) and the in-painting recipe
+(configs/inpainting/celebahq_cond_ddm_const_ldm.yaml).
 
 Same command line and YAML schema as the other drivers (``--cfg``, ``--max-steps``); model construction, gradient accumulation,
 clip-norm, EMA, the checkpoint layout and the multi-GPU launch are the shared Trainer of train_uncond_dpm.py.  What differs from
 that driver (reference lines of train_cond_ldm.py in brackets):
   * batch source: {'image', 'cond'} pairs of ddm.data.SRDataset [:57-63], made on the device by one HIP kernel from a uint8
-    image pool (adm_amd.ddm.sr_data.SRBatchStream) instead of PIL in dataloader workers;
+    image pool (adm_amd.ddm.sr_data.SRBatchStream) instead of PIL in dataloader workers; with ``data.class_name:
+    ddm.data.InpaintDataset`` the {'image', 'cond', 'ori_mask'} triples of adm_amd.ddm.inpaint_data.InpaintBatchStream;
   * LR schedule: ratio max((1 - it/N)^0.96, min_lr/lr) from step 0, no warm-up [:150];
   * weight decay defaults to 1e-2 [:72];
   * the periodic and ``test_before`` samples are conditioned on a training batch: sample(batch_size=cond.shape[0], cond=..., mask=
@@ -24,12 +26,25 @@ import torch
 import torch.distributed as dist
 
 from train_uncond_dpm import Cfg, Trainer, build_model, parse_args, save_grid
+from adm_amd.ddm.inpaint_data import InpaintBatchStream
 from adm_amd.ddm.sr_data import SRBatchStream
 from adm_amd.optim import lr_lambda_cond
 
 
 def grid_columns(batch):
     return 2 ** math.floor(math.log2(math.sqrt(batch)))          # train_cond_ldm.py:89, 309
+
+
+INPAINT_CLASSES = ("ddm.data.InpaintDataset", "InpaintDataset")
+
+
+def batch_stream(data_cfg, batch, image_size, device, seed):
+    """The batch source ``data.class_name`` names: in-painting triples for ddm.data.InpaintDataset, super-resolution pairs otherwise
+    (SRBatchStream raises for what it does not know).  ``class_name: synthetic`` stands for the dataset ``data.synthetic_of`` names."""
+    cls = data_cfg.get("class_name")
+    if cls in INPAINT_CLASSES or (cls == "synthetic" and data_cfg.get("synthetic_of") in INPAINT_CLASSES):
+        return InpaintBatchStream(data_cfg, batch, image_size, device, seed)
+    return SRBatchStream(data_cfg, batch, image_size, device, seed)
 
 
 class CondTrainer(Trainer):
@@ -74,8 +89,8 @@ def main(args):
     ldm = build_model(model_cfg).to(device).train()          # the Unet (and its encoder) exists before FlatParams is built
     global_batch = int(cfg.data.batch_size)
     assert global_batch % world == 0, "split_batches: the YAML batch_size is the global batch"
-    stream = SRBatchStream(cfg.data, global_batch // world, tuple(cfg.data.get("image_size") or model_cfg.image_size), device,
-                           seed=1000 + rank)
+    stream = batch_stream(cfg.data, global_batch // world, tuple(cfg.data.get("image_size") or model_cfg.image_size), device,
+                          seed=1000 + rank)
     trainer = CondTrainer(ldm, stream, cfg, device, rank, world)
     if cfg.trainer.get("test_before", False) and rank == 0:          # train_cond_ldm.py:74-91
         name = f"sample-{cfg.trainer.get('resume_milestone', 0)}_{model_cfg.sampling_timesteps}.png"
