@@ -324,7 +324,7 @@ def _h3_operands(weight: torch.Tensor, ent: "_Packed", which: int):
 
 # ADM_DETERMINISTIC=1: bitwise reproducible backward.  The weight / bias gradient kernels normally combine their pixel-range
 # splits with fp32 atomics (order-dependent rounding); with this switch every split stores its partial tile to a workspace
-# and the unpack launch sums them in split order (adm_conv_wgrad_ws / adm_unpack_wgrad_splits).  Everything else on the
+# and the unpack launch sums them in split order (_wgrad_workspace / _unpack_wgrad below).  Everything else on the
 # training step (forward, data gradients, GroupNorm, attention, loss, norm, optimiser) is reproducible unconditionally.
 DETERMINISTIC = os.environ.get("ADM_DETERMINISTIC", "0") == "1"
 
@@ -971,6 +971,151 @@ def _conv_data_pass(tag, x, x16, weight, pk, which, bias, res, y, ks, up, tile, 
     return amax_y
 
 
+def _wgrad_kind(B, Ho, Wo, ks, up, qkv, bf16, xdtype, bounds):
+    """Which weight-gradient kernel a stride-1 conv takes, as the label the profiler gets, from the layer's facts and the module switches
+    alone.  xdtype: how x is stored; bounds: both operands came with their max |.| (the fp16 format, conv_wgrad_x6.hip FMT 1).  Returns
+    (kind, wmode, planes, conv_shaped): the packed tile's Winograd form, and whether the launch takes conv sizes or the GEMM's."""
+    pow2 = lambda v: v > 0 and (v & (v - 1)) == 0
+    wino_ok = _use_wino(B, Ho, Wo, ks, up, -1) and not qkv and pow2(Ho) and pow2(Wo)
+    # bf16 mode with bf16 activation storage: the split-bf16 Winograd kernel (dy split exactly, x as stored) is faster than the
+    # direct bf16 weight gradient (~250 vs 179 TFLOP/s algorithmic) and more accurate.  With f32 storage (ADM_BF16_STORAGE=0)
+    # the direct kernel stays: it rounds x on load, so the two storage modes keep computing the same thing.
+    xbf = xdtype == torch.bfloat16
+    x6_bf = bf16 and xbf and BF16X6 and WINOGRAD2D and wino_ok and Ho >= 2
+    wino = not bf16 and wino_ok
+    wino2 = (wino and WINOGRAD2D and (not up or BF16X6) and Ho >= 2) or x6_bf   # 2-D F(3x3, 2x2): 12 x-folded planes per cout
+    x6 = wino2 and BF16X6          # f32 products on the bf16 MFMA by exact three-term splitting (conv_wgrad_x6.hip)
+    g6 = (GEMM_WGRAD_X6 and BF16X6 and (not bf16 or xbf) and ks == 1 and not up
+          and B * Ho * Wo >= GEMM_X6_MIN_M)      # ... 1x1 convs (its MODE 1)
+    h3 = bounds and (x6 or g6) and not bf16 and H3_WGRAD
+    kind = "wgrad_wino2h3" if (h3 and x6) else "wgrad_gemmh3" if h3 else "wgrad_wino2x6" if x6 else "wgrad_gemmx6" if g6 else "wgrad_wino2" if wino2 else "wgrad_wino" if wino else "wgrad"
+    return kind, 2 if wino2 else int(wino), 12 if wino2 else ks * ks, not kind.startswith("wgrad_gemm")
+
+
+def _wgrad_workspace(kind, det, defer, weight, like, B, Ho, Wo, cip, cop, ks, up, wmode, planes, need_b):
+    """(dwp, splits, bws): what a weight-gradient kernel of `kind` writes.  det: `splits` partial tiles by the kernel's own plan query
+    and, with need_b, as many bias rows bws; defer: the layer's zero-at-rest workspace, which the end-of-backward table unpacks and
+    clears; else a fresh tile.  splits = 0 and bws = None outside det."""
+    if det:        # splits store partial tiles to a workspace; the unpack launch sums them in a fixed order
+        splits = (hip.lib().adm_conv_wgrad_x6_plan(B, Ho, Wo, cip, cop) if kind in ("wgrad_wino2x6", "wgrad_wino2h3") else
+                  hip.lib().adm_gemm_wgrad_x6_plan(B * Ho * Wo, cip, cop) if kind.startswith("wgrad_gemm") else
+                  hip.lib().adm_conv_wgrad_plan(B, Ho, Wo, cip, cop, ks, int(up), wmode))
+        if splits < 1:
+            raise RuntimeError(f"adm_conv_wgrad_plan failed with code {splits}")
+        return _new((splits, cop, planes * cip), like), splits, (_new((splits, cop), like) if need_b else None)
+    if defer:
+        _begin_defer()          # (before the kernel: a pass that died may have left this workspace dirty)
+        return _rest_workspace_for(weight, (cop, planes * cip), like), 0, None
+    return _new((cop, planes * cip), like), 0, None
+
+
+def _unpack_wgrad(weight, sink, dwp, ks, qkv, wino2, defer, splits, bws, dbk):
+    """The packed tile dwp -> the OIHW gradient: added into `sink` (the flat gradient buffer's view; the caller then announces it with
+    _notify, after what it still has to finish) or stored to a new tensor, which is returned for autograd.  defer: as a row of the
+    end-of-backward table; splits > 0: sums that many partial tiles, and the bias rows bws into dbk; wino2: 2-D Winograd planes."""
+    co, ci = weight.shape[0], weight.shape[1]
+    cop, cip = ceil32(co), ceil32(ci)
+    dst = sink if sink is not None else _like(weight)
+    acc = int(sink is not None)
+    if defer:
+        _defer_unpack(dwp, dst, co, ci, 0 if wino2 else ks * ks, cip, qkv)
+    elif wino2:    # the y half of G^T rides in the unpack: dW[ky] = sum_ey Gt[ky][ey] wx[ey]
+        call("adm_unpack_wgrad_wino2d", ptr(dwp), splits or 1, ptr(dst), co, ci, cop, cip, acc, ptr(bws) if splits else None,
+             ptr(dbk) if splits else None)
+    elif splits:
+        call("adm_unpack_wgrad_splits", ptr(dwp), splits, ptr(dst), co, ci, ks, cop, cip, int(qkv), acc, ptr(bws), ptr(dbk))
+    else:
+        call("adm_unpack_wgrad", ptr(dwp), ptr(dst), co, ci, ks, cop, cip, int(qkv), acc)
+    return None if sink is not None else dst
+
+
+def _finish_bias(bias_to, dbp, bsink, bias, co, qkv, dy):
+    """The bias gradient from where the kernels left it (dbp, packed order) to where the route `bias_to` of _Conv.backward sends it;
+    returns db for autograd, None when the flat gradient buffer took it (then announced here)."""
+    db = dbp if bias_to == "fresh" else None
+    if bias_to == "table":
+        _defer_unpack(dbp, bsink, co, 1, 1, 1, qkv)
+    elif bias_to == "permute":
+        db = _new((co,), dy)
+        call("adm_permute_vec", ptr(dbp), ptr(db), co, co, int(qkv), 1)
+    if bias_to in ("sink", "table"):
+        _notify(bias)
+    return db
+
+
+def _conv_param_pass(x, dy, weight, bias, ks, up, qkv, bf16, amax_x, need_w, wsink, bias_to, bsink):
+    """The weight and bias gradients of a stride-1 conv from its saved input x and dy: selects the weight-gradient kernel and its
+    workspace, launches, unpacks and hands over.  Returns (dw, db) for autograd, None where the flat gradient buffer took one or none
+    was asked for.  The caller states:
+      amax_x          the bound x came with on the fp16 format, or None (dy's is looked up only where it would change the kernel)
+      need_w, wsink   the weight needs a gradient; its view of the flat gradient buffer, or None
+      bias_to, bsink  the bias gradient's route (None: not needed); its view of the flat gradient buffer, or None"""
+    B, Ho, Wo, cop = dy.shape
+    co, ci = weight.shape[0], weight.shape[1]
+    cip = ceil32(ci)
+    # fp32: the weight-gradient kernel also produces the bias gradient (column sums of dy) on its way
+    fused_b = bias_to is not None and need_w and not bf16
+    # dbp: where the kernel (fused_b: it accumulates) or adm_colsum (it stores) leaves the bias gradient, in packed order
+    dbp = None
+    if bias_to == "sink":
+        dbp = bsink
+    elif bias_to == "table":
+        _begin_defer()
+        dbp = _rest_workspace_for(bias, (cop,), dy)
+    elif bias_to is not None:
+        n = co if bias_to == "fresh" else cop
+        dbp = torch.zeros((n,), device=dy.device, dtype=_f32) if fused_b else _new((n,), dy)
+    dw = db = None
+    if need_w:
+        dbk = dbp if fused_b else None      # (what the kernel is given)
+        det = DETERMINISTIC and not bf16
+        defer = DEFER_UNPACK and wsink is not None and not det      # (with a side stream: the flush joins it first)
+        facts = (B, Ho, Wo, ks, up, qkv, bf16, x.dtype)
+        kind, wmode, planes, conv_shaped = _wgrad_kind(*facts, False)
+        dwp, splits, bws = _wgrad_workspace(kind, det, defer, weight, dy, B, Ho, Wo, cip, cop, ks, up, wmode, planes, fused_b)
+        # fp16 format (conv_wgrad_x6.hip FMT 1): both operands came with their bounds
+        kind_h3 = _wgrad_kind(*facts, True)[0]
+        amax_dy = _get_amax(dy) if amax_x is not None and kind_h3 != kind else None
+        if amax_dy is not None:
+            _check_bound(x, amax_x, "a conv input (weight gradient)")
+            kind = kind_h3
+        # x, dy, the packed dW tile and the bias gradient's rows (per split under det); then conv-shaped or GEMM-shaped sizes
+        head = (ptr(x), ptr(dy), ptr(dwp), ptr(bws if det else dbk))
+        size = (B, Ho, Wo, cip, cip, cop, cop) if conv_shaped else (B * Ho * Wo, cip, cip, cop, cop)
+        nsplit = splits if det else -1 if defer else 0       # -1: chosen by the launcher, workspace zero on entry (no memset)
+        with _Prof(kind, 2.0 * B * Ho * Wo * co * ci * ks * ks,
+                   f"{kind.replace('_', '-')} P={B * Ho * Wo} Co={cop} Ci={cip} ks={ks}"):
+            if kind == "wgrad_wino2h3":
+                call("adm_conv_wgrad_x6_h3", *head, *size, nsplit, int(up), int(det), _bptr(amax_x), _bptr(amax_dy))
+            elif kind == "wgrad_gemmh3":
+                call("adm_gemm_wgrad_x6_h3", *head, *size, nsplit, int(det), _bptr(amax_x), _bptr(amax_dy))
+            elif kind == "wgrad_gemmx6":
+                call("adm_gemm_wgrad_x6_bf16a" if bf16 else "adm_gemm_wgrad_x6_ws" if det else "adm_gemm_wgrad_x6", *head, *size, nsplit)
+            elif kind == "wgrad_wino2x6" and (bf16 or det):
+                call("adm_conv_wgrad_x6_bf16a" if bf16 else "adm_conv_wgrad_x6_ws", *head, *size, nsplit, int(up))
+            elif kind == "wgrad_wino2x6":
+                call("adm_conv_wgrad_x6_up" if up else "adm_conv_wgrad_x6", *head, *size, nsplit)
+            elif bf16:       # (no bias gradient from the direct bf16 kernels)
+                call("adm_conv_wgrad_bf16a" if x.dtype == torch.bfloat16 else "adm_conv_wgrad_bf16", *head[:3], *size, ks, int(up), nsplit)
+            elif det:
+                call("adm_conv_wgrad_ws", *head, *size, ks, int(up), nsplit, wmode)
+            elif kind == "wgrad_wino2":
+                call("adm_conv_wgrad_wino2d", *head, *size, nsplit)
+            elif kind == "wgrad_wino":
+                call("adm_conv_wgrad_wino_up" if up else "adm_conv_wgrad_wino", *head, *size, nsplit)
+            else:
+                call("adm_conv_wgrad_bias", *head, *size, ks, int(up), nsplit)
+        dw = _unpack_wgrad(weight, wsink, dwp, ks, qkv, wmode == 2, defer, splits, bws, dbk)
+        if fused_b:
+            db = _finish_bias(bias_to, dbp, bsink, bias, co, qkv, dy)
+        if wsink is not None:
+            _notify(weight)
+    if bias_to is not None and not fused_b:
+        call("adm_colsum", ptr(dy), ptr(dbp), B * Ho * Wo, cop, cop, int(bias_to == "sink"))
+        db = _finish_bias(bias_to, dbp, bsink, bias, co, qkv, dy)
+    return dw, db
+
+
 class _Conv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, residual, ks, up, qkv, tile, amax=None):
@@ -1013,7 +1158,8 @@ class _Conv(torch.autograd.Function):
         co, ci = weight.shape[0], weight.shape[1]
         cip = ceil32(ci)
         dx = dw = db = None
-        wsink = _direct_grad(weight) if ctx.needs_input_grad[1] else None
+        need_w = ctx.needs_input_grad[1]
+        wsink = _direct_grad(weight) if need_w else None
         bsink = _direct_grad(bias) if ctx.needs_input_grad[2] else None
         # how the bias gradient travels -- the one place that decides it
         bias_to = None
@@ -1026,8 +1172,7 @@ class _Conv(torch.autograd.Function):
                 bias_to = "table"
             else:
                 bias_to = "permute"         # a padded temporary, then adm_permute_vec into a new [co] for autograd
-        # fp32: the weight-gradient kernel also produces the bias gradient (column sums of dy) on its way
-        fused_b = bias_to is not None and ctx.needs_input_grad[1] and not bf16
+        params = (x, dy, weight, bias, ks, up, qkv, bf16, ctx.amax_x, need_w, wsink, bias_to, bsink)
         side = None
         if SIDE_WGRAD and PROFILE is None and wsink is not None and bias_to in (None, "sink", "table"):    # (nothing goes back through autograd)
             side = _wgrad_stream()
@@ -1035,131 +1180,8 @@ class _Conv(torch.autograd.Function):
             ev.record()                      # dy (and x) are complete at this point of the main stream
             side.wait_event(ev)
             _queue_join_at_end_of_backward()
-
-        def weight_and_bias_grads():
-            nonlocal dw, db
-            # dbp: where the kernel (fused_b: it accumulates) or adm_colsum (it stores) leaves the bias gradient, in packed order
-            dbp = None
-            if bias_to == "sink":
-                dbp = bsink
-            elif bias_to == "table":
-                _begin_defer()
-                dbp = _rest_workspace_for(bias, (cop,), dy)
-            elif bias_to is not None:
-                n = co if bias_to == "fresh" else cop
-                dbp = torch.zeros((n,), device=dy.device, dtype=_f32) if fused_b else _new((n,), dy)
-                if bias_to == "fresh":
-                    db = dbp
-
-            def finish_bias():
-                nonlocal db
-                if bias_to == "table":
-                    _defer_unpack(dbp, bsink, co, 1, 1, 1, qkv)
-                elif bias_to == "permute":
-                    db = _new((co,), dy)
-                    call("adm_permute_vec", ptr(dbp), ptr(db), co, co, int(qkv), 1)
-                if bias_to in ("sink", "table"):
-                    _notify(bias)
-
-            if ctx.needs_input_grad[1]:
-                dbk = dbp if fused_b else None      # (what the kernel is given)
-                pow2 = lambda v: v > 0 and (v & (v - 1)) == 0
-                wino_ok = _use_wino(B, Ho, Wo, ks, up, -1) and not qkv and pow2(Ho) and pow2(Wo)
-                # bf16 mode with bf16 activation storage: the split-bf16 Winograd kernel (dy split exactly, x as stored) is faster than the
-                # direct bf16 weight gradient (~250 vs 179 TFLOP/s algorithmic) and more accurate.  With f32 storage (ADM_BF16_STORAGE=0)
-                # the direct kernel stays: it rounds x on load, so the two storage modes keep computing the same thing.
-                xbf = x.dtype == torch.bfloat16
-                x6_bf = bf16 and xbf and BF16X6 and WINOGRAD2D and wino_ok and Ho >= 2
-                wino_w = not bf16 and wino_ok
-                wino2_w = (wino_w and WINOGRAD2D and (not up or BF16X6) and Ho >= 2) or x6_bf   # 2-D F(3x3, 2x2): 12 x-folded planes per cout
-                wmode = 2 if wino2_w else int(wino_w)
-                planes = 12 if wino2_w else ks * ks
-                det = DETERMINISTIC and not bf16
-                defer = DEFER_UNPACK and wsink is not None and not det      # (with a side stream: the flush joins it first)
-                x6_w = wino2_w and BF16X6          # f32 products on the bf16 MFMA by exact three-term splitting (conv_wgrad_x6.hip)
-                g6_w = (GEMM_WGRAD_X6 and BF16X6 and (not bf16 or xbf) and ks == 1 and not up
-                        and B * Ho * Wo >= GEMM_X6_MIN_M)      # ... 1x1 convs (its MODE 1)
-                splits, bws = 1, None
-                if det:        # splits store partial tiles to a workspace; the unpack launch sums them in a fixed order
-                    splits = (hip.lib().adm_conv_wgrad_x6_plan(B, Ho, Wo, cip, cop) if x6_w else
-                              hip.lib().adm_gemm_wgrad_x6_plan(B * Ho * Wo, cip, cop) if g6_w else
-                              hip.lib().adm_conv_wgrad_plan(B, Ho, Wo, cip, cop, ks, int(up), wmode))
-                    if splits < 1:
-                        raise RuntimeError(f"adm_conv_wgrad_plan failed with code {splits}")
-                    dwp = _new((splits, cop, planes * cip), dy)
-                    bws = _new((splits, cop), dy) if fused_b else None
-                elif defer:
-                    _begin_defer()          # (before the kernel: a pass that died may have left this workspace dirty)
-                    dwp = _rest_workspace_for(weight, (cop, planes * cip), dy)
-                else:
-                    dwp = _new((cop, planes * cip), dy)
-                auto = -1 if defer else 0        # -1: chosen by the launcher, workspace zero on entry (no memset)
-                amax_x, amax_dy = ctx.amax_x, None
-                if amax_x is not None and (x6_w or g6_w) and not bf16 and H3_WGRAD:
-                    amax_dy = _get_amax(dy)
-                h3_w = amax_dy is not None          # fp16 format (conv_wgrad_x6.hip FMT 1): both operands came with their bounds
-                if h3_w:
-                    _check_bound(x, amax_x, "a conv input (weight gradient)")
-                # x, dy, the packed dW tile and the bias gradient's rows (per split under det); then conv-shaped or GEMM-shaped sizes
-                head = (ptr(x), ptr(dy), ptr(dwp), ptr(bws if det else dbk))
-                conv_g = (B, Ho, Wo, cip, cip, cop, cop)
-                gemm_g = (B * Ho * Wo, cip, cip, cop, cop)
-                nsplit = splits if det else auto
-                kind = "wgrad_wino2h3" if (h3_w and x6_w) else "wgrad_gemmh3" if h3_w else "wgrad_wino2x6" if x6_w else "wgrad_gemmx6" if g6_w else "wgrad_wino2" if wino2_w else "wgrad_wino" if wino_w else "wgrad"
-                with _Prof(kind, 2.0 * B * Ho * Wo * co * ci * ks * ks,
-                           f"{kind.replace('_', '-')} P={B * Ho * Wo} Co={cop} Ci={cip} ks={ks}"):
-                    if bf16 and x6_w and xbf:
-                        call("adm_conv_wgrad_x6_bf16a", *head, *conv_g, auto, int(up))
-                    elif bf16 and g6_w and xbf:
-                        call("adm_gemm_wgrad_x6_bf16a", *head, *gemm_g, auto)
-                    elif bf16 and not (x6_w or g6_w):       # (no bias gradient from the direct bf16 kernels)
-                        call("adm_conv_wgrad_bf16a" if xbf else "adm_conv_wgrad_bf16", *head[:3], *conv_g, ks, int(up), auto)
-                    elif h3_w and x6_w:
-                        call("adm_conv_wgrad_x6_h3", *head, *conv_g, nsplit, int(up), int(det), _bptr(amax_x), _bptr(amax_dy))
-                    elif h3_w:
-                        call("adm_gemm_wgrad_x6_h3", *head, *gemm_g, nsplit, int(det), _bptr(amax_x), _bptr(amax_dy))
-                    elif det and g6_w:
-                        call("adm_gemm_wgrad_x6_ws", *head, *gemm_g, splits)
-                    elif g6_w:
-                        call("adm_gemm_wgrad_x6", *head, *gemm_g, auto)
-                    elif det and x6_w:
-                        call("adm_conv_wgrad_x6_ws", *head, *conv_g, splits, int(up))
-                    elif det:
-                        call("adm_conv_wgrad_ws", *head, *conv_g, ks, int(up), splits, wmode)
-                    elif x6_w:
-                        call("adm_conv_wgrad_x6_up" if up else "adm_conv_wgrad_x6", *head, *conv_g, auto)
-                    elif wino2_w:
-                        call("adm_conv_wgrad_wino2d", *head, *conv_g, auto)
-                    elif wino_w:
-                        call("adm_conv_wgrad_wino_up" if up else "adm_conv_wgrad_wino", *head, *conv_g, auto)
-                    else:
-                        call("adm_conv_wgrad_bias", *head, *conv_g, ks, int(up), auto)
-                if wsink is not None:
-                    dst, acc = wsink, 1
-                else:
-                    dw = _like(weight)
-                    dst, acc = dw, 0
-                if defer:
-                    _defer_unpack(dwp, dst, co, ci, 0 if wino2_w else ks * ks, cip, qkv)
-                elif wino2_w:    # the y half of G^T rides in the unpack: dW[ky] = sum_ey Gt[ky][ey] wx[ey]
-                    call("adm_unpack_wgrad_wino2d", ptr(dwp), splits, ptr(dst), co, ci, cop, cip, acc, ptr(bws) if det else None,
-                         ptr(dbk) if det else None)
-                elif det:
-                    call("adm_unpack_wgrad_splits", ptr(dwp), splits, ptr(dst), co, ci, ks, cop, cip, int(qkv), acc, ptr(bws),
-                         ptr(dbk))
-                else:
-                    call("adm_unpack_wgrad", ptr(dwp), ptr(dst), co, ci, ks, cop, cip, int(qkv), acc)
-                if fused_b:
-                    finish_bias()
-                if wsink is not None:
-                    _notify(weight)
-            if bias_to is not None and not fused_b:
-                call("adm_colsum", ptr(dy), ptr(dbp), B * Ho * Wo, cop, cop, int(bias_to == "sink"))
-                finish_bias()
-
-        if side is not None:
             with torch.cuda.stream(side):
-                weight_and_bias_grads()
+                dw, db = _conv_param_pass(*params)
             dy.record_stream(side)           # keep the allocator from recycling them under the side stream
             x.record_stream(side)
         if ctx.needs_input_grad[0]:
@@ -1180,8 +1202,8 @@ class _Conv(torch.autograd.Function):
                 call("adm_resample2x", ptr(dxf), ptr(dx), B, Ho, Wo, cip, 0, 1.0, 0)
             else:
                 dx = dxf
-        if side is None:
-            weight_and_bias_grads()
+        if side is None:             # one stream: after the data gradient
+            dw, db = _conv_param_pass(*params)
         return dx, dw, db, (dy if has_res else None), None, None, None, None, None
 
 
@@ -2078,30 +2100,35 @@ def _conv_dgrad_strided(dy, weight, x_shape, stride, pad_lo):
     return dx
 
 
-def _hand_over_wgrad(weight, bias, dwp, dbp, splits=0, bws=None):
-    """The tail of a strided conv's weight gradient: unpack the tile dwp (splits > 0: sum that many partial tiles, and the rows bws
-    into dbp, in split order) into the flat gradient buffer or a new tensor, then the padded bias gradient dbp (None: not needed)
-    likewise, and announce what went to the buffer.  Returns (dw, db) for autograd: None where the buffer took it."""
+def _conv_wgrad_strided(x, dy, weight, bias, need_b, stride, pad_lo, det_ok):
+    """(dw, db) of the conv above for autograd, None where the flat gradient buffer took one; need_b: the bias wants a gradient.
+    det_ok: under ADM_DETERMINISTIC=1 the pixel-range partials go to a workspace and are summed in split order (no float atomics)."""
+    B, H, W, cip = x.shape
+    Ho, Wo = dy.shape[1], dy.shape[2]
     co, ci, ks = weight.shape[0], weight.shape[1], weight.shape[-1]
-    cop, cip = ceil32(co), ceil32(ci)
+    cop = ceil32(co)
+    det = det_ok and DETERMINISTIC
+    dbp = torch.zeros((cop,), device=dy.device, dtype=_f32) if need_b else None
+    dwp, splits, bws = _wgrad_workspace("wgrad", det, False, weight, dy, B, Ho, Wo, cip, cop, ks, 0, 0, ks * ks, need_b)
+    with _Prof("wgrad", 2.0 * B * Ho * Wo * co * ci * ks * ks, f"wgrad-k{ks}s{stride} P={B * Ho * Wo} Co={cop} Ci={cip}"):
+        size = (B, H, W, Ho, Wo, cip, cip, cop, cop, ks, stride, pad_lo)
+        if det:
+            call("adm_conv_wgrad_strided_ws", ptr(x), ptr(dy), ptr(dwp), ptr(bws), *size, splits)
+        else:
+            call("adm_conv_wgrad_strided", ptr(x), ptr(dy), ptr(dwp), ptr(dbp), *size)
     sink = _direct_grad(weight)
-    dst = sink if sink is not None else _like(weight)
-    acc = int(sink is not None)
-    if splits:
-        call("adm_unpack_wgrad_splits", ptr(dwp), splits, ptr(dst), co, ci, ks, cop, cip, 0, acc, ptr(bws), ptr(dbp))
-    else:
-        call("adm_unpack_wgrad", ptr(dwp), ptr(dst), co, ci, ks, cop, cip, 0, acc)
+    dw = _unpack_wgrad(weight, sink, dwp, ks, False, False, False, splits, bws, dbp)
     if sink is not None:
         _notify(weight)
     db = None
-    if dbp is not None:
+    if dbp is not None:          # the padded bias gradient: added into the flat gradient buffer, or its real entries for autograd
         bsink = _direct_grad(bias)
         if bsink is not None:
             call("adm_add", ptr(bsink), ptr(dbp), ptr(bsink), co)
             _notify(bias)
         else:
             db = dbp[:co].clone()
-    return (None if sink is not None else dst), db
+    return dw, db
 
 
 def conv2d_strided(x, weight, bias=None, *, stride=2, pad_lo=0, pad_hi=1):

@@ -12,8 +12,6 @@ from . import hip, ops
 from .hip import call, ptr
 from .ops import _chk, _like, _new, _Prof, ceil32, packed
 
-_f32 = torch.float32
-
 
 def _part(n_doubles: int, like):
     return _new((max(int(n_doubles), 1),), like, torch.float64)
@@ -21,9 +19,8 @@ def _part(n_doubles: int, like):
 
 # ------------------------------------------------------------------------------------------------ Downsample conv
 class _ConvDown(torch.autograd.Function):
-    """ops.conv2d_strided with a backward: weight gradient on adm_conv_wgrad_strided, data gradient as the transposed conv in GEMM
-    form (col = dy x W^T on the 1x1 kernel, then the adm_col2im gather), as ops_cond._ConvGeneric -- plus the packed-weight cache
-    of ops.packed() and, under ADM_DETERMINISTIC=1, a weight gradient without float atomics."""
+    """ops.conv2d_strided with a backward: ops._conv_wgrad_strided and ops._conv_dgrad_strided, as ops_cond._ConvGeneric -- plus the
+    packed-weight cache of ops.packed() and, under ADM_DETERMINISTIC=1, a weight gradient without float atomics."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride, pad_lo, pad_hi):
@@ -39,29 +36,9 @@ class _ConvDown(torch.autograd.Function):
         x, weight, bias = ctx.saved_tensors
         stride, pad_lo = ctx.meta
         dy = _chk(dy, "dy")
-        B, H, W, cip = x.shape
-        Ho, Wo = dy.shape[1], dy.shape[2]
-        co, ci, ks = weight.shape[0], weight.shape[1], weight.shape[-1]
-        cop = ceil32(co)
         dx = dw = db = None
         if ctx.needs_input_grad[1]:
-            need_b = bias is not None and ctx.needs_input_grad[2]
-            dbp = torch.zeros((cop,), device=dy.device, dtype=_f32) if need_b else None
-            with _Prof("wgrad", 2.0 * B * Ho * Wo * co * ci * ks * ks, f"wgrad-k{ks}s{stride} P={B * Ho * Wo} Co={cop} Ci={cip}"):
-                splits, bws = 0, None
-                if ops.DETERMINISTIC:      # pixel-range partials to a workspace, summed in split order (no float atomics)
-                    splits = hip.lib().adm_conv_wgrad_plan(B, Ho, Wo, cip, cop, ks, 0, 0)
-                    if splits < 1:
-                        raise RuntimeError(f"adm_conv_wgrad_plan failed with code {splits}")
-                    dwp = _new((splits, cop, ks * ks * cip), dy)
-                    bws = _new((splits, cop), dy) if need_b else None
-                    call("adm_conv_wgrad_strided_ws", ptr(x), ptr(dy), ptr(dwp), ptr(bws), B, H, W, Ho, Wo, cip, cip, cop, cop, ks,
-                         stride, pad_lo, splits)
-                else:
-                    dwp = _new((cop, ks * ks * cip), dy)
-                    call("adm_conv_wgrad_strided", ptr(x), ptr(dy), ptr(dwp), ptr(dbp), B, H, W, Ho, Wo, cip, cip, cop, cop, ks,
-                         stride, pad_lo)
-                dw, db = ops._hand_over_wgrad(weight, bias, dwp, dbp, splits, bws)
+            dw, db = ops._conv_wgrad_strided(x, dy, weight, bias, bias is not None and ctx.needs_input_grad[2], stride, pad_lo, True)
         if ctx.needs_input_grad[0]:
             dx = ops._conv_dgrad_strided(dy, weight, x.shape, stride, pad_lo)
         return dx, dw, db, None, None, None

@@ -9,7 +9,7 @@ import torch
 
 from . import hip, ops
 from .hip import call, ptr
-from .ops import _chk, _direct_grad, _like, _new, _notify, _Prof, ceil32, packed
+from .ops import _chk, _direct_grad, _like, _new, _notify, ceil32, packed
 
 _f32 = torch.float32
 
@@ -83,19 +83,10 @@ class _ConvGeneric(torch.autograd.Function):
         x, weight, bias = ctx.saved_tensors
         stride, pad = ctx.meta
         dy = _chk(dy, "dy")
-        B, H, W, cip = x.shape
-        Ho, Wo = dy.shape[1], dy.shape[2]
-        co, ci, ks = weight.shape[0], weight.shape[1], weight.shape[-1]
-        cop = ceil32(co)
         dx = dw = db = None
         if ctx.needs_input_grad[1]:
-            dwp = _new((cop, ks * ks * cip), dy)
-            need_b = bias is not None and ctx.needs_input_grad[2]
-            dbp = torch.zeros((cop,), device=dy.device, dtype=_f32) if need_b else None
-            with _Prof("wgrad", 2.0 * B * Ho * Wo * co * ci * ks * ks, f"wgrad-k{ks}s{stride} P={B * Ho * Wo} Co={cop} Ci={cip}"):
-                call("adm_conv_wgrad_strided", ptr(x), ptr(dy), ptr(dwp), ptr(dbp), B, H, W, Ho, Wo, cip, cip, cop, cop, ks, stride,
-                     pad)
-            dw, db = ops._hand_over_wgrad(weight, bias, dwp, dbp)
+            # det_ok=False: this conv has never taken the deterministic weight gradient (the dispatch trace pins it)
+            dw, db = ops._conv_wgrad_strided(x, dy, weight, bias, bias is not None and ctx.needs_input_grad[2], stride, pad, False)
         if ctx.needs_input_grad[0]:
             dx = ops._conv_dgrad_strided(dy, weight, x.shape, stride, pad)
         return dx, dw, db, None, None

@@ -11,6 +11,9 @@ real library.
 tests/golden/conv_dispatch_trace.json.gz holds the FULL grid.  pytest compares a fixed half of the _Conv grid plus every bf16-storage
 and strided case; ``python tests/test_conv_dispatch_host.py`` compares all of it and ``... --write`` records it again -- nothing else
 writes the fixture, and it is only ever recorded on a tree whose launches are known to be right.
+
+The ids starting with "side " run with SIDE_WGRAD on: the side stream, its event, torch.cuda.stream() and record_stream() are stubs
+that write MARKERS into the same trace, so where the weight-gradient launches sit relative to the side-stream section is pinned too.
 """
 import contextlib
 import gzip
@@ -63,6 +66,12 @@ CONV_SYMBOLS = {
 # ... and what they reach through the packed-weight cache and the end-of-backward table
 IMAGE_SYMBOLS = {"adm_pack_weight_wino", "adm_pack_weight_wino2d", "adm_split3_bf16", "adm_split2_f16", "adm_split3_rows",
                  "adm_split2_rows_f16", "adm_f32_to_bf16", "adm_unpack_wgrad_table"}
+# the side-stream section of _Conv.backward, in the trace of the "side " cases (record_stream by the role of its tensor)
+MARKERS = {"event.record", "side.wait_event", "side.enter", "side.exit", "record_stream", "queue_join"}
+# (B, H, W, cin, cout, ks, up, qkv) of the "side " cases: between them the bias routes none / sink / table / permute
+SIDE_GEOMETRIES = ((16, 16, 16, 128, 128, 3, 0, 0), (16, 8, 8, 128, 192, 3, 1, 0), (2, 32, 32, 192, 576, 1, 0, 0),
+                   (2, 32, 32, 192, 576, 1, 0, 1), (4, 32, 32, 128, 3, 3, 0, 0))
+SIDE_SWITCH_SETS = ({}, {"DETERMINISTIC": True}, {"DEFER_UNPACK": False})
 
 
 def _key(name, args):
@@ -84,7 +93,7 @@ class Recorder:
 
     def __init__(self, mp):
         from adm_amd import hip, ops, ops_ae, ops_cond
-        self.mp, self.ops, self.trace, self.dy_bound = mp, ops, [], None
+        self.mp, self.ops, self.trace, self.dy_bound, self.roles = mp, ops, [], None, {}
         if not os.path.exists(hip.LIB_PATH):
             hip.build()
         record = lambda name, *args: self.trace.append(_key(name, args))
@@ -96,6 +105,27 @@ class Recorder:
         mp.setattr(ops, "_reg_amax", lambda t, slot: self.trace.append("_reg_amax " + ("p" if slot is not None else "0")))
         for name, v in STATE.items():
             mp.setattr(ops, name, v() if callable(v) else v)
+        # the side-stream section (reached only with SIDE_WGRAD on): every stream / event operation leaves a marker
+        mark = self.trace.append
+
+        class Event:
+            record = lambda self: mark("event.record")
+
+        class Side:
+            wait_event = lambda self, ev: mark("side.wait_event")
+
+        @contextlib.contextmanager
+        def on_stream(st):
+            mark("side.enter")
+            yield
+            mark("side.exit")
+
+        side = Side()
+        mp.setattr(ops, "_wgrad_stream", lambda: side)
+        mp.setattr(torch.cuda, "Event", Event)
+        mp.setattr(torch.cuda, "stream", on_stream)
+        mp.setattr(torch.Tensor, "record_stream", lambda t, st: mark("record_stream " + self.roles.get(t.data_ptr(), "other")))
+        mp.setattr(ops, "_queue_join_at_end_of_backward", lambda: mark("queue_join"))
 
     def case(self, switches, binv, fn):
         """(forward launches, backward launches, y carries a bound) of fn() -> (y, dy), under DEFAULTS + switches; binv: inside
@@ -141,7 +171,9 @@ def _conv_case(rec, geom, qkv, bias, res, amax_in, amax_dy, direct, x16=False):
     bound = torch.zeros(ops.AMAX_FLOATS)
     rec.dy_bound = bound if amax_dy else None
     y = ops.conv2d(x, w, b, r, up=bool(up), qkv=bool(qkv), amax=bound if amax_in else None)
-    return y, torch.empty_like(y)
+    dy = torch.empty_like(y)
+    rec.roles = {x.data_ptr(): "x", dy.data_ptr(): "dy"}
+    return y, dy
 
 
 def _strided_case(rec, entry, ks, stride, pads, co, bias, direct):
@@ -184,6 +216,12 @@ def cases(rec):
     for (entry, ks, stride, pads), co, bias, direct, det in itertools.product(strided, (32, 3), (0, 1), (0, 1), (0, 1)):
         cid = f"{entry} k{ks}s{stride}p{pads[0]}{pads[1]} co{co} b{bias}d{direct} det{det}"
         out[cid] = ({"DETERMINISTIC": bool(det)}, 0, lambda a=(entry, ks, stride, pads, co, bias, direct): _strided_case(rec, *a))
+    # SIDE_WGRAD on; d0 (gradients through autograd) must show no side section
+    for geom, sw, bias, bounds, direct in itertools.product(SIDE_GEOMETRIES, SIDE_SWITCH_SETS, (0, 1), (0, 1), (1, 0)):
+        if not direct and (sw or not bias or bounds):
+            continue
+        cid = f"side {'x'.join(map(str, geom[:7]))} q{geom[7]}b{bias}a{bounds}g{bounds}d{direct} {sw_name(sw)}"
+        out[cid] = (dict(sw, SIDE_WGRAD=True), 0, lambda a=(geom[:7], geom[7], bias, 0, bounds, bounds, direct): _conv_case(rec, *a))
     return out
 
 
@@ -214,7 +252,7 @@ def write_fixture(got):
 
 
 def symbols(traces):
-    return {k.split(" ", 1)[0] for fwd, bwd, _ in traces.values() for k in fwd + bwd} - {"_get_amax", "_reg_amax"}
+    return {k.split(" ", 1)[0] for fwd, bwd, _ in traces.values() for k in fwd + bwd} - {"_get_amax", "_reg_amax"} - MARKERS
 
 
 def differing(got, want):
@@ -238,6 +276,21 @@ def test_fixture_covers_every_conv_symbol():
     # a fp16-format data gradient looked its bound up, a 1x1 one handed its own on, a 1x1 forward left one on y
     flat = [k for fwd, bwd, _ in want.values() for k in bwd]
     assert "_get_amax" in flat and "_reg_amax p" in flat and any(amax for _, _, amax in want.values())
+
+
+def test_fixture_pins_the_side_stream_section():
+    want = load_fixture()
+    marker = lambda k: k.split(" ", 1)[0] in MARKERS
+    wgrad = lambda k: k.startswith(("adm_conv_wgrad", "adm_gemm_wgrad"))
+    inside = 0
+    for cid, (_, bwd, _) in want.items():
+        if not cid.startswith("side "):
+            assert not any(map(marker, bwd)), cid
+        elif "d0 " in cid:          # nothing can be accumulated directly: everything stays on the main stream
+            assert any(map(wgrad, bwd)) and not any(map(marker, bwd)), cid
+        elif "side.enter" in bwd:
+            inside += any(map(wgrad, bwd[bwd.index("side.enter"):bwd.index("side.exit")]))
+    assert inside
 
 
 if __name__ == "__main__":
