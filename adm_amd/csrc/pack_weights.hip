@@ -4,6 +4,7 @@
 // model for sampling), so simplicity beats tuning here.
 #include "common.h"
 #include "split_format.h"
+#include <type_traits>
 
 namespace {
 
@@ -102,11 +103,43 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ a
   }
 }
 
+// Destinations of the table kernel come out of an int64 table: said to be global memory, so that the stores are global_store_* and
+// not flat_store_* (which also count against the LDS counter the tile reads wait on).
+template <typename T> using gptr = __attribute__((address_space(1))) T*;
+template <typename T> __device__ __forceinline__ gptr<T> table_ptr(long v) { return (gptr<T>)reinterpret_cast<T*>(v); }
+// a[0..3] -> the three bf16 terms (split3_store's arithmetic), each as one 8-byte store
+__device__ __forceinline__ void split3_store4(const float (&a)[4], gptr<unsigned short> d, long term) {
+  unsigned t[3][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float r1 = a[j] - bf16_head(a[j]), r2 = r1 - bf16_head(r1);
+    t[0][j] = bf16_bits(a[j]); t[1][j] = bf16_bits(r1); t[2][j] = bf16_bits(r2);
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) *(gptr<u32x2>)(d + k * term) = u32x2{t[k][0] | (t[k][1] << 16), t[k][2] | (t[k][3] << 16)};
+}
+// a[0..3] (already scaled) -> the two fp16 terms (split2's arithmetic), each as one 8-byte store
+__device__ __forceinline__ void split2_store4(const float (&a)[4], gptr<unsigned short> d, long term) {
+  unsigned t[2][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    _Float16 h0, h1;
+    split2(a[j], h0, h1);
+    t[0][j] = __builtin_bit_cast(unsigned short, h0); t[1][j] = __builtin_bit_cast(unsigned short, h1);
+  }
+#pragma unroll
+  for (int k = 0; k < 2; ++k) *(gptr<u32x2>)(d + k * term) = u32x2{t[k][0] | (t[k][1] << 16), t[k][2] | (t[k][3] << 16)};
+}
+
 // One launch for ALL layers of a model: table[e] = one row of PT_COLS int64 per layer (the columns: adm_pack_weight_table in
 // include/adm_hip.h; adm_amd/ops.py fills them under the same names).  One workgroup per 32
 // (out-channel) x 32 (in-channel) tile of one layer: the tile's taps-interleaved source runs (32*taps contiguous floats per
 // out-channel) go through LDS once and leave as 128-byte row segments of every operand layout, so reads and writes are
 // coalesced (the previous element-per-thread gather ran at 0.7 TB/s and cost 3.8 ms per optimiser step).
+// The 16-bit images (split_format.h) leave as runs of four consecutive k of one row per (plane, term): thread (row = tid / 8,
+// run = tid % 8) of the 32 x 32 tile, so that one store instruction of a wave covers eight rows of each of the tile's two k-chunks
+// -- two contiguous 256-byte pieces of the [rows][16] blocks -- where the element-per-lane map wrote 2 bytes per lane into 64-byte
+// pieces.  PT_FWD / PT_BWD may be 0: most layers never read their f32 operands (the split kernels read the images).
 enum : int { PT_SRC, PT_FWD, PT_BWD, PT_CO, PT_CI, PT_TAPS, PT_CO_PAD, PT_CI_PAD, PT_QKV, PT_TILE_BEGIN, PT_WF, PT_WB, PT_W2F, PT_W2B, PT_W2F6,
              PT_W2B6, PT_G6F, PT_G6B, PT_W2FH, PT_W2BH, PT_H3_SCALE, PT_H3_FLAG, PT_G6FH, PT_G6BH, PT_COLS };
 static_assert(PT_COLS == 24, "a row of adm_pack_weight_table has 24 columns (include/adm_hip.h)");
@@ -119,53 +152,84 @@ __global__ __launch_bounds__(256) void pack_table_kernel(const long* __restrict_
     if (table[(long)mid * PT_COLS + PT_TILE_BEGIN] <= (long)blockIdx.x) lo = mid; else hi = mid - 1;
   }
   const long* t = table + (long)lo * PT_COLS;
-  const float* __restrict__ w = reinterpret_cast<const float*>(t[PT_SRC]);
-  float* __restrict__ fwd = reinterpret_cast<float*>(t[PT_FWD]);
-  float* __restrict__ bwd = reinterpret_cast<float*>(t[PT_BWD]);
+  const gptr<const float> w = table_ptr<const float>(t[PT_SRC]);
+  const gptr<float> fwd = table_ptr<float>(t[PT_FWD]);
+  const gptr<float> bwd = table_ptr<float>(t[PT_BWD]);
   const int Co = (int)t[PT_CO], Ci = (int)t[PT_CI], taps = (int)t[PT_TAPS], Co_pad = (int)t[PT_CO_PAD], Ci_pad = (int)t[PT_CI_PAD], qkv = (int)t[PT_QKV];
-  float* __restrict__ wf = reinterpret_cast<float*>(t[PT_WF]);
-  float* __restrict__ wb = reinterpret_cast<float*>(t[PT_WB]);
+  const gptr<float> wf = table_ptr<float>(t[PT_WF]);
+  const gptr<float> wb = table_ptr<float>(t[PT_WB]);
   const int local = (int)((long)blockIdx.x - t[PT_TILE_BEGIN]);
   const int tiles_ci = Ci_pad >> 5;
   const int co0 = (local / tiles_ci) << 5, ci0 = (local % tiles_ci) << 5;
   const int run = 32 * taps;                       // floats per out-channel row of the tile
   const int n = 32 * run;
-  for (int e = threadIdx.x; e < n; e += 256) {
-    const int r = e / run, c = e - r * run;        // c = ci_l * taps + tap
-    const int cop = co0 + r, ci = ci0 + c / taps;
-    float v = 0.f;
-    if (cop < Co && ci < Ci) v = w[((long)(qkv ? qkv_to_ref(cop) : cop) * Ci + ci0) * taps + c];
-    tile[r][c] = v;
-  }
+  // NB loads in flight per lane, then their NB LDS writes (one load per trip left the read side waiting out a memory round trip
+  // 4 * taps times per tile); n / 256 = 4 * taps trips: twelve at a time for the 3x3 layers, four otherwise
+  auto fill = [&](auto batch) {
+    constexpr int NB = decltype(batch)::value;
+    for (int e0 = threadIdx.x; e0 < n; e0 += 256 * NB) {
+      float v[NB];
+      int at[NB];
+#pragma unroll
+      for (int u = 0; u < NB; ++u) {
+        const int e = e0 + u * 256;
+        const int r = e / run, c = e - r * run;    // c = ci_l * taps + tap
+        const int cop = co0 + r, ci = ci0 + c / taps;
+        v[u] = 0.f;
+        if (cop < Co && ci < Ci) v[u] = w[((long)(qkv ? qkv_to_ref(cop) : cop) * Ci + ci0) * taps + c];
+        at[u] = r * (32 * 9 + 1) + c;
+      }
+#pragma unroll
+      for (int u = 0; u < NB; ++u) (&tile[0][0])[at[u]] = v[u];
+    }
+  };
+  if (taps % 3 == 0) fill(std::integral_constant<int, 12>{}); else fill(std::integral_constant<int, 4>{});
   __syncthreads();
   // 1x1 layers on conv_gemm_x6.hip: both operands in both split formats of split_format.h, rows_image_offset: three bf16 terms
   // (PT_G6F, PT_G6B) and two fp16 terms of scale * w (PT_G6FH, PT_G6BH)
-  unsigned short* __restrict__ g6f = reinterpret_cast<unsigned short*>(t[PT_G6F]);
-  unsigned short* __restrict__ g6b = reinterpret_cast<unsigned short*>(t[PT_G6B]);
-  unsigned short* __restrict__ g6fh = reinterpret_cast<unsigned short*>(t[PT_G6FH]);
-  unsigned short* __restrict__ g6bh = reinterpret_cast<unsigned short*>(t[PT_G6BH]);
+  const gptr<unsigned short> g6f = table_ptr<unsigned short>(t[PT_G6F]);
+  const gptr<unsigned short> g6b = table_ptr<unsigned short>(t[PT_G6B]);
+  const gptr<unsigned short> g6fh = table_ptr<unsigned short>(t[PT_G6FH]);
+  const gptr<unsigned short> g6bh = table_ptr<unsigned short>(t[PT_G6BH]);
   const float hscale = __uint_as_float((unsigned)t[PT_H3_SCALE]);
   bool hbad = false;                               // a scaled weight left the fp16 range
-  auto store_rows = [&](unsigned short* d6, unsigned short* dh, int rows, int n, int k, float v) {
-    if (d6) split3_store(v, d6 + rows_image_offset(3, rows, n, k), split_term_stride(rows));
-    if (dh) {
-      hbad |= split_f16_overflow(v * hscale);
-      split2_store(v * hscale, dh + rows_image_offset(2, rows, n, k), split_term_stride(rows));
+  if (fwd) {
+    for (int e = threadIdx.x; e < n; e += 256) {   // forward operand [Co_pad][taps][Ci_pad]: ci fastest
+      const int ci_l = e & 31, rest = e >> 5;
+      const int tap = rest % taps, co_l = rest / taps;
+      fwd[((long)(co0 + co_l) * taps + tap) * Ci_pad + ci0 + ci_l] = tile[co_l][ci_l * taps + tap];
     }
-  };
-  for (int e = threadIdx.x; e < n; e += 256) {     // forward operand [Co_pad][taps][Ci_pad]: ci fastest
-    const int ci_l = e & 31, rest = e >> 5;
-    const int tap = rest % taps, co_l = rest / taps;
-    const float v = tile[co_l][ci_l * taps + tap];
-    fwd[((long)(co0 + co_l) * taps + tap) * Ci_pad + ci0 + ci_l] = v;
-    if (taps == 1) store_rows(g6f, g6fh, Co_pad, co0 + co_l, ci0 + ci_l, v);
   }
-  for (int e = threadIdx.x; e < n; e += 256) {     // data-gradient operand [Ci_pad][taps flipped][Co_pad]: co fastest
-    const int co_l = e & 31, rest = e >> 5;
-    const int tapf = rest % taps, ci_l = rest / taps;
-    const float v = tile[co_l][ci_l * taps + (taps - 1 - tapf)];
-    bwd[((long)(ci0 + ci_l) * taps + tapf) * Co_pad + co0 + co_l] = v;
-    if (taps == 1) store_rows(g6b, g6bh, Ci_pad, ci0 + ci_l, co0 + co_l, v);
+  if (bwd) {
+    for (int e = threadIdx.x; e < n; e += 256) {   // data-gradient operand [Ci_pad][taps flipped][Co_pad]: co fastest
+      const int co_l = e & 31, rest = e >> 5;
+      const int tapf = rest % taps, ci_l = rest / taps;
+      bwd[((long)(ci0 + ci_l) * taps + tapf) * Co_pad + co0 + co_l] = tile[co_l][ci_l * taps + (taps - 1 - tapf)];
+    }
+  }
+  // the image maps: row r4 of the tile, columns c4 .. c4 + 3 (one run of a 16-k chunk)
+  const int r4 = threadIdx.x >> 3, c4 = (threadIdx.x & 7) << 2;
+  if (taps == 1) {
+#pragma unroll
+    for (int which = 0; which < 2; ++which) {      // 0: rows = couts, k = cin; 1 (data gradient): rows = cins, k = cout
+      const gptr<unsigned short> d6 = which ? g6b : g6f;
+      const gptr<unsigned short> dh = which ? g6bh : g6fh;
+      if (!d6 && !dh) continue;
+      float v[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = which ? tile[c4 + j][r4] : tile[r4][c4 + j];
+      const int rows = which ? Ci_pad : Co_pad;
+      const int nn = (which ? ci0 : co0) + r4, k = (which ? co0 : ci0) + c4;
+      if (d6) split3_store4(v, d6 + rows_image_offset(3, rows, nn, k), split_term_stride(rows));
+      if (dh) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          v[j] = v[j] * hscale;
+          hbad |= split_f16_overflow(v[j]);
+        }
+        split2_store4(v, dh + rows_image_offset(2, rows, nn, k), split_term_stride(rows));
+      }
+    }
   }
   int* __restrict__ hflag = reinterpret_cast<int*>(t[PT_H3_FLAG]);
   if (hbad && hflag) *hflag = 1;                   // the host falls back to the bf16 format
@@ -188,47 +252,75 @@ __global__ __launch_bounds__(256) void pack_table_kernel(const long* __restrict_
   // 2-D Winograd F(2x2, 3x3) operands (conv_wino2d.hip): U = G g G^T, plane ey * 4 + ex
   // ... and both split formats of them (split_format.h, wino_image_offset) for conv_wino2d_x6.hip: three bf16 terms (PT_W2F6, PT_W2B6)
   // and two fp16 terms of scale * U (PT_W2FH, PT_W2BH); 0 when unused
-  float* __restrict__ wf2 = reinterpret_cast<float*>(t[PT_W2F]);
-  float* __restrict__ wb2 = reinterpret_cast<float*>(t[PT_W2B]);
-  unsigned short* __restrict__ wf6 = reinterpret_cast<unsigned short*>(t[PT_W2F6]);
-  unsigned short* __restrict__ wb6 = reinterpret_cast<unsigned short*>(t[PT_W2B6]);
-  unsigned short* __restrict__ wfh = reinterpret_cast<unsigned short*>(t[PT_W2FH]);
-  unsigned short* __restrict__ wbh = reinterpret_cast<unsigned short*>(t[PT_W2BH]);
-  if (wf2 || wb2 || wf6 || wb6 || wfh || wbh) {
+  const gptr<float> wf2 = table_ptr<float>(t[PT_W2F]);
+  const gptr<float> wb2 = table_ptr<float>(t[PT_W2B]);
+  const gptr<unsigned short> wf6 = table_ptr<unsigned short>(t[PT_W2F6]);
+  const gptr<unsigned short> wb6 = table_ptr<unsigned short>(t[PT_W2B6]);
+  const gptr<unsigned short> wfh = table_ptr<unsigned short>(t[PT_W2FH]);
+  const gptr<unsigned short> wbh = table_ptr<unsigned short>(t[PT_W2BH]);
+  // G g of the three filter rows of g (flipped for the data gradient): tr[a][ex]
+  auto half_transform = [](const float* g, int which, float (&tr)[3][4]) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const int ra = which ? 2 - a : a;                // flipped filter for the data gradient
+      const float g0 = which ? g[ra * 3 + 2] : g[ra * 3], g1 = g[ra * 3 + 1], g2 = which ? g[ra * 3] : g[ra * 3 + 2];
+      tr[a][0] = g0; tr[a][1] = (g0 + g1 + g2) * 0.5f; tr[a][2] = (g0 - g1 + g2) * 0.5f; tr[a][3] = g2;
+    }
+  };
+  if (wf2 || wb2) {                                  // the f32 planes: one element per lane, 128-byte row segments
     const long plane2 = (long)Co_pad * Ci_pad;
     for (int e = threadIdx.x; e < 32 * 32; e += 256) {
       // forward operand: ci fastest; data-gradient operand: co fastest -> two index maps over the same 32 x 32 tile
       for (int which = 0; which < 2; ++which) {
-        float* __restrict__ dst = which ? wb2 : wf2;
-        unsigned short* __restrict__ dst6 = which ? wb6 : wf6;
-        unsigned short* __restrict__ dsth = which ? wbh : wfh;
-        if (!dst && !dst6 && !dsth) continue;
+        const gptr<float> dst = which ? wb2 : wf2;
+        if (!dst) continue;
         const int fast = e & 31, slow = e >> 5;
         const int co_l = which ? fast : slow, ci_l = which ? slow : fast;
-        const float* g = &tile[co_l][ci_l * 9];
         float tr[3][4];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          const int ra = which ? 2 - a : a;            // flipped filter for the data gradient
-          const float g0 = which ? g[ra * 3 + 2] : g[ra * 3], g1 = g[ra * 3 + 1], g2 = which ? g[ra * 3] : g[ra * 3 + 2];
-          tr[a][0] = g0; tr[a][1] = (g0 + g1 + g2) * 0.5f; tr[a][2] = (g0 - g1 + g2) * 0.5f; tr[a][3] = g2;
-        }
+        half_transform(&tile[co_l][ci_l * 9], which, tr);
         // (rows, cols) = (Co_pad, Ci_pad) forward, (Ci_pad, Co_pad) data gradient
-        const int rows = which ? Ci_pad : Co_pad, cols = which ? Co_pad : Ci_pad;
-        const int n = which ? ci0 + ci_l : co0 + co_l, c = which ? co0 + co_l : ci0 + ci_l;
-        const long o = (long)n * cols + c;
+        const int cols = which ? Co_pad : Ci_pad;
+        const long o = (long)(which ? ci0 + ci_l : co0 + co_l) * cols + (which ? co0 + co_l : ci0 + ci_l);
 #pragma unroll
         for (int ex = 0; ex < 4; ++ex) {
           const float c0 = tr[0][ex], c1 = tr[1][ex], c2 = tr[2][ex];
           const float u[4] = {c0, (c0 + c1 + c2) * 0.5f, (c0 - c1 + c2) * 0.5f, c2};
 #pragma unroll
-          for (int ey = 0; ey < 4; ++ey) {
-            if (dst) dst[(long)(ey * 4 + ex) * plane2 + o] = u[ey];
-            if (dst6) split3_store(u[ey], dst6 + wino_image_offset(3, ey, ex, rows, cols, n, c), split_term_stride(rows));
-            if (dsth) {
-              hbad |= split_f16_overflow(u[ey] * hscale);
-              split2_store(u[ey] * hscale, dsth + wino_image_offset(2, ey, ex, rows, cols, n, c), split_term_stride(rows));
+          for (int ey = 0; ey < 4; ++ey) dst[(long)(ey * 4 + ex) * plane2 + o] = u[ey];
+        }
+      }
+    }
+  }
+  if (wf6 || wb6 || wfh || wbh) {                    // the split images: four k of one row per lane and (plane, term)
+#pragma unroll
+    for (int which = 0; which < 2; ++which) {
+      const gptr<unsigned short> dst6 = which ? wb6 : wf6;
+      const gptr<unsigned short> dsth = which ? wbh : wfh;
+      if (!dst6 && !dsth) continue;
+      float tr[4][3][4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) half_transform(which ? &tile[c4 + j][r4 * 9] : &tile[r4][(c4 + j) * 9], which, tr[j]);
+      const int rows = which ? Ci_pad : Co_pad, cols = which ? Co_pad : Ci_pad;
+      const int nn = (which ? ci0 : co0) + r4, c = (which ? co0 : ci0) + c4;
+#pragma unroll
+      for (int ex = 0; ex < 4; ++ex) {
+        float u[4][4];                                 // u[j][ey]
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float c0 = tr[j][0][ex], c1 = tr[j][1][ex], c2 = tr[j][2][ex];
+          u[j][0] = c0; u[j][1] = (c0 + c1 + c2) * 0.5f; u[j][2] = (c0 - c1 + c2) * 0.5f; u[j][3] = c2;
+        }
+#pragma unroll
+        for (int ey = 0; ey < 4; ++ey) {
+          float v[4] = {u[0][ey], u[1][ey], u[2][ey], u[3][ey]};
+          if (dst6) split3_store4(v, dst6 + wino_image_offset(3, ey, ex, rows, cols, nn, c), split_term_stride(rows));
+          if (dsth) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              v[j] = v[j] * hscale;
+              hbad |= split_f16_overflow(v[j]);
             }
+            split2_store4(v, dsth + wino_image_offset(2, ey, ex, rows, cols, nn, c), split_term_stride(rows));
           }
         }
       }

@@ -85,12 +85,47 @@ _H3_IMAGES = ("w2fh", "w2bh", "g6fh", "g6bh")              # the images that can
 
 
 class _Packed:
-    __slots__ = ("key", "fwd", "bwd", "bias", "fwd16", "bwd16", "src", "h3_off") + tuple(name for name, _ in _PACK_IMAGES)
+    """The f32 operands `fwd` / `bwd` are refreshed ON DEMAND: most layers run on the split kernels, which read the 16-bit images, and
+    would have both f32 operands rewritten by every repack without anyone reading them.  Reading the attribute is the use:
+    repack_all() refreshes, in its one launch, the operands that were read since the previous repack and leaves the others stale;
+    the next read of a stale operand refreshes that one with a per-layer adm_pack_weight launch (on the reader's stream) and brings
+    it back into the table.  A layer on the direct kernels reads every step, so it never leaves the table.  Bookkeeping goes around
+    the properties: the raw slots `_fwd` / `_bwd`, or _operand(ent, which, count=False) for a one-time read that needs current values."""
+    __slots__ = (("key", "_fwd", "_bwd", "bias", "fwd16", "bwd16", "src", "h3_off", "_read", "_stale", "_owner")
+                 + tuple(name for name, _ in _PACK_IMAGES))
 
     def __init__(self):
         for name in self.__slots__:
             setattr(self, name, None)
         self.h3_off = False          # True: a fp16 image of this entry overflowed (_h3_weight_image), the layer stays on the bf16 format
+        self._read = 3               # bit 0 / 1: fwd / bwd was read since the last repack (an entry made by hand: always refreshed)
+        self._stale = 0              # bit 0 / 1: fwd / bwd was left out of the last repack(s)
+
+    fwd = property(lambda self: _operand(self, 0), lambda self, t: setattr(self, "_fwd", t))
+    bwd = property(lambda self: _operand(self, 1), lambda self, t: setattr(self, "_bwd", t))
+
+
+operand_refreshes = 0       # diagnostics: per-layer launches that refreshed a stale f32 operand (none in a steady training loop)
+
+
+def _operand(ent: "_Packed", which: int, count: bool = True):
+    """The current f32 operand of a packed entry: which = 0 forward, 1 data gradient (the properties _Packed.fwd / .bwd).  count=False:
+    a one-time read (the source of an image's first build) that must not keep the operand in the repack table."""
+    global operand_refreshes
+    bit = 1 << which
+    if ent._stale & bit:
+        w = ent._owner() if ent._owner is not None else None
+        if w is None:
+            raise RuntimeError("adm_amd: a packed operand outlived its parameter")
+        co, ci, ks, qkv = ent.src
+        w = _chk(w.detach(), "weight")
+        call("adm_pack_weight", ptr(w), None if which else ptr(ent._fwd), ptr(ent._bwd) if which else None, co, ci, ks, ceil32(co),
+             ceil32(ci), int(qkv))
+        ent._stale &= ~bit
+        operand_refreshes += 1
+    if count:
+        ent._read |= bit
+    return ent._bwd if which else ent._fwd
 
 
 # Contraction precision of the conv / Linear kernels: "f32" (default: exact fp32 MFMA) or "bf16" (BASELINE
@@ -261,7 +296,7 @@ def _h3_flag_tensor(like):
 def _h3_weight_image(ent: "_Packed", split) -> bool:
     """Runs split(flag) -- a weight split kernel that raises the int32 device flag it is given when a scaled weight leaves the fp16
     range -- on a fresh flag and reads it back: False (and the entry is marked to stay on the bf16 format) when the image overflowed."""
-    flag = torch.zeros(1, device=ent.fwd.device, dtype=torch.int32)
+    flag = torch.zeros(1, device=ent._fwd.device, dtype=torch.int32)
     split(flag)
     if torch.cuda.is_current_stream_capturing():     # (no read-back inside a capture: the sampler packs in its eager warm-up first)
         return True
@@ -445,7 +480,7 @@ def _gemm_x6_operand(ent: "_Packed", which: int):
         return getattr(ent, name)
 
     def build():
-        src = ent.bwd if which else ent.fwd
+        src = _operand(ent, which, count=False)      # (a one-time read: it does not keep the f32 operand in the repack table)
         img = torch.empty((3,) + tuple(src.shape), device=src.device, dtype=torch.bfloat16)
         call("adm_split3_rows", ptr(src), ptr(img), src.shape[0], src.shape[1], src.shape[1])
         return (img,)
@@ -462,7 +497,7 @@ def _gemm_h3_operand(ent: "_Packed", which: int):
         return getattr(ent, name)
 
     def build():
-        src = ent.bwd if which else ent.fwd
+        src = _operand(ent, which, count=False)      # (a one-time read: it does not keep the f32 operand in the repack table)
         img = torch.empty((2,) + tuple(src.shape), device=src.device, dtype=torch.float16)
         ok = _h3_weight_image(ent, lambda flag: call("adm_split2_rows_f16", ptr(src), ptr(img), src.shape[0], src.shape[1], src.shape[1],
                                                      H3_WSCALE, ptr(flag)))
@@ -489,9 +524,10 @@ def packed(weight: torch.Tensor, bias: Optional[torch.Tensor], ks: int, qkv: boo
     ent = _Packed()
     ent.key = key
     ent.src = (co, ci, ks, qkv)
-    ent.fwd = _new((cop, ks * ks * cip), w)
-    ent.bwd = _new((cip, ks * ks * cop), w)
-    call("adm_pack_weight", ptr(w), ptr(ent.fwd), ptr(ent.bwd), co, ci, ks, cop, cip, int(qkv))
+    ent._fwd = _new((cop, ks * ks * cip), w)
+    ent._bwd = _new((cip, ks * ks * cop), w)
+    ent._read, ent._owner = 0, weakref.ref(weight)      # both current and not read yet (see _Packed)
+    call("adm_pack_weight", ptr(w), ptr(ent._fwd), ptr(ent._bwd), co, ci, ks, cop, cip, int(qkv))
     if bias is not None and not qkv and cop == co:
         ent.bias = _chk(bias.detach(), "bias")          # usable as is
     elif bias is not None:
@@ -518,7 +554,8 @@ def invalidate_packed():
 # Registry of live packed parameters, so that the optimiser can refresh ALL packed operands with one launch
 # (adm_pack_weight_table) instead of two small launches per layer on first use after every step.
 _pack_registry: dict = {}
-_pack_table = None          # (device int64 table, [entries], total 32x32 tiles, host rows)
+_pack_table = None          # (device int64 table, [entries], total 32x32 tiles, host rows, the entries' _read masks the table was made for)
+pack_table_builds = 0       # diagnostics: uploads of that table (a blocking copy: none in a steady training loop)
 
 
 _H3_WSCALE_BITS = int.from_bytes(__import__("struct").pack("<f", H3_WSCALE), "little")
@@ -526,9 +563,10 @@ _H3_WSCALE_BITS = int.from_bytes(__import__("struct").pack("<f", H3_WSCALE), "li
 
 def _pack_row(src: torch.Tensor, ent: _Packed, co: int, ci: int, ks: int, qkv: bool, tile_begin: int) -> list:
     """The row of adm_pack_weight_table that re-derives every operand of the packed entry `ent` from the OIHW / [out, in] tensor `src`:
-    fwd, bwd and whichever images exist (_PACK_IMAGES); tile_begin = the 32 x 32 tiles of the rows before this one."""
+    fwd, bwd and whichever images exist (_PACK_IMAGES); tile_begin = the 32 x 32 tiles of the rows before this one.  (Always both f32
+    operands: repack_all() zeroes the column of one that nobody read.)"""
     row = [0] * PACK_TABLE_COLS
-    row[PT_SRC], row[PT_FWD], row[PT_BWD] = src.data_ptr(), ent.fwd.data_ptr(), ent.bwd.data_ptr()
+    row[PT_SRC], row[PT_FWD], row[PT_BWD] = src.data_ptr(), ent._fwd.data_ptr(), ent._bwd.data_ptr()
     row[PT_CO], row[PT_CI], row[PT_TAPS], row[PT_CO_PAD], row[PT_CI_PAD] = co, ci, ks * ks, ceil32(co), ceil32(ci)
     row[PT_QKV], row[PT_TILE_BEGIN] = int(qkv), tile_begin
     for name, col in _PACK_IMAGES:
@@ -543,8 +581,9 @@ def _pack_row(src: torch.Tensor, ent: _Packed, co: int, ci: int, ks: int, qkv: b
 
 def repack_all():
     """Called by the fused optimiser after it rewrote the flat parameter buffer: re-derives every registered packed
-    operand in place with one kernel launch and marks the entries current."""
-    global _pack_table, _pack_epoch, _h3_checks, FP16X3
+    operand in place with one kernel launch and marks the entries current.  Of the f32 operands only those that were read since the
+    previous repack are refreshed (_Packed); the device table is rebuilt when that set changes."""
+    global _pack_table, _pack_epoch, _h3_checks, FP16X3, pack_table_builds
     _pack_epoch += 1
     if _h3_flag is not None and FP16X3:
         _h3_checks += 1
@@ -566,16 +605,24 @@ def repack_all():
             ents.append((wref, bref, ks, qkv, ent))
         if not rows:
             return
-        dev = ents[0][0]().device
-        _pack_table = (torch.tensor(rows, dtype=torch.int64, device=dev), ents, tiles, rows)
-    table, ents, total_tiles, rows = _pack_table
+        _pack_table = (None, ents, tiles, rows, None)
+    table, ents, total_tiles, rows, masks = _pack_table
     for (wref, bref, ks, qkv, ent), row in zip(ents, rows):      # storage moved or parameter died -> rebuild lazily
         w = wref()
         if w is None or w.data_ptr() != row[PT_SRC] or getattr(w, "_adm_packed", None) is not ent:
             _pack_table = None
             return
+    read = tuple(e[4]._read for e in ents)
+    if table is None or read != masks:
+        masked = [row if m == 3 else row[:PT_FWD] + [row[PT_FWD] * (m & 1), row[PT_BWD] * (m >> 1)] + row[PT_BWD + 1:]
+                  for row, m in zip(rows, read)]
+        table = torch.tensor(masked, dtype=torch.int64, device=ents[0][0]().device)
+        _pack_table = (table, ents, total_tiles, rows, read)
+        pack_table_builds += 1
     call("adm_pack_weight_table", ptr(table), len(ents), total_tiles)
-    for wref, bref, ks, qkv, ent in ents:
+    for (wref, bref, ks, qkv, ent), m in zip(ents, read):
+        ent._stale |= 3 & ~m
+        ent._read = 0
         w = wref()
         b = bref() if bref is not None else None
         co = w.shape[0]
@@ -1521,6 +1568,7 @@ class AffineGroup:
             w, b = lin.weight, lin.bias
             ent = packed(w, b, 1, False)
             want = self.wcat.data_ptr() + 4 * o * self.K
+            # (reading ent.fwd is also what keeps this layer's rows of wcat in the repack table: the grouped GEMM reads them every step)
             if ent.fwd.data_ptr() != want:                  # new entry (first use, load_state_dict, ...): move its operand in
                 view = self.wcat[o:o + n]
                 view.copy_(ent.fwd)
@@ -1549,12 +1597,14 @@ class AffineGroup:
             self.wcat_t = torch.empty((self.K, self.total), device=self.wcat.device, dtype=_f32)
             self.sig_t = self.t_table = None
         if self.sig_t != self.sig:
-            # the LDS-tiled table kernel with ONE row: the [total][K] operand as the source of its own forward image (an in-place
-            # identity) and of the [K][total] data-gradient image (adm_pack_weight's element-wise transpose: 0.50 ms; this: ~0.13)
+            # the LDS-tiled table kernel with ONE row: the [total][K] operand as the source of the [K][total] data-gradient image alone
+            # (PT_FWD = 0; adm_pack_weight's element-wise transpose: 0.50 ms; this: ~0.09)
             if self.t_table is None:
                 ent = _Packed()       # (no images; total and K are multiples of 32, so the row's padded sizes are the sizes themselves)
                 ent.fwd, ent.bwd = self.wcat, self.wcat_t
-                self.t_table = torch.tensor([_pack_row(self.wcat, ent, self.total, self.K, 1, False, 0)], dtype=torch.int64).to(self.wcat.device)
+                row = _pack_row(self.wcat, ent, self.total, self.K, 1, False, 0)
+                row[PT_FWD] = 0
+                self.t_table = torch.tensor([row], dtype=torch.int64).to(self.wcat.device)
             call("adm_pack_weight_table", ptr(self.t_table), 1, (self.total // 32) * (self.K // 32))
             self.sig_t = self.sig
         return self.wcat_t

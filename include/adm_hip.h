@@ -244,8 +244,8 @@ int adm_pack_weight(const float* w, float* wp_fwd, float* wp_bwd, int Co, int Ci
 /* adm_pack_weight (+ adm_pack_weight_wino) for every layer of a model in ONE launch (used after each optimiser step).
  * table = device array of n_entries rows of 24 int64 (the PT_* names of csrc/pack_weights.hip and adm_amd/ops.py):
  *    0 src          the OIHW / [out, in] parameter
- *    1 fwd          wp_fwd of adm_pack_weight (required)
- *    2 bwd          wp_bwd of adm_pack_weight (required)
+ *    1 fwd          wp_fwd of adm_pack_weight; 0 when unused
+ *    2 bwd          wp_bwd of adm_pack_weight; 0 when unused
  *    3 Co, 4 Ci, 5 taps = ks*ks, 6 Co_pad, 7 Ci_pad, 8 qkv   as adm_pack_weight
  *    9 tile_begin   exclusive prefix sum of (Co_pad/32)*(Ci_pad/32) in row order; total_tiles = the sum over all rows
  *   10 wf, 11 wb    1-D Winograd operands of adm_pack_weight_wino (forward, data gradient)
@@ -256,8 +256,9 @@ int adm_pack_weight(const float* w, float* wp_fwd, float* wp_bwd, int Co, int Ci
  *   20 h3_scale     that scale (a power of two; the formats: adm_amd/csrc/split_format.h): the bits of a float in the low 32 bits
  *   21 h3_flag      int* raised to 1 when a scaled weight of columns 18, 19, 22, 23 leaves the fp16 range; 0 = none
  *   22 g6fh, 23 g6bh   two-term fp16 images of scale * (1x1 operands), as adm_split2_rows_f16
- * Columns 10-19, 22 and 23 are destinations and may be 0 (not derived); 10-15, 18 and 19 are read for 3x3 layers only, 16, 17, 22 and 23
- * for 1x1 layers only. */
+ * Columns 1, 2, 10-19, 22 and 23 are destinations and may be 0, each on its own (not derived: nothing is written for it, the
+ * others are); 10-15, 18 and 19 are read for 3x3 layers only, 16, 17, 22 and 23 for 1x1 layers only.  The 16-bit images (14-19, 22,
+ * 23) are written with 8-byte stores and must be 8-byte aligned. */
 int adm_pack_weight_table(const long* table, int n_entries, long total_tiles, hipStream_t stream);
 /* inverse of the fwd packing for gradients: dw OIHW = (accumulate ? dw : 0) + dwp */
 int adm_unpack_wgrad(const float* dwp, float* dw, int Co, int Ci, int ks, int Co_pad, int Ci_pad, int qkv,
