@@ -532,6 +532,27 @@ int adm_sr_batch(const uint8_t* pool, long pool_bytes, const int64_t* img_off, c
                  const int* vbounds, const int* vcoef, int kv, float* image, float* cond, uint8_t* cond_u8, int B, int H, int W,
                  int h, int w, hipStream_t stream);
 
+/* ---------------- saliency pairs (ddm/data.py:996-1026, DUTSDataset.__getitem__) ----------------
+ * One launch makes a batch from TWO uint8 pools in device memory (adm_sr_batch's layout each: packed, 4-byte aligned, a multiple of
+ * 4 bytes): sample b is image n = idx[b] (clamped to [0, n_images)): `rgb` [B][3][H][W] = (u8 / 255) * 2 - 1 of the rgb_hw[2n] x
+ * rgb_hw[2n+1] HWC photo at byte rgb_off[n] resized to H x W, `gray` [B][1][H][W] the same of the gray_hw[2n] x gray_hw[2n+1]
+ * one-byte-per-pixel map at byte gray_off[n] (the two sizes need not agree), both with PIL's 8-bit two-pass arithmetic as in
+ * adm_sr_batch; `rgb_u8` [B][H][W][3] / `gray_u8` [B][H][W] (each may be NULL) = the resized bytes.  flip[b] != 0 mirrors the
+ * columns of every output, after the resize.
+ *   tab: the int32 table pool of tab_ints ints; table t starts at tab[tab_dir[2t]] as bounds [out][2] = {window start, window
+ *   length} followed by coefficients [out][k], k = tab_dir[2t+1] (22 fractional bits; adm_amd/ddm/sr_data.py resample_table);
+ *   img_tab [n_images][4] = table of the photo's width -> W, of its height -> H, of the map's width -> W, of its height -> H.
+ *   max_h / max_w: the largest source height / width of either pool, kh / kv: the longest horizontal / vertical table; they size
+ *   the LDS rectangle of an ADM_SR_TILE_H x ADM_SR_TILE_W tile.  adm_pair_resize_lds = the LDS bytes that takes; above 64 KiB
+ *   (a source more than about 7 times the target) adm_pair_resize_batch returns ADM_EINVAL without launching.
+ * A table or an image that lies about its size gives wrong pixels, never an access outside the pools. */
+long adm_pair_resize_lds(int H, int W, int max_h, int max_w, int kh, int kv);
+int adm_pair_resize_batch(const uint8_t* rgb_pool, long rgb_bytes, const int64_t* rgb_off, const int* rgb_hw,
+                          const uint8_t* gray_pool, long gray_bytes, const int64_t* gray_off, const int* gray_hw, int n_images,
+                          const int* tab, long tab_ints, const int* tab_dir, int n_tables, const int* img_tab, int max_h,
+                          int max_w, int kh, int kv, const int* idx, const int* flip, float* rgb, float* gray, uint8_t* rgb_u8,
+                          uint8_t* gray_u8, int B, int H, int W, hipStream_t stream);
+
 /* ---------------- in-painting batches (ddm/data.py:384-476, InpaintDataset.__getitem__ / random_mask / RandomBrush) ----------------
  * A mask is hole = 0 / keep = 1 on integer pixel coordinates of an S x S image, defined in integers: a pixel is a
  * hole when a clipped rectangle, a stroke segment (butt-ended band: 0 <= dot <= L2 and 4 cross^2 <= w^2 L2, int64) or a stroke

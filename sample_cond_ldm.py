@@ -23,6 +23,11 @@ With ``data.class_name: ddm.data.InpaintDataset`` (in-painting, configs/inpainti
 window: each image gets a mask drawn on the device (adm_amd.ddm.inpaint_data), the model is sampled once on the masked image with
 ``mask=`` / ``cond_image=``, and the composite -- kept pixels from the image, holes from the sample -- is written under the image's
 name; ``sampler.save_masks: True`` also writes ``masks/<name>``.  PSNR is printed as the reference's sampler prints it (:195, 217).
+
+With ``data.class_name: ddm.data.DUTSDataset`` and ``split: test`` (saliency, configs/saliency/duts_cond_ddm_const_ldm_sample.yaml) the
+condition is the photo resized to the model's resolution and the windows run at the output's own scale (the reference's
+``slide_sample``, :220-283: ``slide_sample_sr`` with ``scale=1``); ``sampler.out_channels`` defaults to 1, ``crop_size`` / ``stride`` to
+``image_size``; each one-channel prediction is written as a mode-L png under the photo's name, and the PSNR is against the resized map.
 """
 import argparse
 import importlib
@@ -201,6 +206,30 @@ class InpaintCondStream:
             yield batch
 
 
+DUTS_CLASSES = ("ddm.data.DUTSDataset", "DUTSDataset")
+
+
+class DUTSCondStream:
+    """``data.class_name: ddm.data.DUTSDataset`` with ``split: test`` (``DUTS-TE`` below ``data_root``): pair i in sorted order, photo and
+    map resized to the model's resolution by the kernel that makes the training batches (adm_amd.ddm.pair_data), no flip (ddm/data.py:
+    987-991).  'cond' is the photo, 'image' the map; 'ori_size' is the photo's own size, as the reference records it (:1026)."""
+
+    def __init__(self, data_cfg, n, image_size, device, seed):
+        from adm_amd.ddm.pair_data import DUTSBatchStream
+        if (data_cfg.get("split") or "train") != "test":
+            raise ValueError("sampling ddm.data.DUTSDataset needs data.split: test (DUTS-TE, in order, unflipped)")
+        self.n = n
+        self.stream = DUTSBatchStream(data_cfg, 1, image_size, device, seed)
+
+    def __iter__(self):
+        s = self.stream
+        for i in range(self.n):
+            batch = s.next_batch(idx=[i % s.pool.n], flip=[0])
+            batch["ori_size"] = batch["ori_size"][0]
+            batch["img_name"] = batch["img_name"][0][:-4] + ".png"          # reference :215-216: the photo's name, as png
+            yield batch
+
+
 def main():
     ap = argparse.ArgumentParser(description="sliding-window conditional latent sampler (MI355X hot path)")
     ap.add_argument("--cfg", required=True)
@@ -244,6 +273,7 @@ def main():
     n_total = int(s.sample_num) if args.max_images is None else min(int(s.sample_num), args.max_images)
     per_rank = n_total // world
     inpaint = cfg.data.get("class_name") in INPAINT_CLASSES
+    duts = cfg.data.get("class_name") in DUTS_CLASSES
     if inpaint:
         size = tuple(cfg.data.get("image_size") or mc.image_size)
         stream = InpaintCondStream(cfg.data, per_rank, size, device, seed=2000 + rank)
@@ -253,6 +283,12 @@ def main():
             raise NotImplementedError(f"in-painting samples the whole image in one window: sampler.crop_size {crop} must equal image_size {size}")
         if bool(s.get("save_masks", False)):
             os.makedirs(os.path.join(out_dir, "masks"), exist_ok=True)
+    elif duts:
+        size = tuple(cfg.data.get("image_size") or mc.image_size)
+        stream = DUTSCondStream(cfg.data, per_rank, size, device, seed=2000 + rank)
+        # The reference's saliency sample YAML has neither key, and its own driver would fail on them (cfg.sampler.crop_size, :190):
+        # they default to one window, the image at model resolution.
+        crop, stride = tuple(s.get("crop_size") or size), tuple(s.get("stride") or size)
     else:
         stream = CondStream(cfg.data, per_rank, device, seed=2000 + rank)
         crop, stride = tuple(s.crop_size), tuple(s.stride)
@@ -269,6 +305,16 @@ def main():
             Image.fromarray(arr).save(os.path.join(out_dir, name))
             if bool(s.get("save_masks", False)):
                 Image.fromarray((mask[0, 0] * 255).to(torch.uint8).cpu().numpy()).save(os.path.join(out_dir, "masks", name))
+            done += 1
+            continue
+        if duts:          # the reference's slide_sample (:220-283): windows over the condition at the output's own resolution
+            fn = lambda c: ldm.sample(cond=list(ldm.model.init_conv_mask(c)), latent_hw=(c.shape[2] // down, c.shape[3] // down))
+            pred = slide_sample_sr(fn, cond, tuple(cond.shape[-2:]), crop, stride, out_channels=int(s.get("out_channels", 1)), scale=1,
+                                   window_batch=int(s.get("window_batch", 0)), flip_test=bool(s.get("flip_test", False)))
+            psnr += float(-10.0 * torch.log10(torch.mean((pred - image) ** 2)))          # against the resized map (:195)
+            arr = (pred[0].clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0).cpu().numpy()
+            name = batch["img_name"] if world == 1 else f"{rank * per_rank + done: 010d}.png"
+            Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr).save(os.path.join(out_dir, name))
             done += 1
             continue
         # the encoder runs ONCE per window batch (the reference re-runs it inside every denoising step, cond_unet_sd.py:821)

@@ -135,6 +135,9 @@ def save_grid(img, path, nrow):
     for i in range(B):
         r, c = divmod(i, nrow)
         canvas[:, r * H:(r + 1) * H, c * W:(c + 1) * W] = img[i]
+    if C == 1:          # a one-channel sample (saliency maps): mode L; Image.fromarray refuses an [H, W, 1] array
+        Image.fromarray(canvas[0].numpy()).save(path)
+        return
     Image.fromarray(canvas.permute(1, 2, 0).numpy()).save(path)
 
 
