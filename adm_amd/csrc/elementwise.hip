@@ -329,13 +329,13 @@ __global__ void q_sample_kernel(const float* __restrict__ x0, const float* __res
 
 __global__ __launch_bounds__(256) void ddm_loss_kernel(const float* __restrict__ cp, const float* __restrict__ np_,
                                                        const float* __restrict__ x0, const float* __restrict__ noise,
-                                                       const float* __restrict__ w, float* __restrict__ per_sample,
+                                                       const float* __restrict__ w, double* __restrict__ per_sample,
                                                        float* __restrict__ dc, float* __restrict__ dn, float gscale,
                                                        long n) {
-  __shared__ float red[4];
+  __shared__ double red[4];
   const int b = blockIdx.x;
   const float w1 = w[2 * b], w2 = w[2 * b + 1];
-  float acc = 0.f;
+  double acc = 0.0;                    // f32 terms summed in f64: the sum's error is its terms' roundings, whatever n and the chunking
   for (long i = blockIdx.y * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.y * blockDim.x) {
     long k = (long)b * n + i;
     float e1 = cp[k] + x0[k];          // C_pred - C, C = -x0
@@ -343,7 +343,7 @@ __global__ __launch_bounds__(256) void ddm_loss_kernel(const float* __restrict__
     acc += w1 * e1 * e1 + w2 * e2 * e2;
     if (dc) { dc[k] = gscale * 2.f * w1 * e1; dn[k] = gscale * 2.f * w2 * e2; }
   }
-  acc = wave_sum(acc);
+  acc = wave_sum_d(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(&per_sample[b], red[0] + red[1] + red[2] + red[3]);
@@ -351,19 +351,19 @@ __global__ __launch_bounds__(256) void ddm_loss_kernel(const float* __restrict__
 
 // Latent variant (ddm_const_2.py:527-596): the weighted SSE above plus  w3 * sum |x_rec - x0|,
 // x_rec = x_t - C_pred t - t noise_pred  (const_2: g(t) = t), evaluated in the reference's operation order.
-// w = [B][3] = (w1, w2, w3);  per_sample[b] gets the SSE part, per_l1[b] the UN-weighted L1 sum.
+// w = [B][3] = (w1, w2, w3);  per_sample[b] gets the SSE part, per_l1[b] the UN-weighted L1 sum (both f64, as in ddm_loss_kernel).
 __global__ __launch_bounds__(256) void ddm_loss_latent_kernel(const float* __restrict__ cp, const float* __restrict__ np_,
                                                               const float* __restrict__ x0, const float* __restrict__ noise,
                                                               const float* __restrict__ xt, const float* __restrict__ t,
-                                                              const float* __restrict__ w, float* __restrict__ per_sample,
-                                                              float* __restrict__ per_l1, float* __restrict__ dc,
+                                                              const float* __restrict__ w, double* __restrict__ per_sample,
+                                                              double* __restrict__ per_l1, float* __restrict__ dc,
                                                               float* __restrict__ dn, float gscale, long n, int schedule,
                                                               int use_l1) {
-  __shared__ float red[8];
+  __shared__ double red[8];
   const int b = blockIdx.x;
   const float w1 = w[3 * b], w2 = w[3 * b + 1], w3 = w[3 * b + 2], tb = t[b];
   const float gt = schedule == 0 ? sqrtf(tb) : tb;       // 'const': sqrt(t) (ddm_const.py:290-293); 'const_2': t
-  float acc = 0.f, l1 = 0.f;
+  double acc = 0.0, l1 = 0.0;
   for (long i = blockIdx.y * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.y * blockDim.x) {
     long k = (long)b * n + i;
     float c = cp[k], e = np_[k];
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(256) void ddm_loss_latent_kernel(const float* __res
       dn[k] = gscale * (g2 - w3 * gt * sg);
     }
   }
-  acc = wave_sum(acc); l1 = wave_sum(l1);
+  acc = wave_sum_d(acc); l1 = wave_sum_d(l1);
   if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = acc; red[4 + (threadIdx.x >> 6)] = l1; }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -483,8 +483,8 @@ __global__ __launch_bounds__(256) void sumsq_final_kernel(const double* __restri
 
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, float* __restrict__ ema, const double* __restrict__ sumsq, long n,
-                             float lr, float b1, float b2, float eps, float wd, float max_norm, float bc1, float bc2s,
-                             float ema_w, float grad_scale) {
+                             float lr, float b1, float b2, float omb1, float omb2, float eps, float wd, float max_norm, float bc1,
+                             float bc2s, float ema_w, float grad_scale) {
   float clip = 1.f;
   if (sumsq && max_norm > 0.f) {
     float nrm = (float)sqrt(*sumsq) * grad_scale;
@@ -494,13 +494,16 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     float gv = g[i] * gs;
     float pv = p[i] * (1.f - lr * wd);
-    float mv = b1 * m[i] + (1.f - b1) * gv;
-    float vv = b2 * v[i] + (1.f - b2) * gv * gv;
+    float mv = b1 * m[i] + omb1 * gv;
+    float vv = b2 * v[i] + omb2 * gv * gv;
     m[i] = mv; v[i] = vv;
     float denom = sqrtf(vv) / bc2s + eps;
     pv -= (lr / bc1) * (mv / denom);
     p[i] = pv;
-    if (ema) ema[i] += ema_w * (pv - ema[i]);
+    if (ema) {      // torch's lerp: from the nearer end, so a weight of 1 (ema_decay 0: the warm-up's plain copy) gives p bit for bit
+      const float ev = ema[i];
+      ema[i] = ema_w < 0.5f ? ev + ema_w * (pv - ev) : pv - (pv - ev) * (1.f - ema_w);
+    }
   }
 }
 
@@ -790,11 +793,11 @@ extern "C" int adm_q_sample(const float* x0, const float* noise, const float* t,
 }
 
 extern "C" int adm_ddm_loss(const float* c_pred, const float* n_pred, const float* x0, const float* noise,
-                            const float* w, float* per_sample, float* d_c, float* d_n, float gscale, int B, long n,
+                            const float* w, double* per_sample, float* d_c, float* d_n, float gscale, int B, long n,
                             hipStream_t stream) {
   if (!c_pred || !n_pred || !x0 || !noise || !w || !per_sample || B <= 0 || n <= 0) return ADM_EINVAL;
   if ((d_c == nullptr) != (d_n == nullptr)) return ADM_EINVAL;
-  if (hipMemsetAsync(per_sample, 0, sizeof(float) * B, stream) != hipSuccess) return ADM_ELAUNCH;
+  if (hipMemsetAsync(per_sample, 0, sizeof(double) * B, stream) != hipSuccess) return ADM_ELAUNCH;
   int chunks = (int)((n + 1023) / 1024);
   if (chunks > 64) chunks = 64;
   if (n <= 65536) chunks = 1;          // one workgroup per sample: the reported per-sample sums are bitwise reproducible
@@ -805,14 +808,14 @@ extern "C" int adm_ddm_loss(const float* c_pred, const float* n_pred, const floa
 }
 
 extern "C" int adm_ddm_loss_latent(const float* c_pred, const float* n_pred, const float* x0, const float* noise,
-                                   const float* xt, const float* t, const float* w, float* per_sample, float* per_l1,
+                                   const float* xt, const float* t, const float* w, double* per_sample, double* per_l1,
                                    float* d_c, float* d_n, float gscale, int B, long n, int schedule, int use_l1,
                                    hipStream_t stream) {
   if (!c_pred || !n_pred || !x0 || !noise || !xt || !t || !w || !per_sample || !per_l1 || B <= 0 || n <= 0) return ADM_EINVAL;
   if (schedule != 0 && schedule != 1) return ADM_EINVAL;
   if ((d_c == nullptr) != (d_n == nullptr)) return ADM_EINVAL;
-  if (hipMemsetAsync(per_sample, 0, sizeof(float) * B, stream) != hipSuccess) return ADM_ELAUNCH;
-  if (hipMemsetAsync(per_l1, 0, sizeof(float) * B, stream) != hipSuccess) return ADM_ELAUNCH;
+  if (hipMemsetAsync(per_sample, 0, sizeof(double) * B, stream) != hipSuccess) return ADM_ELAUNCH;
+  if (hipMemsetAsync(per_l1, 0, sizeof(double) * B, stream) != hipSuccess) return ADM_ELAUNCH;
   int chunks = (int)((n + 1023) / 1024);
   if (chunks > 64) chunks = 64;
   if (n <= 65536) chunks = 1;
@@ -854,13 +857,17 @@ extern "C" int adm_sumsq(const float* g, double* sumsq, double* partials, long n
 }
 
 extern "C" int adm_adamw_step(float* p, const float* g, float* m, float* v, float* ema, const double* sumsq, long n,
-                              float lr, float beta1, float beta2, float eps, float wd, float max_norm, int step,
-                              float ema_decay, float grad_scale, hipStream_t stream) {
+                              float lr, double beta1, double beta2, float eps, float wd, float max_norm, int step,
+                              double ema_decay, float grad_scale, hipStream_t stream) {
   if (!p || !g || !m || !v || n <= 0 || step < 1) return ADM_EINVAL;
-  float bc1 = 1.f - powf(beta1, (float)step);
-  float bc2s = sqrtf(1.f - powf(beta2, (float)step));
-  hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid(n, 4)), dim3(256), 0, stream, p, g, m, v, ema, sumsq, n, lr, beta1,
-                     beta2, eps, wd, max_norm, bc1, bc2s, 1.f - ema_decay, grad_scale);
+  // The betas and the EMA decay arrive in double, and everything derived from them -- 1 - beta, the bias corrections, the EMA weight
+  // -- is formed in double and rounded once, as torch.optim.AdamW forms them from Python floats.  From a float beta2 = 0.999f,
+  // 1 - beta2 is 1.0000467e-3, and 1 - beta2^step in float is off by up to 1e-5: both move the update by 1e-5 of itself.
+  const float bc1 = (float)(1.0 - pow(beta1, (double)step));
+  const float bc2s = (float)sqrt(1.0 - pow(beta2, (double)step));
+  hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid(n, 4)), dim3(256), 0, stream, p, g, m, v, ema, sumsq, n, lr, (float)beta1,
+                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, wd, max_norm, bc1, bc2s, (float)(1.0 - ema_decay),
+                     grad_scale);
   ADM_CHECK_LAUNCH();
   return ADM_OK;
 }

@@ -150,7 +150,7 @@ _SIGS = {
     "adm_linattn_bwd": [P, P, P, P, P, P, P, P, I, I, P],
     "adm_sumsq_blocks": [L],
     "adm_sumsq": [P, P, P, L, P],
-    "adm_adamw_step": [P, P, P, P, P, P, L, F, F, F, F, F, F, I, F, F, P],
+    "adm_adamw_step": [P, P, P, P, P, P, L, F, D, D, F, F, F, I, D, F, P],
     "adm_lpips_input": [P, P, P, P, P, P, P, I, I, I, P],
     "adm_lpips_input_bwd": [P, P, P, P, P, I, I, I, P],
     "adm_maxpool2x2_fwd": [P, P, I, I, I, I, P],

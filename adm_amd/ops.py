@@ -2249,10 +2249,11 @@ class _DdmLoss(torch.autograd.Function):
         c_pred, n_pred = _chk(c_pred, "C_pred"), _chk(n_pred, "noise_pred")
         B = c_pred.shape[0]
         n = c_pred.numel() // B
-        per = _new((B,), c_pred)
+        per = _new((B,), c_pred, torch.float64)          # the sums leave the kernel in fp64 and are rounded to f32 once
         dc, dn = _like(c_pred), _like(n_pred)
         call("adm_ddm_loss", ptr(c_pred), ptr(n_pred), ptr(x0), ptr(noise), ptr(w), ptr(per), ptr(dc), ptr(dn), 1.0 / B,
              B, n)
+        per = per.to(_f32)
         ctx.save_for_backward(dc, dn)
         ctx.mark_non_differentiable(per)
         return per.sum() / B, per
@@ -2276,10 +2277,11 @@ class _DdmLossLatent(torch.autograd.Function):
         c_pred, n_pred = _chk(c_pred, "C_pred"), _chk(n_pred, "noise_pred")
         B = c_pred.shape[0]
         n = c_pred.numel() // B
-        per, l1 = _new((B,), c_pred), _new((B,), c_pred)
+        per, l1 = _new((B,), c_pred, torch.float64), _new((B,), c_pred, torch.float64)      # (fp64 sums, rounded to f32 once)
         dc, dn = _like(c_pred), _like(n_pred)
         call("adm_ddm_loss_latent", ptr(c_pred), ptr(n_pred), ptr(x0), ptr(noise), ptr(xt), ptr(t), ptr(w), ptr(per),
              ptr(l1), ptr(dc), ptr(dn), 1.0 / B, B, n, int(schedule), int(use_l1))
+        per, l1 = per.to(_f32), l1.to(_f32)
         ctx.save_for_backward(dc, dn)
         ctx.mark_non_differentiable(per, l1)
         return (per.sum() + (l1 * w[:, 2]).sum()) / B, per, l1

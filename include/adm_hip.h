@@ -453,15 +453,16 @@ int adm_q_sample(const float* x0, const float* noise, const float* t, float* xt,
                  hipStream_t stream);
 /* Weighted SSE loss and its gradients (ddm_const.py:335-358 with ddm/loss.py MSE_Loss 'sum'):
  * per_sample[b] = w1[b] sum (Cp+x0)^2 + w2[b] sum (Np-noise)^2 ; dCp = gscale*2 w1 (Cp + x0) ; dNp likewise.
- * w = [B][2] weights precomputed on device. */
+ * w = [B][2] weights precomputed on device.  per_sample is fp64 [B], zero-filled by the call: the f32 terms are summed in fp64 (one
+ * workgroup per sample up to n = 65536: bitwise reproducible; above, up to 64 chunks per sample meet in fp64 atomics). */
 int adm_ddm_loss(const float* c_pred, const float* n_pred, const float* x0, const float* noise, const float* w,
-                 float* per_sample, float* d_c, float* d_n, float gscale, int B, long n, hipStream_t stream);
+                 double* per_sample, float* d_c, float* d_n, float gscale, int B, long n, hipStream_t stream);
 /* Latent-space loss (LatentDiffusion.p_losses, ddm_const_2.py:527-596, schedule const_2): the two weighted SSE terms
  * of adm_ddm_loss plus w3[b] * sum |x_rec - x0| with x_rec = xt - Cp t - t Np.  w = [B][3] = (w1, w2, w3).
  * per_sample[b] = SSE part, per_l1[b] = un-weighted L1 sum; dCp = gscale (2 w1 (Cp + x0) - w3 t sign(x_rec - x0)),
- * dNp = gscale (2 w2 (Np - noise) - w3 t sign(x_rec - x0)).  Both outputs are zero-filled by the call. */
+ * dNp = gscale (2 w2 (Np - noise) - w3 t sign(x_rec - x0)).  Both sums are fp64 [B], zero-filled by the call. */
 int adm_ddm_loss_latent(const float* c_pred, const float* n_pred, const float* x0, const float* noise, const float* xt,
-                        const float* t, const float* w, float* per_sample, float* per_l1, float* d_c, float* d_n,
+                        const float* t, const float* w, double* per_sample, double* per_l1, float* d_c, float* d_n,
                         float gscale, int B, long n, int schedule, int use_l1,
                         hipStream_t stream);
 /* One deterministic sampler update in fp64 (ddm_const.py:450-455 / ddm_const_2.py:363-368):
@@ -614,9 +615,10 @@ int adm_sumsq_blocks(long n);
 int adm_sumsq(const float* g, double* sumsq, double* partials, long n, hipStream_t stream);
 /* AdamW step on flat buffers with the clip factor computed on device from sumsq[0]:
  * g *= min(1, max_norm/(sqrt(sumsq)+1e-6)); decoupled weight decay; optional EMA lerp
- * (ema += (1-decay)(p-ema)) fused into the same pass when ema != NULL. */
+ * (ema += (1-decay)(p-ema)) fused into the same pass when ema != NULL.  beta1, beta2 and ema_decay are doubles: 1 - beta, the bias
+ * corrections 1 - beta^step and the EMA weight are formed from them in double on the host and rounded to float once. */
 int adm_adamw_step(float* p, const float* g, float* m, float* v, float* ema, const double* sumsq, long n, float lr,
-                   float beta1, float beta2, float eps, float wd, float max_norm, int step, float ema_decay,
+                   double beta1, double beta2, float eps, float wd, float max_norm, int step, double ema_decay,
                    float grad_scale, hipStream_t stream);
 
 
