@@ -393,6 +393,43 @@ __global__ __launch_bounds__(256) void ddm_loss_latent_kernel(const float* __res
   }
 }
 
+// Pixel-space variant with the L1 twins (ddm_const.py:343-348 / ddm_const_2.py:235-240): the twins are per-sample MEANS where the
+// latent ones are sums, so loss_simple_b = [w1 (SSE_C + L1_C / n) + w2 (SSE_eps + L1_eps / n)] / 2.  The four un-weighted sums leave
+// the kernel separately in fp64 (sums[b] = SSE_C, SSE_eps, L1_C, L1_eps) and the host combines them, so the logged values need no
+// second pass; dCp = gscale * 0.5 * w1 * (2 e1 + sign(e1) / n) with sign(0) = 0, dNp likewise.
+__global__ __launch_bounds__(256) void ddm_loss_l1_kernel(const float* __restrict__ cp, const float* __restrict__ np_,
+                                                          const float* __restrict__ x0, const float* __restrict__ noise,
+                                                          const float* __restrict__ w, double* __restrict__ sums,
+                                                          float* __restrict__ dc, float* __restrict__ dn, float gscale, long n) {
+  __shared__ double red[16];
+  const int b = blockIdx.x;
+  const float inv_n = 1.f / (float)n;
+  const float k1 = gscale * 0.5f * w[2 * b], k2 = gscale * 0.5f * w[2 * b + 1];
+  double s1 = 0.0, s2 = 0.0, a1 = 0.0, a2 = 0.0;
+  for (long i = blockIdx.y * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.y * blockDim.x) {
+    const long k = (long)b * n + i;
+    const float e1 = cp[k] + x0[k];          // C_pred - C, C = -x0
+    const float e2 = np_[k] - noise[k];
+    s1 += e1 * e1; s2 += e2 * e2;
+    a1 += fabsf(e1); a2 += fabsf(e2);
+    if (dc) {
+      const float g1 = e1 > 0.f ? inv_n : (e1 < 0.f ? -inv_n : 0.f), g2 = e2 > 0.f ? inv_n : (e2 < 0.f ? -inv_n : 0.f);
+      dc[k] = k1 * (2.f * e1 + g1);
+      dn[k] = k2 * (2.f * e2 + g2);
+    }
+  }
+  s1 = wave_sum_d(s1); s2 = wave_sum_d(s2); a1 = wave_sum_d(a1); a2 = wave_sum_d(a2);
+  if ((threadIdx.x & 63) == 0) {
+    const int wv = threadIdx.x >> 6;
+    red[wv] = s1; red[4 + wv] = s2; red[8 + wv] = a1; red[12 + wv] = a2;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int q = 4 * threadIdx.x;
+    atomicAdd(&sums[4 * (long)b + threadIdx.x], red[q] + red[q + 1] + red[q + 2] + red[q + 3]);
+  }
+}
+
 __global__ void sampler_step_kernel(double* __restrict__ x, const float* __restrict__ cp, const float* __restrict__ np_,
                                     double t_cur, double t_next, double g_cur, double g_next, int clip_x0,
                                     double scale_input, int last, long n) {
@@ -821,6 +858,20 @@ extern "C" int adm_ddm_loss_latent(const float* c_pred, const float* n_pred, con
   if (n <= 65536) chunks = 1;
   hipLaunchKernelGGL(ddm_loss_latent_kernel, dim3(B, chunks), dim3(256), 0, stream, c_pred, n_pred, x0, noise, xt, t, w,
                      per_sample, per_l1, d_c, d_n, gscale, n, schedule, use_l1);
+  ADM_CHECK_LAUNCH();
+  return ADM_OK;
+}
+
+extern "C" int adm_ddm_loss_l1(const float* c_pred, const float* n_pred, const float* x0, const float* noise, const float* w,
+                               double* sums, float* d_c, float* d_n, float gscale, int B, long n, hipStream_t stream) {
+  if (!c_pred || !n_pred || !x0 || !noise || !w || !sums || B <= 0 || n <= 0) return ADM_EINVAL;
+  if ((d_c == nullptr) != (d_n == nullptr)) return ADM_EINVAL;
+  if (hipMemsetAsync(sums, 0, sizeof(double) * 4 * B, stream) != hipSuccess) return ADM_ELAUNCH;
+  int chunks = (int)((n + 1023) / 1024);
+  if (chunks > 64) chunks = 64;
+  if (n <= 65536) chunks = 1;          // one workgroup per sample: the four sums are bitwise reproducible
+  hipLaunchKernelGGL(ddm_loss_l1_kernel, dim3(B, chunks), dim3(256), 0, stream, c_pred, n_pred, x0, noise, w, sums, d_c, d_n,
+                     gscale, n);
   ADM_CHECK_LAUNCH();
   return ADM_OK;
 }

@@ -70,6 +70,45 @@ __global__ __launch_bounds__(256) void lpips_input_bwd_kernel(const f32x4* __res
   }
 }
 
+// One-channel image (the saliency map of the pixel-space recipe): ScalingLayer broadcasts it, (inp - shift) / scale with inp [B,1,H,W] and
+// shift [1,3,1,1] gives three channels from the same x_rec (lpips.py:56-63).  a, n_pred, x_noisy are [B][1][HW]; schedules -1, 0, 1 as
+// above (the linear schedule is not built for one channel).  Same store pattern: eight threads per pixel, one 16-byte store each.
+__global__ __launch_bounds__(256) void lpips_input_c1_kernel(const float* __restrict__ a, const float* __restrict__ n_pred,
+                                                             const float* __restrict__ x_noisy, const float* __restrict__ t,
+                                                             const float* __restrict__ shift, const float* __restrict__ scale,
+                                                             f32x4* __restrict__ y, long pixels, int HW, int schedule) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  const long p = idx >> 3;
+  if (p >= pixels) return;
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if ((idx & 7) == 0) {
+    float xr;
+    if (schedule < 0) xr = a[p];
+    else if (schedule == 0) xr = -a[p];
+    else {
+      const float tb = t[p / HW];
+      xr = x_noisy[p] - a[p] * tb - tb * n_pred[p];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = (xr - shift[c]) / scale[c];
+  }
+  y[idx] = v;
+}
+
+// d x_rec = dy[.., 0] / scale[0] + dy[.., 1] / scale[1] + dy[.., 2] / scale[2], summed in that order (no atomics: one thread owns the
+// pixel), then the schedule's factor as in lpips_input_bwd_kernel.  One 16-byte load, one (schedule 1: two) contiguous 4-byte stores.
+__global__ __launch_bounds__(256) void lpips_input_c1_bwd_kernel(const f32x4* __restrict__ dy, const float* __restrict__ t,
+                                                                 const float* __restrict__ scale, float* __restrict__ d_a,
+                                                                 float* __restrict__ d_n, long pixels, int HW, int schedule) {
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= pixels) return;
+  const f32x4 g = dy[p * 8];
+  const float m = schedule < 0 ? 1.f : schedule == 0 ? -1.f : -t[p / HW];
+  const float d = m * ((g[0] / scale[0] + g[1] / scale[1]) + g[2] / scale[2]);
+  d_a[p] = d;
+  if (schedule == 1) d_n[p] = d;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // 2x2 max-pool, stride 2, NHWC
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -269,6 +308,28 @@ extern "C" int adm_lpips_input_bwd(const float* dy, const float* t, const float*
   const long pixels = (long)B * HW;
   hipLaunchKernelGGL(lpips_input_bwd_kernel, dim3(adm_cdiv(pixels, 256)), dim3(256), 0, stream, reinterpret_cast<const f32x4*>(dy),
                      t, scale, d_a, d_n, pixels, HW, schedule);
+  ADM_CHECK_LAUNCH();
+  return ADM_OK;
+}
+
+extern "C" int adm_lpips_input_c1(const float* a, const float* n_pred, const float* x_noisy, const float* t, const float* shift,
+                                  const float* scale, float* y, int B, int HW, int schedule, hipStream_t stream) {
+  if (!a || !shift || !scale || !y || B <= 0 || HW <= 0 || schedule < -1 || schedule > 1 || !al16(y)) return ADM_EINVAL;
+  if (schedule == 1 && (!n_pred || !x_noisy || !t)) return ADM_EINVAL;
+  const long pixels = (long)B * HW;
+  hipLaunchKernelGGL(lpips_input_c1_kernel, dim3(adm_cdiv(pixels * 8, 256)), dim3(256), 0, stream, a, n_pred, x_noisy, t, shift,
+                     scale, reinterpret_cast<f32x4*>(y), pixels, HW, schedule);
+  ADM_CHECK_LAUNCH();
+  return ADM_OK;
+}
+
+extern "C" int adm_lpips_input_c1_bwd(const float* dy, const float* t, const float* scale, float* d_a, float* d_n, int B, int HW,
+                                      int schedule, hipStream_t stream) {
+  if (!dy || !scale || !d_a || B <= 0 || HW <= 0 || schedule < -1 || schedule > 1 || !al16(dy)) return ADM_EINVAL;
+  if (schedule == 1 && (!t || !d_n)) return ADM_EINVAL;
+  const long pixels = (long)B * HW;
+  hipLaunchKernelGGL(lpips_input_c1_bwd_kernel, dim3(adm_cdiv(pixels, 256)), dim3(256), 0, stream,
+                     reinterpret_cast<const f32x4*>(dy), t, scale, d_a, d_n, pixels, HW, schedule);
   ADM_CHECK_LAUNCH();
   return ADM_OK;
 }

@@ -24,7 +24,6 @@ class DDPM(DDPMBase):
 
 class LatentDiffusion(DDPM):
     USES_LPIPS = False
-    SUPPORTS_L1 = True
     CLIP_IN_SAMPLER = False
 
     def __init__(self, auto_encoder, scale_factor=1.0, scale_by_std=True, scale_by_softsign=False, input_keys=("image",),

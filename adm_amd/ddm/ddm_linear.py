@@ -34,7 +34,6 @@ class DDPM(DDPMBase):
     SCHEDULE = "linear"
     DEFAULT_EPS = 1e-4
     AUGMENT_P = 0.12           # ddm_linear.py:110
-    SUPPORTS_L1 = True
     NO_LPIPS_WARNING = ("adm_amd: the LPIPS term (perceptual_weight > 0) needs VGG16 weights that cannot be fetched offline; "
                         "loss_vlb is its MAE part alone (see DESIGN.md)")
 

@@ -13,6 +13,9 @@ Differences, all documented in DESIGN.md:
     (adm_amd/ddm/lpips.py) when ``perceptual_weight > 0`` AND its weights were supplied: by the cfg key ``lpips_ckpt``, by
     ``set_perceptual_loss()``, or by a checkpoint whose state dict carries ``perceptual_loss.*``.  No weights ship and none
     are ever fetched; without them the wrapper warns and ``loss_vlb`` is 0;
+  * ``use_l1`` in pixel space (per-sample MEAN |.| twins, ddm_const.py:345-348 / ddm_const_2.py:237-240) is one launch of its own
+    (``ops.ddm_loss_l1``); a conditional denoiser gets ``batch['cond']`` (ddm_const_2.py:157-161) and ``sample(cond=...)`` runs the
+    built-in condition encoder once per call in eval mode, not once per step (same bits);
   * ``use_augment`` runs the AugmentPipe on the GPU (adm_amd/ddm/augment.py) without the reference's per-step host
     read-back of the padding margin; its draws are injectable (``augment_draws=``).
 """
@@ -40,7 +43,6 @@ class DDPMBase(nn.Module):
     DEFAULT_EPS = 1e-4
     USES_LPIPS = True           # the pixel-space p_losses has the LPIPS term; LatentDiffusion's does not
     AUGMENT_P = 0.15            # AugmentPipe probability multiplier: 0.15 in ddm_const.py:179, 0.12 in ddm_const_2.py:112
-    SUPPORTS_L1 = False         # use_l1 (L1 twins of the SSE terms) exists in the latent p_losses only (ddm_const_2.py:556-559)
     CLIP_IN_SAMPLER = True      # pixel-space 'const' sampler clamps the predicted x0 (ddm_const.py:453-454); latent ones never do
     NO_LPIPS_WARNING = ("adm_amd: the LPIPS term (perceptual_weight > 0) needs VGG16 weights that cannot be fetched "
                         "offline; loss_vlb is 0 (see DESIGN.md)")
@@ -72,9 +74,7 @@ class DDPMBase(nn.Module):
         self.start_dist = start_dist
         self.loss_type = loss_type
         self.sampling_timesteps = 10 if sampling_timesteps is None else sampling_timesteps
-        if use_l1 and not self.SUPPORTS_L1:
-            raise NotImplementedError("use_l1 is implemented for the latent wrappers only (no pixel-space DDM config sets it)")
-        self.use_l1 = use_l1
+        self.use_l1 = use_l1        # pixel space: per-sample MEAN |.| twins (ddm_const.py:345-348); latent: sums (ddm_const_2.py:556-559)
         self.perceptual_weight = perceptual_weight
         if lpips_ckpt is None:
             lpips_ckpt = _cfg_get(cfg, "lpips_ckpt", None)
@@ -174,6 +174,9 @@ class DDPMBase(nn.Module):
 
     def training_step(self, batch, *args, **kwargs):
         z = self.get_input(batch)
+        cond = batch.get("cond") if hasattr(batch, "get") else None
+        if cond is not None:          # conditional denoiser: self(z, cond) -> model(x_t, t, cond)   (ddm_const_2.py:157-161)
+            return self(z, cond, *args, **kwargs)
         return self(z, *args, **kwargs)
 
     def forward(self, x, *args, t: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, **kwargs):
@@ -195,7 +198,7 @@ class DDPMBase(nn.Module):
         x_start = x_start.to(torch.float32).contiguous()
         t = t.to(torch.float32).contiguous()
         x_noisy = self.q_sample(x_start, noise, t)
-        C_pred, noise_pred = self.model(x_noisy, t, **kwargs)
+        C_pred, noise_pred = self.model(x_noisy, t, *args, **kwargs)
         lpips = self.lpips_active
         if lpips:       # the predictions get a second consumer: the gradient sum is ops.fanout's kernel, not autograd's in-place add
             C_pred, C_lp = ops.fanout(C_pred, 2)
@@ -205,7 +208,8 @@ class DDPMBase(nn.Module):
                 noise_pred, noise_lp = ops.fanout(noise_pred, 2)
         w1, w2 = self.loss_weights(t)
         w = torch.stack([w1, w2], dim=1).contiguous()
-        loss_simple_mean, per_sample = ops.ddm_loss(C_pred, noise_pred, x_start, noise, w)
+        loss_fn = ops.ddm_loss_l1 if self.use_l1 else ops.ddm_loss
+        loss_simple_mean, per_sample = loss_fn(C_pred, noise_pred, x_start, noise, w)
         B, n = x_start.shape[0], x_start[0].numel()
         if lpips:
             # loss_vlb = LPIPS(x_rec, x_start).sum([1,2,3]) * rec_weight is [B] * [B,1] -> [B,B] in the reference, and its sum / B the
@@ -267,17 +271,27 @@ class DDPMBase(nn.Module):
         return torch.cat([ts, torch.zeros(1, dtype=torch.float64)])
 
     @torch.no_grad()
-    def sample(self, batch_size=16, up_scale=1, cond=None, denoise=True, x_T: Optional[torch.Tensor] = None):
-        if cond is not None:
-            raise NotImplementedError("conditional sampling is not on the unconditional hot path")
+    def sample(self, batch_size=16, up_scale=1, cond=None, denoise=True, x_T: Optional[torch.Tensor] = None, epsilons=None):
+        if cond is not None:       # ddm_const.py:368-378: the condition sets the batch size
+            batch_size = cond[0].shape[0] if isinstance(cond, (list, tuple)) else cond.shape[0]
+            cond = self._encode_cond_once(cond)
         h, w = self.image_size
         shape = (batch_size, self.channels, h, w)
         sample_type = _cfg_get(self.cfg, "sample_type", "deterministic")
         if sample_type == "deterministic":
-            return self.sample_fn_d(shape, x_T=x_T)
+            return self.sample_fn_d(shape, x_T=x_T, cond=cond)
         if sample_type == "stochastic":
-            return self.sample_fn_s(shape, x_T=x_T)
+            return self.sample_fn_s(shape, x_T=x_T, cond=cond, epsilons=epsilons)
         raise NotImplementedError(sample_type)
+
+    def _encode_cond_once(self, cond):
+        """The reference runs the condition encoder on the same photo at every sampler step.  In eval mode it is a pure function of
+        the photo, so its four feature maps are computed once per sample() and handed on as the list the denoiser accepts: the same
+        bits.  In train mode (stochastic depth draws per call) and without the built-in encoder the per-step call stays."""
+        enc = getattr(self.model, "init_conv_mask", None)
+        if isinstance(cond, torch.Tensor) and isinstance(enc, nn.Module) and not self.model.training:
+            return list(enc(cond))
+        return cond
 
     @torch.no_grad()
     def sample_fn_d(self, shape, up_scale=1, unnormalize=True, cond=None, denoise=False, x_T=None,
@@ -339,7 +353,7 @@ class DDPMBase(nn.Module):
             s = cur if k == n - 1 else steps[k]
             t_vec = torch.full((B,), cur, dtype=torch.float64, device=dev)
             s_vec = torch.full((B,), s, dtype=torch.float64, device=dev)
-            C, noise = self.model(img, t_vec)
+            C, noise = self.model(img, t_vec, cond) if cond is not None else self.model(img, t_vec)
             z = (epsilons[k].to(device=dev, dtype=torch.float64) if epsilons is not None
                  else torch.randn(shape, device=dev, dtype=torch.float64)).contiguous()
             ops.sampler_step_stochastic(img, C, noise, z, t_vec, s_vec, self._sched, self.clip_x_start,

@@ -115,6 +115,7 @@ _SIGS = {
     "adm_q_sample": [P, P, P, P, I, L, I, P],
     "adm_ddm_loss": [P, P, P, P, P, P, P, P, F, I, L, P],
     "adm_ddm_loss_latent": [P, P, P, P, P, P, P, P, P, P, P, F, I, L, I, I, P],
+    "adm_ddm_loss_l1": [P, P, P, P, P, P, P, P, F, I, L, P],
     "adm_sampler_step": [P, P, P, D, D, I, I, D, I, L, P],
     "adm_sampler_step_stochastic": [P, P, P, P, P, P, I, I, D, I, I, L, P],
     "adm_q_sample_linear": [P, P, P, P, P, I, L, P],
@@ -153,6 +154,8 @@ _SIGS = {
     "adm_adamw_step": [P, P, P, P, P, P, L, F, D, D, F, F, F, I, D, F, P],
     "adm_lpips_input": [P, P, P, P, P, P, P, I, I, I, P],
     "adm_lpips_input_bwd": [P, P, P, P, P, I, I, I, P],
+    "adm_lpips_input_c1": [P, P, P, P, P, P, P, I, I, I, P],
+    "adm_lpips_input_c1_bwd": [P, P, P, P, P, I, I, I, P],
     "adm_maxpool2x2_fwd": [P, P, I, I, I, I, P],
     "adm_maxpool2x2_bwd": [P, P, P, I, I, I, I, P],
     "adm_lpips_head_blocks": [I],

@@ -2268,6 +2268,38 @@ def ddm_loss(c_pred, n_pred, x0, noise, w):
     return _DdmLoss.apply(c_pred, n_pred, _chk(x0, "x0"), _chk(noise, "noise"), _chk(w, "weights"))
 
 
+class _DdmLossL1(torch.autograd.Function):
+    """Pixel-space loss with use_l1 (ddm_const.py:343-348 / ddm_const_2.py:235-240): simple_b = [w1 (SSE_C + mean|e_C|) +
+    w2 (SSE_eps + mean|e_eps|)] / 2.  Returns (sum_b simple_b / B, per-sample simple); the four fp64 sums of the kernel are
+    combined here in fp64 and rounded to f32 once."""
+
+    @staticmethod
+    def forward(ctx, c_pred, n_pred, x0, noise, w):
+        c_pred, n_pred = _chk(c_pred, "C_pred"), _chk(n_pred, "noise_pred")
+        B = c_pred.shape[0]
+        n = c_pred.numel() // B
+        sums = _new((B, 4), c_pred, torch.float64)
+        dc, dn = _like(c_pred), _like(n_pred)
+        call("adm_ddm_loss_l1", ptr(c_pred), ptr(n_pred), ptr(x0), ptr(noise), ptr(w), ptr(sums), ptr(dc), ptr(dn), 1.0 / B,
+             B, n)
+        w64 = w.to(torch.float64)
+        per = (0.5 * (w64[:, 0] * (sums[:, 0] + sums[:, 2] / n) + w64[:, 1] * (sums[:, 1] + sums[:, 3] / n))).to(_f32)
+        ctx.save_for_backward(dc, dn)
+        ctx.mark_non_differentiable(per)
+        return per.sum() / B, per
+
+    @staticmethod
+    def backward(ctx, gloss, _gper):
+        dc, dn = ctx.saved_tensors
+        return dc * gloss, dn * gloss, None, None, None
+
+
+def ddm_loss_l1(c_pred, n_pred, x0, noise, w):
+    """The pixel-space p_losses with use_l1: like ddm_loss, with the per-sample MEAN absolute errors added and the sum halved.
+    w = [B][2] as DDPMBase.loss_weights makes it ('const' and 'const_2' alike)."""
+    return _DdmLossL1.apply(c_pred, n_pred, _chk(x0, "x0"), _chk(noise, "noise"), _chk(w, "weights"))
+
+
 class _DdmLossLatent(torch.autograd.Function):
     """LatentDiffusion.p_losses (ddm_const_2.py:527-596): weighted SSE + w3 * sum|x_rec - x0|.  Returns
     (sum_b simple_b / B, per-sample simple, per-sample un-weighted L1)."""
@@ -2400,15 +2432,50 @@ class _LpipsInput(torch.autograd.Function):
         return da, dn, None, None, None, None, None
 
 
+class _LpipsInputC1(torch.autograd.Function):
+    """_LpipsInput for a one-channel image [B,1,H,W]: ScalingLayer's broadcast (lpips.py:56-63) fills channels 0..2 from the one x_rec;
+    the gradient is the sum over the three channels in a fixed order.  Schedules -1, 0 and 1."""
+
+    @staticmethod
+    def forward(ctx, a, n_pred, x_noisy, t, shift, scale, schedule):
+        a = _chk(a, "C_pred" if schedule >= 0 else "image")
+        B, _, H, W = a.shape
+        if schedule == 1:
+            n_pred, x_noisy, t = _chk(n_pred, "noise_pred"), _chk(x_noisy, "x_noisy"), _chk(t, "t")
+            if n_pred.shape != a.shape or x_noisy.shape != a.shape:
+                raise RuntimeError("adm_amd: noise_pred and x_noisy must be one-channel like C_pred")
+        y = _new((B, H, W, 32), a)
+        call("adm_lpips_input_c1", ptr(a), ptr(n_pred), ptr(x_noisy), ptr(t), ptr(shift), ptr(scale), ptr(y), B, H * W, schedule)
+        ctx.save_for_backward(t if schedule == 1 else None, scale)
+        ctx.meta = (tuple(a.shape), schedule)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        t, scale = ctx.saved_tensors
+        (B, _, H, W), schedule = ctx.meta
+        dy = _chk(dy, "dy")
+        da = _new((B, 1, H, W), dy)
+        dn = _new((B, 1, H, W), dy) if schedule == 1 else None
+        call("adm_lpips_input_c1_bwd", ptr(dy), ptr(t), ptr(scale), ptr(da), ptr(dn), B, H * W, schedule)
+        return da, dn, None, None, None, None, None
+
+
 def lpips_input(a, n_pred, x_noisy, t, shift, scale, schedule: int):
     """The LPIPS network's input [B,H,W,32] from NCHW tensors: schedule -1 takes the image `a`; 0 ('const') and 1 ('const_2')
     take a = C_pred and rebuild x_rec (ddm_const.py:326 / ddm_const_2.py:217); 2 ('linear') takes a = theta_pred [B,6,H,W]
-    (ddm_linear.py:173-176).  Differentiable in a and, for const_2 and linear, n_pred."""
+    (ddm_linear.py:173-176).  Differentiable in a and, for const_2 and linear, n_pred.  A one-channel `a` takes the broadcasting
+    kernel (schedules -1, 0, 1)."""
     if schedule not in (-1, 0, 1, 2):
         raise ValueError(schedule)
+    one_channel = a.dim() == 4 and a.shape[1] == 1
+    if one_channel and schedule == 2:
+        raise NotImplementedError("the linear schedule's LPIPS input is not built for a one-channel image")
     shift, scale = _chk(shift.reshape(-1), "shift"), _chk(scale.reshape(-1), "scale")
     if schedule < 1:
         n_pred = x_noisy = t = None
+    if one_channel:
+        return _LpipsInputC1.apply(a, n_pred, x_noisy, t, shift, scale, int(schedule))
     return _LpipsInput.apply(a, n_pred, x_noisy, t, shift, scale, int(schedule))
 
 

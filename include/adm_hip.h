@@ -465,6 +465,12 @@ int adm_ddm_loss_latent(const float* c_pred, const float* n_pred, const float* x
                         const float* t, const float* w, double* per_sample, double* per_l1, float* d_c, float* d_n,
                         float gscale, int B, long n, int schedule, int use_l1,
                         hipStream_t stream);
+/* Pixel-space loss with use_l1 (ddm_const.py:343-348 / ddm_const_2.py:235-240): the L1 twins are per-sample MEANS over n = C H W,
+ * loss_simple_b = [w1 (SSE_C + L1_C / n) + w2 (SSE_eps + L1_eps / n)] / 2.  sums = fp64 [B][4] = un-weighted (SSE_C, SSE_eps, L1_C,
+ * L1_eps), zero-filled by the call; the caller combines them.  dCp = gscale 0.5 w1 (2 (Cp + x0) + sign(Cp + x0) / n), dNp likewise
+ * with w2 and Np - noise; sign(0) = 0.  w = [B][2].  d_c and d_n may both be NULL (no gradients).  Chunking as adm_ddm_loss. */
+int adm_ddm_loss_l1(const float* c_pred, const float* n_pred, const float* x0, const float* noise, const float* w, double* sums,
+                    float* d_c, float* d_n, float gscale, int B, long n, hipStream_t stream);
 /* One deterministic sampler update in fp64 (ddm_const.py:450-455 / ddm_const_2.py:363-368):
  * x0 = x - C t - eps g(t); [clamp]; x_next = x0 + C t' + eps g(t');  if last: clamp, /scale, (x+1)/2 */
 int adm_sampler_step(double* x, const float* c_pred, const float* n_pred, double t_cur, double t_next, int schedule,
@@ -718,6 +724,15 @@ int adm_lpips_input(const float* a, const float* n_pred, const float* x_noisy, c
  * d_n = -sqrt(t) d x_rec. */
 int adm_lpips_input_bwd(const float* dy, const float* t, const float* scale, float* d_a, float* d_n, int B, int HW,
                         int schedule, hipStream_t stream);
+
+/* The same for a one-channel image: a, n_pred, x_noisy are [B][1][HW] and ScalingLayer's broadcast gives channels 0..2 =
+ * (x_rec - shift[c]) / scale[c] from the one x_rec (lpips.py:56-63).  Schedules -1, 0 and 1 only; 2 returns ADM_EINVAL.
+ * The adjoint sums d x_rec = dy0 / scale0 + dy1 / scale1 + dy2 / scale2 in that fixed order (no atomics) and applies the schedule's
+ * factor; schedule 1 also writes d_n.  d_a, d_n: [B][1][HW]. */
+int adm_lpips_input_c1(const float* a, const float* n_pred, const float* x_noisy, const float* t, const float* shift,
+                       const float* scale, float* y, int B, int HW, int schedule, hipStream_t stream);
+int adm_lpips_input_c1_bwd(const float* dy, const float* t, const float* scale, float* d_a, float* d_n, int B, int HW,
+                           int schedule, hipStream_t stream);
 
 /* nn.MaxPool2d(2, 2) of VGG16 `features` on NHWC: x [B][H][W][C] -> y [B][H/2][W/2][C]; H, W even, C % 4 == 0.  The backward
  * finds the maximum again from x (no index tensor) and gives the gradient to the first one in the order (0,0), (0,1), (1,0), (1,1),

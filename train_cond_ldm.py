@@ -73,7 +73,7 @@ class CondTrainer(Trainer):
         self.cond_sample(batch, os.path.join(self.results, f"sample-{milestone}.png"))
 
 
-def main(args):
+def main(args, trainer_cls=None):
     cfg = Cfg(args.cfg)
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("ADM_LOCAL_DEVICE", os.environ.get("LOCAL_RANK", "0")))
@@ -96,7 +96,7 @@ def main(args):
     assert global_batch % world == 0, "split_batches: the YAML batch_size is the global batch"
     stream = batch_stream(cfg.data, global_batch // world, tuple(cfg.data.get("image_size") or model_cfg.image_size), device,
                           seed=1000 + rank)
-    trainer = CondTrainer(ldm, stream, cfg, device, rank, world)
+    trainer = (trainer_cls or CondTrainer)(ldm, stream, cfg, device, rank, world)
     if cfg.trainer.get("test_before", False) and rank == 0:          # train_cond_ldm.py:74-91
         name = f"sample-{cfg.trainer.get('resume_milestone', 0)}_{model_cfg.sampling_timesteps}.png"
         trainer.cond_sample(next(stream), os.path.join(cfg.trainer.results_folder, name))
