@@ -1,5 +1,6 @@
-// Forward kernels of the Swin condition encoder (unet/swin_transformer.py of the reference): the fused shifted-window attention
-// core, LayerNorm with weight and bias over the last axis, and the PatchMerging gather fused with its LayerNorm(4C).
+// Kernels of the Swin condition encoder (unet/swin_transformer.py of the reference): the fused shifted-window attention
+// core, LayerNorm with weight and bias over the last axis, the PatchMerging gather fused with its LayerNorm(4C), their backward
+// kernels, and (at the end) the patch embedding of the single-channel variant fused with its LayerNorm, forward and backward.
 // Everything between them (qkv / proj / MLP / reduction Linears, GELU, residual adds) runs on the existing GEMM and elementwise
 // kernels.  f32 throughout.
 #include "common.h"
@@ -732,6 +733,340 @@ extern "C" int adm_rowscale_add(const float* x, const float* r, const float* s, 
   const long blocks = (total4 + 255) / 256;
   if (blocks > 0x7fffffffL) return ADM_EINVAL;
   hipLaunchKernelGGL(rowscale_add_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, r, s, y, n / 4, total4);
+  ADM_CHECK_LAUNCH();
+  return ADM_OK;
+}
+
+// ================================================================================================
+// Patch embedding of a ONE-channel image fused with its LayerNorm (first_coonv of the single-channel encoder):
+//   x [B][1][H][W] -> conv 4x4 stride 4, no padding (16 FMAs + bias per output) -> LayerNorm over E -> y [B][H/4][W/4][E]
+// in one launch, with neither a channel-padded copy of x nor the pre-norm tensor in memory.  No MFMA (K = 16): the kernel is bound
+// by the store of y.  G = the power of two >= E / 4 (at most 64) lanes share a token, each lane owns Q float4 of its row (quads
+// sub, sub + G of the row), so a wave covers 64 / G consecutive tokens and every store instruction writes whole contiguous rows in
+// 16-byte pieces.  A lane keeps the 16 stem weights of its 4 * Q channels in registers and walks token groups wave, wave + NW, ...
+// The LayerNorm runs on the conv outputs in registers: the mean across the G lanes, then the sum of squared deviations from it.
+// E % 32 == 0, 32 <= E <= PE_MAXE.  Trailing rows / columns of x (H % 4, W % 4) are never read.
+// ================================================================================================
+#define PE_WAVES 4
+#define PE_MAXE 512
+#define PE_PART 19             // floats per channel of a backward partial: dW[16], db, dgamma, dbeta
+#define PE_BWD_MAXBLOCKS 256
+
+struct PatchP {
+  const float* x;
+  int H, W, Ht, Wt, E, vec;      // vec: rows of a patch are read as one float4 (W % 4 == 0 and x 16-byte aligned)
+  long T;                        // B * Ht * Wt tokens
+};
+
+template <int G>
+__device__ __forceinline__ float pe_group_sum(float v) {
+#pragma unroll
+  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ void pe_load_patch(const PatchP& p, long t, float (&px)[16]) {
+  const long hw = (long)p.Ht * p.Wt;
+  const long b = t / hw;
+  const int r = (int)(t - b * hw);
+  const int ty = r / p.Wt, tx = r - ty * p.Wt;
+  const float* src = p.x + ((size_t)b * p.H + 4 * (size_t)ty) * p.W + 4 * (size_t)tx;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (p.vec) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)i * p.W);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) px[4 * i + e] = v[e];
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) px[4 * i + e] = src[(size_t)i * p.W + e];
+    }
+  }
+}
+
+// the stem weights [E][16] and bias of this lane's channels; a lane past the row (E / 4 is no power of two) holds zeros
+template <int G, int Q>
+__device__ __forceinline__ void pe_load_weights(const float* __restrict__ w, const float* __restrict__ cb, int sub, int E4,
+                                                float (&wr)[Q][4][16], float (&br)[Q][4]) {
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int i4 = sub + G * q;
+    const bool on = i4 < E4;
+    const f32x4 bv = on ? *reinterpret_cast<const f32x4*>(cb + i4 * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      br[q][j] = bv[j];
+#pragma unroll
+      for (int k4 = 0; k4 < 4; ++k4) {
+        const f32x4 v = on ? *reinterpret_cast<const f32x4*>(w + ((size_t)i4 * 4 + j) * 16 + k4 * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) wr[q][j][k4 * 4 + e] = v[e];
+      }
+    }
+  }
+}
+
+// conv outputs of this lane's channels, centred on the token's mean (two passes over registers); returns 1 / sqrt(var + eps)
+template <int G, int Q>
+__device__ __forceinline__ float pe_conv_centre(const float (&wr)[Q][4][16], const float (&br)[Q][4], const float (&px)[16], int sub,
+                                                int E4, float eps, float (&c)[Q][4]) {
+  const float invE = 1.0f / (float)(E4 * 4);
+  float sum = 0.f;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float a = br[q][j];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) a = fmaf(wr[q][j][k], px[k], a);
+      c[q][j] = a;
+    }
+    sum += (c[q][0] + c[q][1]) + (c[q][2] + c[q][3]);          // (zeros on a lane past the row)
+  }
+  const float mean = pe_group_sum<G>(sum) * invE;
+  float sq = 0.f;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const bool on = sub + G * q < E4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      c[q][j] = on ? c[q][j] - mean : 0.f;
+      sq = fmaf(c[q][j], c[q][j], sq);
+    }
+  }
+  return 1.0f / sqrtf(pe_group_sum<G>(sq) * invE + eps);
+}
+
+template <int G, int Q>
+__global__ __launch_bounds__(PE_WAVES * 64) void patch_embed_ln_kernel(PatchP p, const float* __restrict__ w,
+                                                                       const float* __restrict__ cb, const float* __restrict__ gamma,
+                                                                       const float* __restrict__ beta, float* __restrict__ y,
+                                                                       float eps) {
+  constexpr int TPW = 64 / G;          // tokens per wave and pass
+  const int lane = threadIdx.x & 63, sub = lane & (G - 1), grp = lane / G;
+  const int E4 = p.E >> 2;
+  float wr[Q][4][16], br[Q][4];
+  pe_load_weights<G, Q>(w, cb, sub, E4, wr, br);
+  f32x4 gr[Q], be[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const bool on = sub + G * q < E4;
+    gr[q] = on ? *reinterpret_cast<const f32x4*>(gamma + (sub + G * q) * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+    be[q] = on ? *reinterpret_cast<const f32x4*>(beta + (sub + G * q) * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  const long NW = (long)gridDim.x * PE_WAVES;
+  const long nTG = (p.T + TPW - 1) / TPW;
+  for (long tg = (long)blockIdx.x * PE_WAVES + (threadIdx.x >> 6); tg < nTG; tg += NW) {          // (wave-uniform trip count)
+    const long t = tg * TPW + grp;
+    const bool live = t < p.T;          // a group past the last token recomputes the last one and stores nothing
+    float px[16], c[Q][4];
+    pe_load_patch(p, live ? t : p.T - 1, px);
+    const float rstd = pe_conv_centre<G, Q>(wr, br, px, sub, E4, eps, c);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const int i4 = sub + G * q;
+      if (live && i4 < E4) {
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = c[q][j] * rstd * gr[q][j] + be[q][j];
+        *reinterpret_cast<f32x4*>(y + (size_t)t * p.E + (size_t)i4 * 4) = o;
+      }
+    }
+  }
+}
+
+static int pe_params(PatchP& p, const float* x, int B, int H, int W, int E) {
+  if (B <= 0 || H < 4 || W < 4 || E < 32 || E > PE_MAXE || (E & 31)) return ADM_EINVAL;
+  p.x = x; p.H = H; p.W = W; p.Ht = H / 4; p.Wt = W / 4; p.E = E;
+  p.vec = (W & 3) == 0 && ((uintptr_t)x & 15) == 0;
+  p.T = (long)B * p.Ht * p.Wt;
+  return ADM_OK;
+}
+
+// G lanes per token, Q float4 per lane: 32 -> (8, 1), 64 -> (16, 1), 96 / 128 -> (32, 1), 160 .. 256 -> (64, 1), above -> (64, 2)
+#define PE_DISPATCH(E)                          \
+  do {                                          \
+    if ((E) <= 32) PE_GO(8, 1);                 \
+    else if ((E) <= 64) PE_GO(16, 1);           \
+    else if ((E) <= 128) PE_GO(32, 1);          \
+    else if ((E) <= 256) PE_GO(64, 1);          \
+    else PE_GO(64, 2);                          \
+  } while (0)
+
+static long pe_token_groups(long T, int E) {
+  const int G = E <= 32 ? 8 : E <= 64 ? 16 : E <= 128 ? 32 : 64;
+  const int tpw = 64 / G;
+  return (T + tpw - 1) / tpw;
+}
+
+extern "C" int adm_patch_embed_ln_fwd(const float* x, const float* w, const float* cb, const float* gamma, const float* beta,
+                                      float* y, int B, int H, int W, int E, float eps, hipStream_t stream) {
+  if (!x || !w || !cb || !gamma || !beta || !y) return ADM_EINVAL;
+  PatchP p;
+  if (pe_params(p, x, B, H, W, E) != ADM_OK) return ADM_EINVAL;
+  if (((uintptr_t)w | (uintptr_t)cb | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)y) & 15) return ADM_EINVAL;
+  long blocks = (pe_token_groups(p.T, E) + 8 * PE_WAVES - 1) / (8 * PE_WAVES);          // ~8 token groups per wave: the weights load once
+  if (blocks > 0x7fffffffL) return ADM_EINVAL;
+#define PE_GO(G, Q) hipLaunchKernelGGL((patch_embed_ln_kernel<G, Q>), dim3((unsigned)blocks), dim3(PE_WAVES * 64), 0, stream, p, w, cb, gamma, beta, y, eps)
+  PE_DISPATCH(E);
+#undef PE_GO
+  ADM_CHECK_LAUNCH();
+  return ADM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Backward of the fused stem: dW [E][16], db, dgamma, dbeta [E] from x and dy; there is no dX (the condition image takes no
+// gradient).  Nothing is saved by the forward: the conv outputs and the token statistics are recomputed from x, as above.
+//   xh = (c - mean) * rstd      dgamma += dy * xh      dbeta += dy      g = dy * gamma
+//   dc = rstd * (g - mean(g) - xh * mean(g * xh))      db += dc      dW[e][k] += dc[e] * patch[k]
+// Same lane layout as the forward; a lane keeps its 4 * Q * 19 sums in registers over its token groups.  Then, in a fixed order:
+// the 64 / G token slots of a wave are added by shuffles, the four waves of a workgroup add into LDS one after the other, the
+// workgroup writes one partial [19 * E] (dW, db, dgamma, dbeta back to back), and patch_embed_bwd_reduce adds the partials in
+// workgroup order.  No float atomics: the same bits every run.
+// ------------------------------------------------------------------------------------------------
+static long pe_bwd_blocks(long T, int E) {
+  long b = (pe_token_groups(T, E) + 4 * PE_WAVES - 1) / (4 * PE_WAVES);
+  return b < 1 ? 1 : b > PE_BWD_MAXBLOCKS ? PE_BWD_MAXBLOCKS : b;
+}
+
+extern "C" long adm_patch_embed_ln_bwd_ws_floats(int B, int H, int W, int E) {
+  PatchP p;
+  if (pe_params(p, nullptr, B, H, W, E) != ADM_OK) return 0;
+  return pe_bwd_blocks(p.T, E) * PE_PART * (long)E;
+}
+
+template <int G, int Q>
+__global__ __launch_bounds__(PE_WAVES * 64) void patch_embed_ln_bwd_kernel(PatchP p, const float* __restrict__ w,
+                                                                           const float* __restrict__ cb,
+                                                                           const float* __restrict__ gamma,
+                                                                           const float* __restrict__ dy, float* __restrict__ part,
+                                                                           float eps) {
+  constexpr int TPW = 64 / G;
+  __shared__ float sP[PE_PART * PE_MAXE];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, sub = lane & (G - 1), grp = lane / G;
+  const int E = p.E, E4 = E >> 2;
+  const float invE = 1.0f / (float)E;
+  float wr[Q][4][16], br[Q][4];
+  pe_load_weights<G, Q>(w, cb, sub, E4, wr, br);
+  f32x4 gr[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q)
+    gr[q] = sub + G * q < E4 ? *reinterpret_cast<const f32x4*>(gamma + (sub + G * q) * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+  float aW[Q][4][16], ab[Q][4], ag[Q][4], at[Q][4];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      ab[q][j] = ag[q][j] = at[q][j] = 0.f;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) aW[q][j][k] = 0.f;
+    }
+  }
+  const long NW = (long)gridDim.x * PE_WAVES;
+  const long nTG = (p.T + TPW - 1) / TPW;
+  for (long tg = (long)blockIdx.x * PE_WAVES + wave; tg < nTG; tg += NW) {
+    const long t = tg * TPW + grp;
+    const bool live = t < p.T;          // a group past the last token runs on the last one with dy = 0: it adds zeros
+    float px[16], c[Q][4];
+    pe_load_patch(p, live ? t : p.T - 1, px);
+    const float rstd = pe_conv_centre<G, Q>(wr, br, px, sub, E4, eps, c);
+    f32x4 d[Q];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const int i4 = sub + G * q;
+      d[q] = live && i4 < E4 ? *reinterpret_cast<const f32x4*>(dy + (size_t)t * E + (size_t)i4 * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        c[q][j] *= rstd;                                   // xh
+        ag[q][j] = fmaf(d[q][j], c[q][j], ag[q][j]);
+        at[q][j] += d[q][j];
+        d[q][j] *= gr[q][j];                               // from here on: dy * gamma
+        s1 += d[q][j];
+        s2 = fmaf(d[q][j], c[q][j], s2);
+      }
+    }
+    const float m1 = pe_group_sum<G>(s1) * invE, m2 = pe_group_sum<G>(s2) * invE;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float dc = rstd * (d[q][j] - m1 - c[q][j] * m2);
+        const float dcv = sub + G * q < E4 ? dc : 0.f;          // (a lane past the row would add -rstd * m1)
+        ab[q][j] += dcv;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) aW[q][j][k] = fmaf(dcv, px[k], aW[q][j][k]);
+      }
+    }
+  }
+  // the token slots of the wave, in a fixed order: afterwards the lanes of slot 0 hold the wave's sums
+#pragma unroll
+  for (int o = G; o < 64; o <<= 1) {
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        ab[q][j] += __shfl_xor(ab[q][j], o, 64);
+        ag[q][j] += __shfl_xor(ag[q][j], o, 64);
+        at[q][j] += __shfl_xor(at[q][j], o, 64);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) aW[q][j][k] += __shfl_xor(aW[q][j][k], o, 64);
+      }
+    }
+  }
+  // the waves of the workgroup, one after the other
+  for (int turn = 0; turn < PE_WAVES; ++turn) {
+    if (wave == turn && grp == 0) {
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        const int i4 = sub + G * q;
+        if (i4 < E4) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int ch = i4 * 4 + j;
+            float* pw = sP + ch * 16;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) pw[k] = turn ? pw[k] + aW[q][j][k] : aW[q][j][k];
+            sP[16 * E + ch] = turn ? sP[16 * E + ch] + ab[q][j] : ab[q][j];
+            sP[17 * E + ch] = turn ? sP[17 * E + ch] + ag[q][j] : ag[q][j];
+            sP[18 * E + ch] = turn ? sP[18 * E + ch] + at[q][j] : at[q][j];
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  float* dst = part + (size_t)blockIdx.x * PE_PART * E;
+  for (int i = threadIdx.x; i < PE_PART * E; i += PE_WAVES * 64) dst[i] = sP[i];
+}
+
+// acc: bit 0 dW, bit 1 db, bit 2 dgamma, bit 3 dbeta -- add to what the destination holds
+__global__ __launch_bounds__(256) void patch_embed_bwd_reduce(const float* __restrict__ part, float* __restrict__ dW,
+                                                              float* __restrict__ db, float* __restrict__ dgamma,
+                                                              float* __restrict__ dbeta, long nb, int E, int acc) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= PE_PART * E) return;
+  float s = 0.f;
+  for (long n = 0; n < nb; ++n) s += part[(size_t)n * PE_PART * E + i];
+  const int which = i < 16 * E ? 0 : (i - 16 * E) / E + 1;
+  float* dst = which == 0 ? dW + i : which == 1 ? db + (i - 16 * E) : which == 2 ? dgamma + (i - 17 * E) : dbeta + (i - 18 * E);
+  *dst = (acc >> which) & 1 ? *dst + s : s;
+}
+
+extern "C" int adm_patch_embed_ln_bwd(const float* x, const float* w, const float* cb, const float* gamma, const float* dy,
+                                      float* dW, float* db, float* dgamma, float* dbeta, float* ws, int B, int H, int W, int E,
+                                      float eps, int accumulate, hipStream_t stream) {
+  if (!x || !w || !cb || !gamma || !dy || !dW || !db || !dgamma || !dbeta || !ws) return ADM_EINVAL;
+  PatchP p;
+  if (pe_params(p, x, B, H, W, E) != ADM_OK) return ADM_EINVAL;
+  if (((uintptr_t)w | (uintptr_t)cb | (uintptr_t)gamma | (uintptr_t)dy) & 15) return ADM_EINVAL;
+  const long blocks = pe_bwd_blocks(p.T, E);
+#define PE_GO(G, Q) hipLaunchKernelGGL((patch_embed_ln_bwd_kernel<G, Q>), dim3((unsigned)blocks), dim3(PE_WAVES * 64), 0, stream, p, w, cb, gamma, dy, ws, eps)
+  PE_DISPATCH(E);
+#undef PE_GO
+  ADM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(patch_embed_bwd_reduce, dim3((unsigned)adm_cdiv((long)PE_PART * E, 256)), dim3(256), 0, stream, ws, dW, db, dgamma,
+                     dbeta, blocks, E, accumulate);
   ADM_CHECK_LAUNCH();
   return ADM_OK;
 }

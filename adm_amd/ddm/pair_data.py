@@ -1,5 +1,5 @@
-"""Saliency training pairs on the HIP hot path: the batches of ``ddm.data.DUTSDataset`` (ddm/data.py:953-1026 of the reference) made
-by one kernel launch from two uint8 pools resident in device memory.
+"""Saliency and sketch-to-image training pairs on the HIP hot path: the batches of ``ddm.data.DUTSDataset`` (ddm/data.py:953-1026 of
+the reference) and ``ddm.data.SketchDataset`` (:1028-1103) made by one kernel launch from two uint8 pools resident in device memory.
 
 The reference makes each pair on the host with PIL: the RGB photo and its grey ground-truth map are opened [:1002-1004], both
 resized to ``image_size`` with the antialiased bilinear filter [:982-983, Resize -> F.resize -> Image.resize], flipped with one
@@ -10,7 +10,9 @@ A table depends on (in_size, out_size) only: ``build_table_pool`` makes one per 
 ``adm_pair_resize_batch`` (adm_amd/csrc/pair_data.hip) looks a sample's tables up through its image index and runs PIL's integer
 two-pass arithmetic, so the bytes are PIL's.  No floating-point coefficient arithmetic happens on the device.
 
-``DUTSBatchStream`` is the batch source of train_cond_ldm.py and, with ``split: test``, of sample_cond_ldm.py.  The draws live on the
+``DUTSBatchStream`` and ``SketchBatchStream`` (the same pool and draws with the roles of the two planes exchanged: the photo is the
+``image``, the one-channel sketch the ``cond``) are batch sources of train_cond_ldm.py and, with ``split: test``, of
+sample_cond_ldm.py.  The draws live on the
 device: no ``.item()`` / ``.cpu()`` and no dataloader workers on the per-step path.
 """
 from __future__ import annotations
@@ -28,6 +30,8 @@ from .sr_data import PoolStream, _draw, resample_table
 LDS_BUDGET = 64 * 1024          # kLdsBudget of adm_amd/csrc/pair_data.hip
 DUTS_CLASSES = ("ddm.data.DUTSDataset", "DUTSDataset")
 SPLIT_DIRS = {"train": "DUTS-TR", "test": "DUTS-TE"}          # data.py:964-967
+SKETCH_CLASSES = ("ddm.data.SketchDataset", "SketchDataset")
+SKETCH_SPLIT_DIRS = {"train": "train", "test": "val"}         # data.py:1039-1042
 
 
 def pack_bytes(images: Sequence[np.ndarray], channels: int, what: str):
@@ -221,46 +225,51 @@ def synthetic_sizes(out_hw, n: int) -> List[Tuple[int, int]]:
     return [kinds[i % len(kinds)] for i in range(n)]
 
 
-class DUTSBatchStream(PoolStream):
-    """Infinite iterator of {'image': map [B,1,H,W], 'cond': photo [B,3,H,W]} in [-1, 1] on the GPU, keyed in the order
-    ddm.data.DUTSDataset keys them (data.py:1026).
-
-    Sources, in this order: ``data.class_name: ddm.data.DUTSDataset`` + ``data_root`` (``find_duts_pairs``; decoded once at start-up
-    into the two packed pools); ``data.class_name: synthetic`` with ``synthetic_of: ddm.data.DUTSDataset`` (U(0,255) pools drawn on the
-    device, of a few sizes around ``image_size``).  Anything else raises.
+class PairBatchStream(PoolStream):
+    """Infinite iterator of (RGB, grey) pair batches in [-1, 1] on the GPU from a ``PairPool``: what the saliency and the
+    sketch-to-image streams share.  A subclass names its dataset (``CLASSES``, ``LABEL``), loads its files (``load``) and says which
+    plane is the batch's ``image`` and which its ``cond`` (``ROLES`` = the keys of (rgb, grey)).
 
     ``split: train`` draws the image order as SRBatchStream does (a fresh permutation per epoch, continued across the boundary) and the
-    flip with p = 0.5 when ``augment_horizontal_flip``.  ``split: test`` walks the pairs in sorted order without flips (data.py:987-991)
-    and its batches carry ``img_name`` and ``ori_size`` = [(h, w)] of the photos (:1026); ``names`` / ``ori_sizes`` hold them for the
-    whole pool.  ``next_batch(idx=, flip=)`` accepts injected draws."""
+    flip with p = 0.5 when ``augment_horizontal_flip``.  ``split: test`` walks the pairs in sorted order without flips and its
+    batches carry ``img_name`` and ``ori_size`` = [(h, w)] of the photos; ``names`` / ``ori_sizes`` hold them for the whole pool.
+    ``next_batch(idx=, flip=)`` accepts injected draws."""
 
     SYNTHETIC_PAIRS = 32
+    CLASSES: Tuple[str, ...] = ()
+    LABEL = ""
+    ROLES = ("cond", "image")
+    SYNTHETIC_NAME = "{:010d}.png"
+
+    @staticmethod
+    def load(data_root: str, split: str):
+        raise NotImplementedError
 
     def __init__(self, data_cfg, batch, image_size, device, seed):
         data_cfg = data_cfg or {}
+        full = self.CLASSES[0]
         self.split = data_cfg.get("split") or "train"
         if self.split not in ("train", "test"):
-            raise NotImplementedError(f"data.split {self.split!r}: DUTSDataset.__getitem__ raises for anything but 'train' / 'test' "
-                                      "(data.py:1013-1018)")
+            raise NotImplementedError(f"data.split {self.split!r}: {full}.__getitem__ raises for anything but 'train' / 'test'")
         train = self.split == "train"
         super().__init__(batch, device, seed, train and bool(data_cfg.get("augment_horizontal_flip", False)))
         self.size = (int(image_size[0]), int(image_size[1]))
         cls = data_cfg.get("class_name")
-        if cls in DUTS_CLASSES:
+        if cls in self.CLASSES:
             if not data_cfg.get("data_root"):
-                raise ValueError("data.class_name ddm.data.DUTSDataset needs data.data_root")
-            photos, maps, names = load_duts(data_cfg.get("data_root"), self.split)
+                raise ValueError(f"data.class_name {full} needs data.data_root")
+            photos, maps, names = self.load(data_cfg.get("data_root"), self.split)
             self.pool = PairPool.from_arrays(photos, maps, self.size, device, names)
-        elif cls == "synthetic" and data_cfg.get("synthetic_of") in DUTS_CLASSES:
+        elif cls == "synthetic" and data_cfg.get("synthetic_of") in self.CLASSES:
             self.pool = PairPool.from_uniform_draws(synthetic_sizes(self.size, self.SYNTHETIC_PAIRS), self.size, device, self.gen)
         else:
-            raise NotImplementedError(f"data.class_name {cls!r}: only ddm.data.DUTSDataset + data_root, or 'synthetic' with "
-                                      "synthetic_of: ddm.data.DUTSDataset (U(0,255) pairs, benchmarking only) are implemented")
-        self.names = self.pool.names or [f"{i: 010d}.jpg" for i in range(self.pool.n)]
+            raise NotImplementedError(f"data.class_name {cls!r}: only {full} + data_root, or 'synthetic' with "
+                                      f"synthetic_of: {full} (U(0,255) pairs, benchmarking only) are implemented")
+        self.names = self.pool.names or [self.SYNTHETIC_NAME.format(i) for i in range(self.pool.n)]
         self.ori_sizes = [(int(h), int(w)) for h, w in self.pool.hw_host[0]]
         self._cursor = 0          # split: test
-        print(f"DUTS pool: {self.pool.n} pairs, {len(self.pool.tables['keys'])} resize tables, {self.pool.nbytes / 2 ** 20:.1f} MiB "
-              "resident in device memory")
+        print(f"{self.LABEL} pool: {self.pool.n} pairs, {len(self.pool.tables['keys'])} resize tables, "
+              f"{self.pool.nbytes / 2 ** 20:.1f} MiB resident in device memory")
 
     def draw(self):
         """(idx, flip) of one batch, int32 device tensors.  ``split: test``: the next ``batch`` pairs in order (wrapping), no flip."""
@@ -278,9 +287,11 @@ class DUTSBatchStream(PoolStream):
             d = self.draw()
             idx, flip = (g if v is None else v for v, g in zip((idx, flip), d))
         rgb, gray, rgb_u8, gray_u8 = pair_batch(self.pool, idx, flip, want_u8)
-        out = {"image": gray, "cond": rgb}
+        k_rgb, k_gray = self.ROLES
+        planes = {k_rgb: (rgb, rgb_u8), k_gray: (gray, gray_u8)}
+        out = {k: planes[k][0] for k in ("image", "cond")}          # 'image' first, as both datasets key their samples
         if want_u8:
-            out["image_u8"], out["cond_u8"] = gray_u8, rgb_u8
+            out.update({k + "_u8": planes[k][1] for k in ("image", "cond")})
         if host_idx is not None:
             n = self.pool.n
             out["img_name"] = [self.names[min(max(i, 0), n - 1)] for i in host_idx]
@@ -289,3 +300,73 @@ class DUTSBatchStream(PoolStream):
 
     def __next__(self):
         return self.next_batch()
+
+
+class DUTSBatchStream(PairBatchStream):
+    """{'image': map [B,1,H,W], 'cond': photo [B,3,H,W]}, keyed in the order ddm.data.DUTSDataset keys them (data.py:1026).
+
+    Sources, in this order: ``data.class_name: ddm.data.DUTSDataset`` + ``data_root`` (``find_duts_pairs``; decoded once at start-up
+    into the two packed pools); ``data.class_name: synthetic`` with ``synthetic_of: ddm.data.DUTSDataset`` (U(0,255) pools drawn on the
+    device, of a few sizes around ``image_size``).  Anything else raises.  Splits as in data.py:987-991, 1013-1018."""
+
+    CLASSES = DUTS_CLASSES
+    LABEL = "DUTS"
+    ROLES = ("cond", "image")
+    SYNTHETIC_NAME = "{: 010d}.jpg"
+    load = staticmethod(load_duts)
+
+
+def find_sketch_pairs(data_root: str, split: str = "train"):
+    """[(photo path, sketch path)] sorted by photo path: the reference's discovery (data.py:1039-1057) -- every ``*.png`` below
+    ``data_root/GT/{train|val}`` (``split: test`` reads ``val``; any other split: ``data_root`` itself) whose name does not start
+    with ``._``, its sketch at the same relative path below the sibling tree ``Sketch``.  DEVIATION: a missing sketch raises here and
+    names the file; the reference substitutes a random other sample at run time (:1074-1084)."""
+    from pathlib import Path
+    root = Path(data_root)
+    if split in SKETCH_SPLIT_DIRS:
+        folder, sketches = root / "GT" / SKETCH_SPLIT_DIRS[split], root / "Sketch" / SKETCH_SPLIT_DIRS[split]
+    else:          # the reference's own rule for a bare folder: .../GT/<split>/<class>/<name> -> .../Sketch/<split>/<class>/<name>
+        folder, sketches = root, None
+    photos = sorted(p for p in folder.rglob("*.png") if not p.name.startswith("._"))
+    if not photos:
+        raise FileNotFoundError(f"data.data_root: no png photo below {folder}")
+    pairs = []
+    for p in photos:
+        if sketches is not None:
+            s = sketches / p.relative_to(folder)
+        else:
+            top = p.parent.parent.parent
+            s = top.parent / top.name.replace("GT", "Sketch") / p.parent.parent.name / p.parent.name / p.name
+        if not s.is_file():
+            raise FileNotFoundError(f"the sketch of {p} is missing: {s}")
+        pairs.append((p, s))
+    return pairs
+
+
+def load_sketch(data_root: str, split: str = "train"):
+    """(photos uint8 [H,W,3], sketches uint8 [H,W], photo file names): decoded once with PIL, ``.convert('RGB')`` / ``.convert('L')``
+    (data.py:1079-1081).  An unreadable file raises and names itself."""
+    from PIL import Image
+    photos, sketches, names = [], [], []
+    for p, s in find_sketch_pairs(data_root, split):
+        for path, mode, dst in ((p, "RGB", photos), (s, "L", sketches)):
+            try:
+                dst.append(np.asarray(Image.open(path).convert(mode), dtype=np.uint8))
+            except Exception as e:
+                raise OSError(f"{path} cannot be read as an image: {e}") from e
+        names.append(p.name)
+    return photos, sketches, names
+
+
+class SketchBatchStream(PairBatchStream):
+    """{'image': photo [B,3,H,W], 'cond': sketch [B,1,H,W]}, keyed as ddm.data.SketchDataset keys them (data.py:1103): the
+    sketch-to-image recipe GENERATES the photo, so the roles are the opposite of the saliency stream's.
+
+    Sources: ``data.class_name: ddm.data.SketchDataset`` + ``data_root`` (``find_sketch_pairs``), or ``class_name: synthetic`` with
+    ``synthetic_of: ddm.data.SketchDataset``.  Both planes are resized to ``image_size`` with PIL's antialiased bilinear filter and
+    flipped with one draw (data.py:1059-1063, 1090-1093) by ``adm_pair_resize_batch``."""
+
+    CLASSES = SKETCH_CLASSES
+    LABEL = "sketch"
+    ROLES = ("image", "cond")
+    load = staticmethod(load_sketch)

@@ -2,7 +2,8 @@
 beyond ``adm_amd.ops`` / ``adm_amd.ops_cond``.  NHWC fp32 CUDA tensors, no CPU / eager fallback.  ``window_attention``,
 ``layer_norm``, ``merge_layer_norm`` and ``nhwc_to_nchw`` are autograd Functions with HIP backward kernels; when nothing
 requires grad (the frozen encoder: its forward runs under no_grad) they are the plain forward launches they always were.
-``row_scale_add`` is stochastic depth in "row" mode.  The training path is f32 only: in the bf16 compute mode it raises.
+``row_scale_add`` is stochastic depth in "row" mode.  ``patch_embed_ln`` is the stem of the single-channel encoder (4x4 stride-4
+conv of a one-channel image + LayerNorm in one kernel; parameter gradients only).  The training path is f32 only: in the bf16 compute mode it raises.
 """
 from __future__ import annotations
 
@@ -184,6 +185,63 @@ def merge_layer_norm(x, weight, bias, eps: float = 1e-5):
         return _LayerNorm.apply(x, weight, bias, float(eps), True)
     x = _chk(x, "x")
     return _merge_layer_norm(x, *_ln_params(weight, bias, 4 * x.shape[-1], "PatchMerging norm"), eps)
+
+
+def _patch_embed_args(x, conv_w, conv_b, ln_w, ln_b):
+    if x.dim() != 4 or x.shape[1] != 1:
+        raise RuntimeError(f"patch_embed_ln takes an NCHW image with 1 channel, got {tuple(x.shape)}")
+    E = conv_w.shape[0]
+    if tuple(conv_w.shape) != (E, 1, 4, 4) or any(t.numel() != E for t in (conv_b, ln_w, ln_b)):
+        raise RuntimeError(f"patch_embed_ln: stem weight {tuple(conv_w.shape)} (expected [E, 1, 4, 4]), bias {tuple(conv_b.shape)}, "
+                           f"norm {tuple(ln_w.shape)} / {tuple(ln_b.shape)}")
+    B, _, H, W = x.shape
+    return B, H, W, E
+
+
+def _patch_embed_ln(x, cw, cb, lw, lb, eps):
+    B, H, W, E = _patch_embed_args(x, cw, cb, lw, lb)
+    y = _new((B, H // 4, W // 4, E), x)
+    call("adm_patch_embed_ln_fwd", ptr(x), ptr(cw), ptr(cb), ptr(lw), ptr(lb), ptr(y), B, H, W, E, float(eps))
+    return y
+
+
+class _PatchEmbedLN(torch.autograd.Function):
+    """Saves x and the four parameters: the backward kernel recomputes the conv outputs and the token statistics."""
+
+    @staticmethod
+    def forward(ctx, x, conv_w, conv_b, ln_w, ln_b, eps):
+        params = (conv_w, conv_b, ln_w, ln_b)
+        y = _patch_embed_ln(x, *(_chk(p.detach(), "parameter") for p in params), eps)
+        ctx.save_for_backward(x, *params)
+        _mark_uses(ctx, *((i + 1, p) for i, p in enumerate(params)))
+        ctx.eps = float(eps)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, *params = ctx.saved_tensors
+        dy = _chk(dy, "dy")
+        B, H, W, E = _patch_embed_args(x, *params)
+        want = [ctx.needs_input_grad[i + 1] for i in range(4)]
+        sinks = [_param_grad(p, w) for p, w in zip(params, want)]
+        ws = _new((hip.lib().adm_patch_embed_ln_bwd_ws_floats(B, H, W, E),), x)
+        cw, cb, lw, _ = (_chk(p.detach(), "parameter") for p in params)
+        call("adm_patch_embed_ln_bwd", ptr(x), ptr(cw), ptr(cb), ptr(lw), ptr(dy), *(ptr(d) for d, _ in sinks), ptr(ws), B, H, W, E,
+             ctx.eps, sum(int(acc) << i for i, (_, acc) in enumerate(sinks)))
+        return (None, *(_hand_over(p, d, w, acc) for p, w, (d, acc) in zip(params, want, sinks)), None)
+
+
+def patch_embed_ln(x, conv_w, conv_b, ln_w, ln_b, eps: float = 1e-5):
+    """Conv2d(1, E, 4, 4) + LayerNorm(E) of a one-channel NCHW image in one kernel: [B, 1, H, W] -> [B, H // 4, W // 4, E] NHWC
+    (E a multiple of 32, at most 512; H, W >= 4).  Differentiable in the four parameters only: the condition image never takes a
+    gradient, so an ``x`` that requires one is refused."""
+    if x.requires_grad:
+        raise RuntimeError("patch_embed_ln has no gradient for its input image (the condition takes none): detach it")
+    x = _chk(x, "x")
+    if _wants_grad(conv_w, conv_b, ln_w, ln_b):
+        _patch_embed_args(x, conv_w, conv_b, ln_w, ln_b)
+        return _PatchEmbedLN.apply(x, conv_w, conv_b, ln_w, ln_b, float(eps))
+    return _patch_embed_ln(x, *(_chk(p.detach(), "parameter") for p in (conv_w, conv_b, ln_w, ln_b)), eps)
 
 
 _ONE: dict = {}

@@ -16,7 +16,8 @@ The condition ENCODER ``init_conv_mask`` (cond_unet_sd.py:637-650): ``cond_encod
 ``adm_amd.unet.swin_transformer`` (frozen by default: the reference's ``fix_bb: True`` state; ``train_cond_encoder=True``, also as
 a key of the YAML's ``unet:`` section, calls its ``enable_training()`` so that it trains with the denoiser as under the reference's
 ``fix_bb: False``; its weights come from the checkpoint's ``init_conv_mask.*`` tensors, or for a fresh
-training run from the local file ``cond_encoder_weights`` names; nothing is fetched).  EfficientNet-B7, ResNet-101 and the single-channel Swin variant
+training run from the local file ``cond_encoder_weights`` names; nothing is fetched).  ``single_channel_cond: True`` (keyword or cfg) makes it the one-channel variant (``swin_b(in_chans=1)``, the
+reference's swin_transformer_for_sci) in this two-decoder class; cond_unet_sd.Unet refuses it.  EfficientNet-B7 and ResNet-101
 are not built.  With ``cond_encoder=None`` (the default) the encoder's output -- four feature maps of f, 2f, 4f, 8f channels
 (f = 128 for Swin-B) at 1/4, 1/8, 1/16, 1/32 of the condition image -- is what ``forward`` takes as ``mask`` (a list of four NCHW
 tensors); a user-supplied ``cond_encoder`` callable returns it for the condition image.
@@ -315,9 +316,11 @@ class Unet(nn.Module):
         if isinstance(cond_encoder, str):
             if cond_encoder != "swin_b" or cond_net != "swin":
                 raise NotImplementedError(f"cond_encoder {cond_encoder!r} with cond_net {cond_net!r}: the built-in encoder is 'swin_b'")
-            if kwargs.get("single_channel_cond", False):
-                raise NotImplementedError("single_channel_cond (swin_transformer_for_sci) is not built")
-            cond_encoder = swin_b(fix_bb=bool(kwargs.get("fix_bb", False)))
+            single = bool(_cfg_get(cfg, "single_channel_cond", kwargs.get("single_channel_cond", False)))
+            if single and not self.two_decoders:
+                raise NotImplementedError("single_channel_cond (swin_transformer_for_sci) is built for the two-decoder unet.cond_unet.Unet "
+                                          "only: no reference config pairs it with cond_unet_sd.Unet")
+            cond_encoder = swin_b(fix_bb=bool(kwargs.get("fix_bb", False)), in_chans=1 if single else 3)
             if cond_encoder_weights:          # a local file in torchvision's Swin-B layout (the reference fetches these weights)
                 load_encoder_weights(cond_encoder, cond_encoder_weights)
             if train_cond_encoder:

@@ -14,7 +14,11 @@ reference leaves their ``.grad`` at None), makes ``forward`` run with grad throu
 ``adm_amd.ops_swin``, and switches stochastic depth on in ``.train()`` mode: torchvision's ``StochasticDepth(p_k, "row")`` around
 both branches of block k, p_k = p * k / (n_blocks - 1) (reference :292,303-304,379), restated in ``ops_swin.row_scale_add``.
 Nothing is ever fetched: the weights come from the checkpoint of the conditional model.  Attention / output dropout (0.0 in
-every config), the single-channel variant, EfficientNet-B7 and ResNet-101 are not built.
+every config), EfficientNet-B7 and ResNet-101 are not built.
+
+``in_chans=1`` is the single-channel variant (/root/reference/unet/swin_transformer_for_sci.py, ``single_channel_cond: True``): the
+patch-embedding conv takes one channel (reference :365) and runs fused with its LayerNorm in ``ops_swin.patch_embed_ln``;
+``load_encoder_weights`` averages a 3-channel ImageNet stem over its input channels (reference :458-459).  Everything else is shared.
 
 Reference lines restated: PatchMerging :51-68, shifted_window_attention :71-168, ShiftedWindowAttention :174-248,
 SwinTransformerBlock :251-305, SwinTransformer :308-425.
@@ -115,8 +119,12 @@ class SwinTransformerBlock(nn.Module):
 class SwinTransformer(nn.Module):
     def __init__(self, patch_size: List[int], embed_dim: int, depths: List[int], num_heads: List[int], window_size: List[int],
                  mlp_ratio: float = 4.0, dropout: float = 0.0, attention_dropout: float = 0.0, stochastic_depth_prob: float = 0.0,
-                 num_classes: int = 1000, norm_layer=None, block=None, fix_bb: bool = True):
+                 num_classes: int = 1000, norm_layer=None, block=None, fix_bb: bool = True, in_chans: int = 3):
         super().__init__()
+        if in_chans not in (1, 3):
+            raise NotImplementedError(f"the condition encoder takes 3-channel images or, as the single-channel variant, 1-channel ones; "
+                                      f"in_chans={in_chans} is not built")
+        self.in_chans = int(in_chans)
         if list(patch_size) != [4, 4] or embed_dim % 32 or len(depths) != 4 or len(num_heads) != 4:
             raise NotImplementedError("4x4 patches, an embedding width that is a multiple of 32 and four stages (every reference "
                                       "config) are what is built")
@@ -127,7 +135,7 @@ class SwinTransformer(nn.Module):
         self.stochastic_depth_prob = float(stochastic_depth_prob)      # used only after enable_training()
         self.trainable = False
         self._warned = False
-        self.first_coonv = nn.Sequential(nn.Conv2d(3, embed_dim, kernel_size=4, stride=4), nn.Identity(), norm_layer(embed_dim))
+        self.first_coonv = nn.Sequential(nn.Conv2d(self.in_chans, embed_dim, kernel_size=4, stride=4), nn.Identity(), norm_layer(embed_dim))
         layers: List[nn.Module] = []
         for i_stage in range(len(depths)):
             dim = embed_dim * 2 ** i_stage
@@ -200,8 +208,8 @@ class SwinTransformer(nn.Module):
             self._warned = True
             warnings.warn("SwinTransformer: the backbone is frozen in this build (forward only, eval semantics) until "
                           "enable_training() is called (Unet(..., train_cond_encoder=True)); fix_bb: False alone does not train it")
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise RuntimeError(f"the condition encoder takes an NCHW image with 3 channels, got {tuple(x.shape)}")
+        if x.dim() != 4 or x.shape[1] != self.in_chans:
+            raise RuntimeError(f"the condition encoder takes an NCHW image with {self.in_chans} channels, got {tuple(x.shape)}")
         blocks = self.blocks()
         scales = None
         if self.trainable and self.training and any(b.sd_prob > 0.0 for b in blocks):
@@ -213,8 +221,11 @@ class SwinTransformer(nn.Module):
             inv = torch.tensor([1.0 / (1.0 - b.sd_prob) for b in blocks], device=x.device, dtype=torch.float32)
             scales = (keep.to(device=x.device, dtype=torch.float32) * inv[:, None, None]).contiguous()
         conv, ln = self.first_coonv[0], self.first_coonv[2]
-        h = oc.conv2d_generic(ops.nchw_to_nhwc(x.contiguous(), None, 32), conv.weight, conv.bias, stride=4, pad=0)
-        h = osw.layer_norm(h, ln.weight, ln.bias, ln.eps)
+        if self.in_chans == 1:
+            h = osw.patch_embed_ln(x.to(torch.float32), conv.weight, conv.bias, ln.weight, ln.bias, ln.eps)
+        else:
+            h = oc.conv2d_generic(ops.nchw_to_nhwc(x.contiguous(), None, 32), conv.weight, conv.bias, stride=4, pad=0)
+            h = osw.layer_norm(h, ln.weight, ln.bias, ln.eps)
         feats = []
         k = 0
         for i, layer in enumerate(self.features):
@@ -237,8 +248,9 @@ def load_encoder_weights(encoder: SwinTransformer, path: str) -> List[str]:
     the reference pairs the two key lists in order (:455-457): ``features.0.{0,2}`` -> ``first_coonv.{0,2}``, ``features.k`` ->
     ``features.k-1``.  Otherwise the names are the encoder's own.  After that every ``features.*`` tensor of the encoder must be
     present with its shape, and no tensor of the file may be unknown or of another shape; ``first_coonv.*``, ``norm.*`` and
-    ``head.*`` may be absent (they keep their initial values; a ``head`` of another class count is ignored).  Returns the names
-    that were absent."""
+    ``head.*`` may be absent (they keep their initial values; a ``head`` of another class count is ignored).  Into a one-channel
+    encoder a ``[E, 3, 4, 4]`` stem weight loads as its mean over the input channels (reference swin_transformer_for_sci.py
+    :458-459); a ``[E, 1, 4, 4]`` one loads as it is.  Returns the names that were absent."""
     sd = torch.load(path, map_location="cpu", weights_only=True)
     if not isinstance(sd, dict) or not all(isinstance(v, torch.Tensor) for v in sd.values()):
         raise RuntimeError(f"{path}: expected a flat state dict of tensors")
@@ -253,6 +265,9 @@ def load_encoder_weights(encoder: SwinTransformer, path: str) -> List[str]:
             renamed[k] = v
         sd = renamed
     own = encoder.state_dict()
+    stem = sd.get("first_coonv.0.weight")
+    if stem is not None and encoder.in_chans == 1 and stem.dim() == 4 and stem.shape[1] == 3:
+        sd = {**sd, "first_coonv.0.weight": stem.mean(dim=1, keepdim=True)}
     unknown = [k for k in sd if k not in own]
     if unknown:
         raise RuntimeError(f"{path}: {len(unknown)} tensors the encoder does not have (first: {unknown[0]})")

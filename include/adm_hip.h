@@ -852,6 +852,24 @@ int adm_swin_merge_ln_bwd(const float* x, const float* w, const float* dy, float
  * (1 - p).  x == NULL: y = s[b] * r (the gradient of the branch).  A row with s[b] == 0 copies x bit for bit. */
 int adm_rowscale_add(const float* x, const float* r, const float* s, float* y, int B, long n, hipStream_t stream);
 
+/* Patch embedding of a ONE-channel image fused with its LayerNorm (the stem of the single-channel condition encoder): x [B][1][H][W]
+ * f32 -> conv 4x4, stride 4, no padding with w [E][1][4][4] and bias cb [E] -> LayerNorm over E with gamma, beta [E] ->
+ * y [B][H/4][W/4][E] (floor division: trailing rows / columns of x are never read).  One launch; neither a channel-padded copy of x
+ * nor the pre-norm tensor exists in memory.  The statistics are two passes over registers (the mean, then the squared deviations
+ * from it).  E % 32 == 0 and 32 <= E <= 512; anything else, H < 4 or W < 4 returns -22.  w, cb, gamma, beta and y 16-byte aligned;
+ * x is read in 16-byte pieces when it is aligned and W % 4 == 0, else by element. */
+int adm_patch_embed_ln_fwd(const float* x, const float* w, const float* cb, const float* gamma, const float* beta, float* y, int B,
+                           int H, int W, int E, float eps, hipStream_t stream);
+/* Parameter gradients of adm_patch_embed_ln_fwd from x and dy [B][H/4][W/4][E]: dW [E][16], db, dgamma, dbeta [E].  There is no dX.
+ * The conv outputs and the token statistics are recomputed from x (the forward saves nothing).  The sums over tokens go through one
+ * partial per workgroup in ws and a second kernel that adds them in workgroup order: no float atomics, the same bits every run.
+ * accumulate: bit 0 dW, bit 1 db, bit 2 dgamma, bit 3 dbeta -- add to what the destination holds.
+ * ws: adm_patch_embed_ln_bwd_ws_floats(B, H, W, E) floats (need not be cleared; 0 for an unsupported shape). */
+long adm_patch_embed_ln_bwd_ws_floats(int B, int H, int W, int E);
+int adm_patch_embed_ln_bwd(const float* x, const float* w, const float* cb, const float* gamma, const float* dy, float* dW, float* db,
+                           float* dgamma, float* dbeta, float* ws, int B, int H, int W, int E, float eps, int accumulate,
+                           hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,11 @@ With ``data.class_name: ddm.data.DUTSDataset`` and ``split: test`` (saliency, co
 condition is the photo resized to the model's resolution and the windows run at the output's own scale (the reference's
 ``slide_sample``, :220-283: ``slide_sample_sr`` with ``scale=1``); ``sampler.out_channels`` defaults to 1, ``crop_size`` / ``stride`` to
 ``image_size``; each one-channel prediction is written as a mode-L png under the photo's name, and the PSNR is against the resized map.
+
+With ``data.class_name: ddm.data.SketchDataset`` and ``split: test`` (sketch-to-image,
+configs/sketch2img/sketchcoco_cond_ddm_const_ldm_sample.yaml) the condition is the ONE-channel sketch resized to ``image_size`` and the
+output a three-channel image, sampled in one window and written under the sketch's file name.  No PSNR is printed: a generated
+photo has no ground truth to score.
 """
 import argparse
 import importlib
@@ -230,6 +235,29 @@ class DUTSCondStream:
             yield batch
 
 
+SKETCH_CLASSES = ("ddm.data.SketchDataset", "SketchDataset")
+
+
+class SketchCondStream:
+    """``data.class_name: ddm.data.SketchDataset`` with ``split: test`` (``GT/val`` and ``Sketch/val`` below ``data_root``; or
+    ``synthetic`` with ``synthetic_of: ddm.data.SketchDataset``, the uniform-draw pool of the training stream): pair i in sorted order, resized by the kernel that makes the training batches, no flip.  'cond' is the sketch [1,1,H,W]."""
+
+    def __init__(self, data_cfg, n, image_size, device, seed):
+        from adm_amd.ddm.pair_data import SketchBatchStream
+        if (data_cfg.get("split") or "train") != "test":
+            raise ValueError("sampling ddm.data.SketchDataset needs data.split: test (GT/val + Sketch/val, in order, unflipped)")
+        self.n = n
+        self.stream = SketchBatchStream(data_cfg, 1, image_size, device, seed)
+
+    def __iter__(self):
+        s = self.stream
+        for i in range(self.n):
+            batch = s.next_batch(idx=[i % s.pool.n], flip=[0])
+            batch["ori_size"] = batch["ori_size"][0]
+            batch["img_name"] = batch["img_name"][0]          # the sketch's file name (= the photo's: same relative path)
+            yield batch
+
+
 def main():
     ap = argparse.ArgumentParser(description="sliding-window conditional latent sampler (MI355X hot path)")
     ap.add_argument("--cfg", required=True)
@@ -274,6 +302,8 @@ def main():
     per_rank = n_total // world
     inpaint = cfg.data.get("class_name") in INPAINT_CLASSES
     duts = cfg.data.get("class_name") in DUTS_CLASSES
+    sketch = cfg.data.get("class_name") in SKETCH_CLASSES or (cfg.data.get("class_name") == "synthetic"
+                                                               and cfg.data.get("synthetic_of") in SKETCH_CLASSES)
     if inpaint:
         size = tuple(cfg.data.get("image_size") or mc.image_size)
         stream = InpaintCondStream(cfg.data, per_rank, size, device, seed=2000 + rank)
@@ -289,6 +319,12 @@ def main():
         # The reference's saliency sample YAML has neither key, and its own driver would fail on them (cfg.sampler.crop_size, :190):
         # they default to one window, the image at model resolution.
         crop, stride = tuple(s.get("crop_size") or size), tuple(s.get("stride") or size)
+    elif sketch:
+        size = tuple(cfg.data.get("image_size") or mc.image_size)
+        stream = SketchCondStream(cfg.data, per_rank, size, device, seed=2000 + rank)
+        crop = tuple(s.get("crop_size") or size)
+        if crop != size:
+            raise NotImplementedError(f"sketch-to-image samples the whole image in one window: sampler.crop_size {crop} must equal image_size {size}")
     else:
         stream = CondStream(cfg.data, per_rank, device, seed=2000 + rank)
         crop, stride = tuple(s.crop_size), tuple(s.stride)
@@ -305,6 +341,17 @@ def main():
             Image.fromarray(arr).save(os.path.join(out_dir, name))
             if bool(s.get("save_masks", False)):
                 Image.fromarray((mask[0, 0] * 255).to(torch.uint8).cpu().numpy()).save(os.path.join(out_dir, "masks", name))
+            done += 1
+            continue
+        if sketch:          # one window; the generated photo has no ground truth, so nothing is scored
+            if cond.shape[1] != 1 or int(s.get("out_channels", 3)) != 3:
+                raise ValueError(f"sketch-to-image takes a one-channel condition and makes three channels, got cond {tuple(cond.shape)}, "
+                                 f"sampler.out_channels {s.get('out_channels', 3)}")
+            pred = ldm.sample(cond=list(ldm.model.init_conv_mask(cond)),
+                              latent_hw=(cond.shape[2] // down, cond.shape[3] // down)).to(torch.float32)
+            arr = (pred[0].clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0).cpu().numpy()
+            name = batch["img_name"] if world == 1 else f"{rank * per_rank + done: 010d}.png"
+            Image.fromarray(arr).save(os.path.join(out_dir, name))
             done += 1
             continue
         if duts:          # the reference's slide_sample (:220-283): windows over the condition at the output's own resolution
@@ -332,7 +379,8 @@ def main():
         done += 1
     torch.cuda.synchronize()
     dt = time.time() - t0
-    print(f"rank {rank}: {done} images in {dt:.1f}s ({done / max(dt, 1e-9):.2f} images/sec incl. PNG writes); PSNR: {psnr / max(done, 1):.2f}")
+    score = "" if sketch else f"; PSNR: {psnr / max(done, 1):.2f}"
+    print(f"rank {rank}: {done} images in {dt:.1f}s ({done / max(dt, 1e-9):.2f} images/sec incl. PNG writes){score}")
 
 
 if __name__ == "__main__":

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """MI355X counterpart of the reference's conditional LATENT trainer (its train_cond_ldm.py): the 4x super-resolution
 recipe (configs/super-resolution/div2k_cond_ddm_const_ldm_train.yaml), the in-painting recipe
-(configs/inpainting/celebahq_cond_ddm_const_ldm.yaml) and the saliency recipe (configs/saliency/duts_cond_ddm_const_ldm.yaml).
+(configs/inpainting/celebahq_cond_ddm_const_ldm.yaml), the saliency recipe (configs/saliency/duts_cond_ddm_const_ldm.yaml) and the
+sketch-to-image recipe (configs/sketch2img/sketchcoco_cond_ddm_const_ldm.yaml).
 
 Same command line and YAML schema as the other drivers (``--cfg``, ``--max-steps``); model construction, gradient accumulation,
 clip-norm, EMA, the checkpoint layout and the multi-GPU launch are the shared Trainer of train_uncond_dpm.py.  What differs from
@@ -9,7 +10,8 @@ that driver (reference lines of train_cond_ldm.py in brackets):
   * batch source: {'image', 'cond'} pairs of ddm.data.SRDataset [:57-63], made on the device by one HIP kernel from a uint8
     image pool (adm_amd.ddm.sr_data.SRBatchStream) instead of PIL in dataloader workers; with ``data.class_name:
     ddm.data.InpaintDataset`` the {'image', 'cond', 'ori_mask'} triples of adm_amd.ddm.inpaint_data.InpaintBatchStream; with
-    ``ddm.data.DUTSDataset`` the {'image': map, 'cond': photo} pairs of adm_amd.ddm.pair_data.DUTSBatchStream;
+    ``ddm.data.DUTSDataset`` the {'image': map, 'cond': photo} pairs of adm_amd.ddm.pair_data.DUTSBatchStream; with
+    ``ddm.data.SketchDataset`` the {'image': photo, 'cond': sketch} pairs of its SketchBatchStream;
   * LR schedule: ratio max((1 - it/N)^0.96, min_lr/lr) from step 0, no warm-up [:150];
   * weight decay defaults to 1e-2 [:72];
   * the periodic and ``test_before`` samples are conditioned on a training batch: sample(batch_size=cond.shape[0], cond=..., mask=
@@ -28,7 +30,7 @@ import torch.distributed as dist
 
 from train_uncond_dpm import Cfg, Trainer, build_model, parse_args, save_grid
 from adm_amd.ddm.inpaint_data import InpaintBatchStream
-from adm_amd.ddm.pair_data import DUTS_CLASSES, DUTSBatchStream
+from adm_amd.ddm.pair_data import DUTS_CLASSES, SKETCH_CLASSES, DUTSBatchStream, SketchBatchStream
 from adm_amd.ddm.sr_data import SRBatchStream
 from adm_amd.optim import lr_lambda_cond
 
@@ -42,13 +44,15 @@ INPAINT_CLASSES = ("ddm.data.InpaintDataset", "InpaintDataset")
 
 def batch_stream(data_cfg, batch, image_size, device, seed):
     """The batch source ``data.class_name`` names: in-painting triples for ddm.data.InpaintDataset, saliency pairs for
-    ddm.data.DUTSDataset, super-resolution pairs otherwise (SRBatchStream raises for what it does not know).  ``class_name:
+    ddm.data.DUTSDataset, sketch-to-image pairs for ddm.data.SketchDataset, super-resolution pairs otherwise (SRBatchStream raises for what it does not know).  ``class_name:
     synthetic`` stands for the dataset ``data.synthetic_of`` names."""
     cls = data_cfg.get("class_name")
     if cls in INPAINT_CLASSES or (cls == "synthetic" and data_cfg.get("synthetic_of") in INPAINT_CLASSES):
         return InpaintBatchStream(data_cfg, batch, image_size, device, seed)
     if cls in DUTS_CLASSES or (cls == "synthetic" and data_cfg.get("synthetic_of") in DUTS_CLASSES):
         return DUTSBatchStream(data_cfg, batch, image_size, device, seed)
+    if cls in SKETCH_CLASSES or (cls == "synthetic" and data_cfg.get("synthetic_of") in SKETCH_CLASSES):
+        return SketchBatchStream(data_cfg, batch, image_size, device, seed)
     return SRBatchStream(data_cfg, batch, image_size, device, seed)
 
 
