@@ -870,6 +870,36 @@ int adm_patch_embed_ln_bwd(const float* x, const float* w, const float* cb, cons
                            float* dgamma, float* dbeta, float* ws, int B, int H, int W, int E, float eps, int accumulate,
                            hipStream_t stream);
 
+/* ================================================================================================
+ * InceptionV3 feature extractor and feature statistics behind FID / Inception score (csrc/inception.hip).  Forward only, NHWC f32,
+ * channels padded to 32.  These entry points do not look at any compute-mode switch: the math is the exact f32 MFMA.
+ * ================================================================================================ */
+
+/* y[.., yoff : yoff + N] = act(conv(x, w) + bias) for a kh x kw filter (each side 1, 3, 5 or 7), stride 1 or 2, zero padding pad_h /
+ * pad_w (each at most half its side).  x [B][Hin][Win][ldx] with Cin % 32 == 0 channels read (x may itself be a slice of a wider
+ * buffer); wp [N][kh*kw*Cin] with k = (dy*kw + dx)*Cin + c; bias [N] or NULL; N % 32 == 0 -- rows of wp and bias past the real
+ * output channels are zero, so the padded lanes are written as zero.  y has row stride ldy, yoff % 32 == 0, and only columns
+ * yoff .. yoff+N-1 are written; Ho = (Hin + 2 pad_h - kh) / stride + 1, likewise Wo.  act: 1 = ReLU, 0 = none (the fc layer).
+ * tile: -1 = chosen by the launcher, 0..3 = 128x128 / 128x96 / 64x64 / 128x32.  x and wp 16-byte aligned. */
+int adm_conv_rect_relu_fwd(const float* x, const float* wp, const float* bias, float* y, int B, int Hin, int Win, int Cin, int ldx,
+                           int N, int ldy, int yoff, int kh, int kw, int stride, int pad_h, int pad_w, int act, int tile,
+                           hipStream_t stream);
+/* 3x3 pooling of x [B][H][W][ldx] (C % 4 == 0 channels) into y[.., yoff : yoff + C] with row stride ldy.  mode 0: max, stride 2, no
+ * padding (Ho = (H-3)/2 + 1); 1: max, stride 1, pad 1, padding = -inf; 2: average, stride 1, pad 1, divided by the number of taps
+ * inside the image (count_include_pad = False). */
+int adm_pool3x3_fwd(const float* x, float* y, int B, int H, int W, int C, int ldx, int ldy, int yoff, int mode, hipStream_t stream);
+/* x [B][H][W][ldx] -> y [B][C]: spatial mean, summed in float64 in a fixed order. */
+int adm_global_avgpool_fwd(const float* x, float* y, int B, int H, int W, int C, int ldx, hipStream_t stream);
+/* img uint8 [B][3][H][W] -> y [B][299][299][32] f32 (channels 3..31 zero): TensorFlow-1 bilinear resize (align_corners = False; grid =
+ * float(i) * float32(in / out), truncated; hi = min(lo + 1, n - 1); a + (b - a) * d along x, then y; no fma) followed by
+ * (v - 128) / 128.  Equal bit for bit to the same float32 operations on the host. */
+int adm_tf1_resize_norm_u8(const unsigned char* img, float* y, int B, int H, int W, hipStream_t stream);
+/* Streaming first and second moments of feature rows x [n][D] in float64: sum[D] += sum_r (x[r] - shift), outer[D][D] +=
+ * sum_r (x[r] - shift)(x[r] - shift)^T.  first != 0: shift[D] is set to this batch's column mean before anything is added (the
+ * caller clears sum and outer); later calls reuse it.  One thread owns each output element and adds the rows in order: no atomics,
+ * the same bits every run.  The host forms mu = shift + sum / N and sigma = (outer - sum sum^T / N) / (N - 1). */
+int adm_feat_stats_accum(const float* x, int n, int D, double* shift, double* sum, double* outer, int first, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

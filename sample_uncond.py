@@ -8,6 +8,11 @@ in batches of ``sampler.batch_size`` with ``model.sample(batch_size=...)`` (10-s
 and writes them as PNGs named ``f'{i: 010d}.png'`` (reference :168-173 -- note the space flag).
 Each rank samples its own disjoint id range with its own seed; there are no collectives (the reference
 lets every rank write the same names).
+
+``sampler.cal_fid: True`` (with ``sampler.target_path``: an image folder or saved statistics, and ``sampler.inception_weights``: a
+local InceptionV3 state dict) scores the samples after the PNGs are written, as the reference's ``Sampler.cal_fid`` does through
+``fidelity -f -i``: FID against the target and the Inception score, on the HIP extractor (adm_amd/metrics), from the same uint8
+bytes that went into the files.  The result goes to ``<save_folder>/result.json``.  One process only.
 """
 import argparse
 import os
@@ -39,6 +44,17 @@ def load_weights(model, path, use_ema, device):
     return missing, unexpected
 
 
+def check_cal_fid(cfg):
+    """Start-up refusals of ``sampler.cal_fid``, before any device work: one process only; the weights file and the target exist."""
+    s = cfg.get("sampler") or {}
+    if not s.get("cal_fid", False):
+        return
+    from adm_amd.metrics import evaluate
+    evaluate.check_startup(s.get("inception_weights"), "sample_uncond.py (sampler.cal_fid)")
+    if not s.get("target_path") or not os.path.exists(s["target_path"]):
+        raise FileNotFoundError(f"sampler.cal_fid: sampler.target_path {s.get('target_path')!r} does not exist")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfg", required=True)
@@ -47,6 +63,7 @@ def main():
     args = ap.parse_args()
     with open(args.cfg) as f:
         cfg = Cfg(yaml.load(f, Loader=yaml.SafeLoader))
+    check_cal_fid(cfg)
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local)
@@ -55,6 +72,7 @@ def main():
     mc = cfg.model
     dpm = build_model(mc).to(device).eval()          # pixel-space DDPM or LatentDiffusion (+ first stage), reference :50-64
     s = cfg.sampler
+    scorer = None
     if s.get("ckpt_path") and not args.random_init:
         if not os.path.exists(s.ckpt_path):
             raise FileNotFoundError(f"sampler.ckpt_path {s.ckpt_path} does not exist (pass --random-init to sample from "
@@ -73,16 +91,29 @@ def main():
     if args.max_batches is not None:
         n_batches = min(n_batches, args.max_batches)
     img_id, t0, done = rank * per_rank, time.time(), 0
+    if s.get("cal_fid", False):
+        from adm_amd.metrics import evaluate
+        scorer = evaluate.Scorer(s.inception_weights, isc=True, device=device)
+        run = scorer.begin()
     for _ in range(n_batches):
         real_bs = min(bs, per_rank - done)
         batch = dpm.sample(batch_size=real_bs)
-        arr = (batch.clamp(0, 1) * 255).round().to(torch.uint8).permute(0, 2, 3, 1).cpu().numpy()
+        u8 = (batch.clamp(0, 1) * 255).round().to(torch.uint8)
+        if scorer is not None:
+            run.add(u8)                  # the bytes the files hold
+        arr = u8.permute(0, 2, 3, 1).cpu().numpy()
         for j in range(real_bs):
             Image.fromarray(arr[j]).save(os.path.join(out, f"{img_id: 010d}.png"))
             img_id += 1
         done += real_bs
     torch.cuda.synchronize()
     print(f"rank {rank}: {done} images in {time.time() - t0:.1f}s ({done / (time.time() - t0):.1f} images/sec incl. PNG writes)")
+    if scorer is not None:
+        st, logits = run.finish()
+        target = scorer.target_stats(s.target_path, int(s.get("fid_batch_size", 64)))
+        res = evaluate.score(st, target, logits, os.path.join(out, "result.json"))
+        print(f"FID {res['frechet_inception_distance']:.4f}  Inception score {res['inception_score_mean']:.4f} +- "
+              f"{res['inception_score_std']:.4f} ({done} samples)")
 
 
 if __name__ == "__main__":

@@ -17,6 +17,10 @@ bypasses DDP.forward and never synchronises them); images
 Datasets are not shipped: ``data.class_name: synthetic`` draws U(-1,1) images (benchmarking only); ``data.npy`` may point
 at a uint8 [N,32,32,3] .npy file; ``ddm.data.CIFAR10`` + ``img_folder`` reads the standard python batches.  Any other
 data section raises instead of training on noise.
+
+``sampler.test_in_train: True`` (opt-in; no shipped YAML sets it) runs the reference's ``sample_test`` [:339-365] at each milestone:
+EMA samples as PNGs into ``sampler.save_folder``, FID and Inception score into ``result_{milestone}.json``, computed by
+adm_amd/metrics on the HIP InceptionV3 extractor with the local weights file ``sampler.inception_weights``.  One process only.
 """
 import argparse
 import os
@@ -159,6 +163,7 @@ class Trainer:
         self.opt = FusedAdamWEMA(self.flat, lr=self.lr, weight_decay=float(t.get("weight_decay", 1e-4)), max_norm=1.0,
                                  ema=(rank == 0))
         self.warmup_iter = int(t.get("warmup_iter", 5000))      # train_uncond_dpm.py:170
+        self.test_in_train, self.scorer = False, None      # sampler.test_in_train: switched on by this file's main() alone
         self.step = 0
         self.ema_step = 0
         self.ema_initted = False
@@ -242,6 +247,43 @@ class Trainer:
         self.model.train()
         save_grid(img, os.path.join(self.results, f"sample-{milestone}.png"), 4)
 
+    def sample_test(self, milestone):
+        """The reference's Trainer.sample_test (train_uncond_dpm.py:339-365): ``sampler.sample_num`` samples of the EMA weights in
+        batches of ``sampler.batch_size``, written as ``f'{i: 010d}.png'`` into ``sampler.save_folder``, then FID against
+        ``sampler.target_path`` and the Inception score into ``result_{milestone}.json`` of the results folder.  The metrics run on
+        the HIP extractor (adm_amd/metrics) from the bytes the files hold; the target statistics are computed once and cached as
+        ``<target_path>.npz``.  The EMA weights are swapped into the flat parameter buffer for the sampling and swapped back."""
+        from PIL import Image
+        from adm_amd import ops
+        from adm_amd.metrics import evaluate
+        sc = self.cfg.sampler
+        os.makedirs(sc.save_folder, exist_ok=True)
+        if self.scorer is None:
+            self.scorer = evaluate.Scorer(sc.inception_weights, isc=True, device=self.device)
+        num, bs = int(sc.sample_num), int(sc.batch_size)
+        online = self.flat.flat.clone()
+        self.flat.flat.copy_(self.opt.ema)
+        ops.invalidate_packed()
+        self.model.eval()
+        run, img_id = self.scorer.begin(), 0
+        try:
+            with torch.no_grad():
+                while img_id < num:
+                    u8 = (self.model.sample(batch_size=min(bs, num - img_id)).clamp(0, 1) * 255).round().to(torch.uint8)
+                    run.add(u8)
+                    for a in u8.permute(0, 2, 3, 1).cpu().numpy():
+                        Image.fromarray(a).save(os.path.join(sc.save_folder, f"{img_id: 010d}.png"))
+                        img_id += 1
+        finally:
+            self.flat.flat.copy_(online)
+            ops.invalidate_packed()
+            self.model.train()
+        st, logits = run.finish()
+        target = self.scorer.target_stats(sc.target_path, 64)
+        res = evaluate.score(st, target, logits, os.path.join(self.results, f"result_{milestone}.json"))
+        print(f"[sample_test {milestone}] {res}", flush=True)
+        return res
+
     def train(self, max_steps=None):
         last, seen = time.time(), 0
         end = self.train_num_steps if max_steps is None else min(self.train_num_steps, self.step + max_steps)
@@ -285,8 +327,24 @@ class Trainer:
                 self.save(milestone)
                 if self.rank == 0:
                     self.sample_grid(milestone, batch)
+                    if self.test_in_train:
+                        self.sample_test(milestone)
         if self.rank == 0:
             print("training complete")
+
+
+def check_test_in_train(cfg):
+    """Start-up refusals of ``sampler.test_in_train``: one process only, and the weights file and the target must exist."""
+    sc = cfg.get("sampler") or {}
+    if not sc.get("test_in_train", False):
+        return
+    from adm_amd.metrics import evaluate
+    evaluate.check_startup(sc.get("inception_weights"), "train_uncond_dpm.py (sampler.test_in_train)")
+    for key in ("target_path", "save_folder", "sample_num", "batch_size"):
+        if not sc.get(key):
+            raise ValueError(f"sampler.test_in_train needs sampler.{key}")
+    if not os.path.exists(sc["target_path"]):
+        raise FileNotFoundError(f"sampler.test_in_train: sampler.target_path {sc['target_path']!r} does not exist")
 
 
 def build_model(model_cfg):
@@ -302,6 +360,7 @@ def build_model(model_cfg):
 def main(args):
     cfg = Cfg(args.cfg)
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    check_test_in_train(cfg)
     local = int(os.environ.get("ADM_LOCAL_DEVICE", os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
@@ -319,6 +378,7 @@ def main(args):
     stream = ImageStream(cfg.data, global_batch // world, tuple(cfg.data.get("image_size") or model_cfg.image_size), device,
                          seed=1000 + rank)
     trainer = Trainer(dpm, stream, cfg, device, rank, world)
+    trainer.test_in_train = bool((cfg.get("sampler") or {}).get("test_in_train", False))
     if cfg.trainer.get("test_before", False) and rank == 0:
         dpm.eval()
         save_grid(dpm.sample(batch_size=16), os.path.join(cfg.trainer.results_folder, "sample-0.png"), 4)
