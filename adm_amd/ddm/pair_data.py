@@ -25,32 +25,13 @@ import torch
 
 from .. import hip
 from ..hip import call, ptr
-from .sr_data import PoolStream, _draw, resample_table
+from .sr_data import PoolStream, _draw, pack_bytes, resample_table
 
-LDS_BUDGET = 64 * 1024          # kLdsBudget of adm_amd/csrc/pair_data.hip
+LDS_BUDGET = 64 * 1024          # kLdsBudget of adm_amd/csrc/resample_u8.h
 DUTS_CLASSES = ("ddm.data.DUTSDataset", "DUTSDataset")
 SPLIT_DIRS = {"train": "DUTS-TR", "test": "DUTS-TE"}          # data.py:964-967
 SKETCH_CLASSES = ("ddm.data.SketchDataset", "SketchDataset")
 SKETCH_SPLIT_DIRS = {"train": "train", "test": "val"}         # data.py:1039-1042
-
-
-def pack_bytes(images: Sequence[np.ndarray], channels: int, what: str):
-    """``sr_data.pack_pool``'s layout for planes of ``channels`` bytes per pixel (3: uint8 [H,W,3], 1: uint8 [H,W]) without its
-    crop-size check: (bytes uint8 padded to a multiple of 4, byte offsets int64 [N], sizes int32 [N, 2])."""
-    if len(images) == 0:
-        raise ValueError(f"the {what} pool is empty")
-    shape = "[H, W, 3]" if channels == 3 else "[H, W]"
-    off, hw, total = [], [], 0
-    for i, a in enumerate(images):
-        if a.dtype != np.uint8 or a.ndim != (3 if channels == 3 else 2) or (channels == 3 and a.shape[2] != 3) or a.size == 0:
-            raise ValueError(f"{what} {i}: expected a non-empty uint8 {shape}, got {a.dtype} {a.shape}")
-        off.append(total)
-        hw.append((a.shape[0], a.shape[1]))
-        total += a.size
-    flat = np.zeros((total + 3) // 4 * 4, dtype=np.uint8)
-    for a, o in zip(images, off):
-        flat[o:o + a.size] = a.reshape(-1)
-    return flat, np.asarray(off, dtype=np.int64), np.asarray(hw, dtype=np.int32)
 
 
 def build_table_pool(rgb_hw, gray_hw, out_hw) -> Dict[str, np.ndarray]:

@@ -90,18 +90,16 @@ def resample_table(in_size: int, out_size: int, filter: str = "bicubic") -> Tupl
     return bounds, coeffs
 
 
-def pack_pool(images: Sequence[np.ndarray], crop_hw: Tuple[int, int]):
-    """Host half of the pool: uint8 HWC images (sizes may differ) -> (bytes uint8 [n] padded to a multiple of 4, byte offsets int64
-    [N], sizes int32 [N, 2]).  An image smaller than the crop raises, as T.RandomCrop would (data.py:627)."""
-    H, W = int(crop_hw[0]), int(crop_hw[1])
+def pack_bytes(images: Sequence[np.ndarray], channels: int, what: str):
+    """The packing of every uint8 pool, for planes of ``channels`` bytes per pixel (3: uint8 [H,W,3], 1: uint8 [H,W]; sizes may
+    differ): (bytes uint8 padded to a multiple of 4, byte offsets int64 [N], sizes int32 [N, 2])."""
     if len(images) == 0:
-        raise ValueError("the image pool is empty")
+        raise ValueError(f"the {what} pool is empty")
+    shape = "[H, W, 3]" if channels == 3 else "[H, W]"
     off, hw, total = [], [], 0
     for i, a in enumerate(images):
-        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-            raise ValueError(f"image {i}: expected uint8 [H, W, 3], got {a.dtype} {a.shape}")
-        if a.shape[0] < H or a.shape[1] < W:
-            raise ValueError(f"image {i} is {a.shape[0]}x{a.shape[1]}, smaller than the {H}x{W} crop")
+        if a.dtype != np.uint8 or a.ndim != (3 if channels == 3 else 2) or (channels == 3 and a.shape[2] != 3) or a.size == 0:
+            raise ValueError(f"{what} {i}: expected a non-empty uint8 {shape}, got {a.dtype} {a.shape}")
         off.append(total)
         hw.append((a.shape[0], a.shape[1]))
         total += a.size
@@ -109,6 +107,17 @@ def pack_pool(images: Sequence[np.ndarray], crop_hw: Tuple[int, int]):
     for a, o in zip(images, off):
         flat[o:o + a.size] = a.reshape(-1)
     return flat, np.asarray(off, dtype=np.int64), np.asarray(hw, dtype=np.int32)
+
+
+def pack_pool(images: Sequence[np.ndarray], crop_hw: Tuple[int, int]):
+    """Host half of the SR pool: ``pack_bytes`` of uint8 HWC images.  An image smaller than the crop raises, as T.RandomCrop would
+    (data.py:627)."""
+    H, W = int(crop_hw[0]), int(crop_hw[1])
+    flat, off, hw = pack_bytes(images, 3, "image")
+    for i, (h, w) in enumerate(hw.tolist()):
+        if h < H or w < W:
+            raise ValueError(f"image {i} is {h}x{w}, smaller than the {H}x{W} crop")
+    return flat, off, hw
 
 
 def load_image_folder(folder: str, exts=("png", "jpg")) -> Tuple[List[np.ndarray], List[str]]:

@@ -530,7 +530,8 @@ int adm_augment_geometric(const float* images, const int* flips, const int* marg
  *   hbounds [w][2] / vbounds [h][2] = {window start, window length} in crop coordinates; hcoef [w][kh] / vcoef [h][kv] = int32
  *   coefficients with 22 fractional bits, kh / kv = the longest window (adm_amd/ddm/sr_data.py resample_table).
  * A workgroup makes an ADM_SR_TILE_H x ADM_SR_TILE_W tile of `cond` from LDS; ADM_EINVAL, without launching, when the tile's
- * source rectangle (sized from H/h, W/w, kh, kv) needs more than 64 KiB of LDS.  adm_sr_tile(0 / 1) = the tile's rows / columns. */
+ * source rectangle (sized from H/h, W/w, kh, kv) needs more than 64 KiB of LDS.  adm_sr_tile(0 / 1) = the tile's rows / columns.
+ * The resize itself, shared with adm_pair_resize_batch, is adm_amd/csrc/resample_u8.h. */
 #define ADM_SR_TILE_H 16
 #define ADM_SR_TILE_W 16
 int adm_sr_tile(int axis);

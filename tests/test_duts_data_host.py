@@ -144,6 +144,21 @@ def test_an_image_beyond_the_supported_ratio_is_refused_by_name():
         PairPool.from_arrays([tall, wide], [tall[:, :, 0], wide[:, :, 0]], out, CPU, ["tall", "wide"])
 
 
+def test_lds_sizing_is_what_it_was_before_the_resampler_was_shared():
+    """adm_pair_resize_lds(H, W, max_h, max_w, kh, kv) as the library returned it when pair_data.hip still sized its LDS itself:
+    the shapes of the test above, and the 384x384 recipe from 420x420 and 400x300 sources."""
+    from adm_amd import hip
+    from adm_amd.ddm.pair_data import lds_need, taps
+    was = {(40, 56, 160, 224, 9, 9): 19632, (40, 56, 280, 392, 15, 15): 52256, (40, 56, 320, 448, 17, 17): 66760,
+           (40, 56, 280, 56, 3, 15): 14220, (40, 56, 40, 728, 27, 3): 15600, (40, 56, 280, 728, 27, 15): 89808,
+           (40, 56, 360, 504, 19, 19): 82412, (24, 40, 216, 360, 19, 19): 82412, (384, 384, 420, 420, 5, 5): 3400,
+           (384, 384, 400, 300, 3, 5): 2712}
+    for (H, W, max_h, max_w, kh, kv), want in was.items():
+        assert (taps(max_w, W), taps(max_h, H)) == (kh, kv)
+        assert hip.lib().adm_pair_resize_lds(H, W, max_h, max_w, kh, kv) == want == lds_need((H, W), max_h, max_w), (H, W, max_h, max_w)
+    assert hip.lib().adm_pair_resize_lds(40, 56, 160, 224, 0, 9) == -22
+
+
 def test_batch_stream_dispatch(tmp_path):
     from adm_amd.ddm.pair_data import DUTSBatchStream
     from adm_amd.ddm.sr_data import SRBatchStream

@@ -120,6 +120,30 @@ def test_fresh_data_at_the_recipe_shape(gpu, recipe):
     check(pair_batch(pool, idx, flip, want_u8=True), want_rgb, want_gray)
 
 
+@pytest.mark.parametrize("size,out", [((32, 48), (8, 12)), ((72, 104), (18, 26))])
+def test_both_entry_points_are_one_resampler(gpu, size, out):
+    """One photo through adm_sr_batch (the crop is the whole image, bilinear) and as the photo of a one-pair pool through
+    adm_pair_resize_batch, unflipped and flipped: the same bytes and the same floats, and they are the reference's.  32x48 -> 8x12 is
+    the `bilinear` image of tests/golden/g21_sr_data.npz (one tile); 72x104 -> 18x26 crosses tile boundaries in both directions."""
+    from adm_amd.ddm.pair_data import PairPool, pair_batch
+    from adm_amd.ddm.sr_data import ImagePool, Resampler, sr_batch
+    if size == (32, 48):
+        sr = np.load(os.path.join(os.path.dirname(GOLDEN), "g21_sr_data.npz"))
+        photo, want = sr["bilinear.in"], sr["bilinear.cond"]
+        assert str(sr["bilinear.kind"]) == "bilinear" and photo.shape == size + (3,) and want.shape == out + (3,)
+    else:
+        photo = R.hash_bytes(size + (3,), "duts.one_resampler")
+        want = R.resize_rgb(photo, out)
+    _, cond, cond_u8 = sr_batch(ImagePool.from_arrays([photo], size, gpu), Resampler(size, out, "bilinear", gpu), [0, 0], [0, 0], [0, 0],
+                                [0, 1], want_u8=True)
+    pairs = PairPool.from_arrays([photo], [R.hash_bytes(size, "duts.one_resampler.map")], out, gpu)
+    rgb, _, rgb_u8, _ = pair_batch(pairs, [0, 0], [0, 1], want_u8=True)
+    assert cond_u8.dtype == rgb_u8.dtype == torch.uint8 and cond.dtype == rgb.dtype == torch.float32
+    assert torch.equal(cond_u8, rgb_u8) and torch.equal(cond, rgb)
+    want = torch.from_numpy(np.ascontiguousarray(want))
+    assert torch.equal(rgb_u8[0].cpu(), want) and torch.equal(rgb_u8[1].cpu(), want.flip(1))
+
+
 def write_tree(root, split_dir, src, tag):
     """png photos under a .jpg name would not decode as the reference's do; real jpgs are lossy, so the tree is READ BACK for the
     expected bytes."""
