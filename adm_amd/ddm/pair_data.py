@@ -34,15 +34,11 @@ SKETCH_CLASSES = ("ddm.data.SketchDataset", "SketchDataset")
 SKETCH_SPLIT_DIRS = {"train": "train", "test": "val"}         # data.py:1039-1042
 
 
-def build_table_pool(rgb_hw, gray_hw, out_hw) -> Dict[str, np.ndarray]:
-    """The table pool of resizing every source size in ``rgb_hw`` / ``gray_hw`` ([N, 2] = (height, width)) to ``out_hw``:
-    ``tab`` int32 (table t = bounds [out][2] then coefficients [out][k], flattened), ``dir`` int32 [T, 2] = {offset, k},
-    ``img_tab`` int32 [N, 4] = ids of {photo width, photo height, map width, map height}, and ``keys`` = [(in, out)] per table.
-    Equal (in, out) pairs share one table, whichever axis or plane they come from."""
-    H, W = int(out_hw[0]), int(out_hw[1])
-    rgb_hw, gray_hw = np.asarray(rgb_hw).reshape(-1, 2), np.asarray(gray_hw).reshape(-1, 2)
-    if rgb_hw.shape != gray_hw.shape:
-        raise ValueError(f"{rgb_hw.shape[0]} photos but {gray_hw.shape[0]} maps")
+def table_pool(axes) -> Dict[str, np.ndarray]:
+    """The table pool of ``axes`` = [N][A] pairs (in_size, out_size), the 1-D resizes of each of N images: ``tab`` int32 (table t =
+    bounds [out][2] then coefficients [out][k], flattened), ``dir`` int32 [T, 2] = {offset, k}, ``img_tab`` int32 [N, A] = the table id
+    of every pair, and ``keys`` = [(in, out)] per table.  Equal pairs share one table, whichever axis, plane or image they come
+    from; ids are given in the order of first use."""
     ids: Dict[Tuple[int, int], int] = {}
     parts, directory, total = [], [], 0
 
@@ -57,10 +53,19 @@ def build_table_pool(rgb_hw, gray_hw, out_hw) -> Dict[str, np.ndarray]:
             total += bounds.size + coeffs.size
         return ids[key]
 
-    img_tab = np.asarray([[table(r[1], W), table(r[0], H), table(g[1], W), table(g[0], H)] for r, g in zip(rgb_hw, gray_hw)],
-                         dtype=np.int32).reshape(-1, 4)
+    img_tab = np.asarray([[table(i, o) for i, o in row] for row in axes], dtype=np.int32)
     return {"tab": np.concatenate(parts).astype(np.int32), "dir": np.asarray(directory, dtype=np.int32).reshape(-1, 2),
-            "img_tab": img_tab, "keys": list(ids)}
+            "img_tab": img_tab.reshape(len(axes), -1), "keys": list(ids)}
+
+
+def build_table_pool(rgb_hw, gray_hw, out_hw) -> Dict[str, np.ndarray]:
+    """The ``table_pool`` of resizing every source size in ``rgb_hw`` / ``gray_hw`` ([N, 2] = (height, width)) to ``out_hw``:
+    ``img_tab`` int32 [N, 4] = ids of {photo width, photo height, map width, map height}."""
+    H, W = int(out_hw[0]), int(out_hw[1])
+    rgb_hw, gray_hw = np.asarray(rgb_hw).reshape(-1, 2), np.asarray(gray_hw).reshape(-1, 2)
+    if rgb_hw.shape != gray_hw.shape:
+        raise ValueError(f"{rgb_hw.shape[0]} photos but {gray_hw.shape[0]} maps")
+    return table_pool([[(r[1], W), (r[0], H), (g[1], W), (g[0], H)] for r, g in zip(rgb_hw.tolist(), gray_hw.tolist())])
 
 
 def read_table(pool: Dict[str, np.ndarray], t: int, out_size: int):
@@ -81,25 +86,35 @@ def lds_need(out_hw, max_h: int, max_w: int) -> int:
     return int(hip.lib().adm_pair_resize_lds(H, W, int(max_h), int(max_w), taps(max_w, W), taps(max_h, H)))
 
 
-def check_budget(rgb_hw, gray_hw, out_hw, names: Optional[Sequence[str]] = None) -> Tuple[int, int]:
-    """Refuse, by name, a pair whose source-to-target ratio needs more LDS than a workgroup has; returns (max_h, max_w)."""
+def check_sizes(sizes, out_hw, label, what) -> Tuple[int, int]:
+    """The budget rule of every pool of ragged sources: refuse a source ``sizes[i]`` = (height, width) whose ratio to the target
+    needs more LDS than a workgroup has, and a tallest and a widest source that fit one by one but not together (the capacity is
+    sized once, from both).  ``label(i)`` names entry i, ``what(i)`` says what it is ('its photo is', 'it is').  Returns
+    (max_h, max_w)."""
     H, W = int(out_hw[0]), int(out_hw[1])
-    label = (lambda i: f"pair {i} ({names[i]})") if names else (lambda i: f"pair {i}")
-    sizes = np.concatenate([np.asarray(rgb_hw).reshape(-1, 2), np.asarray(gray_hw).reshape(-1, 2)])
-    n, need = len(sizes) // 2, {}
+    sizes = np.asarray(sizes).reshape(-1, 2)
+    need = {}
     for i, (h, w) in enumerate(sizes.tolist()):
         if (h, w) not in need:
             need[(h, w)] = lds_need(out_hw, h, w)
         if need[(h, w)] > LDS_BUDGET:
-            raise ValueError(f"{label(i % n)}: its {'photo' if i < n else 'map'} is {h}x{w}, {h / H:.2f} x {w / W:.2f} times the "
+            raise ValueError(f"{label(i)}: {what(i)} {h}x{w}, {h / H:.2f} x {w / W:.2f} times the "
                              f"{H}x{W} target; its tile needs {need[(h, w)]} bytes of LDS, the budget is {LDS_BUDGET} (ratios up to "
                              "about 7 per axis fit)")
     max_h, max_w = int(sizes[:, 0].max()), int(sizes[:, 1].max())
-    if lds_need(out_hw, max_h, max_w) > LDS_BUDGET:          # the capacity is sized once, from the tallest and the widest source
-        ih, iw = int(sizes[:, 0].argmax()) % n, int(sizes[:, 1].argmax()) % n
+    if lds_need(out_hw, max_h, max_w) > LDS_BUDGET:
+        ih, iw = int(sizes[:, 0].argmax()), int(sizes[:, 1].argmax())
         raise ValueError(f"{label(ih)} ({max_h} rows) and {label(iw)} ({max_w} columns) together need "
                          f"{lds_need(out_hw, max_h, max_w)} bytes of LDS for the {H}x{W} target, the budget is {LDS_BUDGET}")
     return max_h, max_w
+
+
+def check_budget(rgb_hw, gray_hw, out_hw, names: Optional[Sequence[str]] = None) -> Tuple[int, int]:
+    """Refuse, by name, a pair whose source-to-target ratio needs more LDS than a workgroup has; returns (max_h, max_w)."""
+    sizes = np.concatenate([np.asarray(rgb_hw).reshape(-1, 2), np.asarray(gray_hw).reshape(-1, 2)])
+    n = len(sizes) // 2
+    label = (lambda i: f"pair {i % n} ({names[i % n]})") if names else (lambda i: f"pair {i % n}")
+    return check_sizes(sizes, out_hw, label, lambda i: f"its {'photo' if i < n else 'map'} is")
 
 
 class PairPool:

@@ -193,6 +193,7 @@ _SIGS = {
     "adm_inpaint_compose": [P, P, P, P, I, I, L, P],
     "adm_pair_resize_lds": [I, I, I, I, I, I],
     "adm_pair_resize_batch": [P, L, P, P, P, L, P, P, I, P, L, P, I, P, I, I, I, I, P, P, P, P, P, P, I, I, I, P],
+    "adm_image_resize_batch": [P, L, P, P, I, I, P, L, P, I, P, I, I, I, I, P, P, P, P, I, I, I, P],
     "adm_conv_rect_relu_fwd": [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P],
     "adm_pool3x3_fwd": [P, P, I, I, I, I, I, I, I, I, P],
     "adm_global_avgpool_fwd": [P, P, I, I, I, I, I, P],

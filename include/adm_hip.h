@@ -561,6 +561,23 @@ int adm_pair_resize_batch(const uint8_t* rgb_pool, long rgb_bytes, const int64_t
                           int max_w, int kh, int kv, const int* idx, const int* flip, float* rgb, float* gray, uint8_t* rgb_u8,
                           uint8_t* gray_u8, int B, int H, int W, hipStream_t stream);
 
+/* ---------------- first-stage images (ddm/data.py:167-185, ImageDataset.__getitem__; the map of DUTSDataset, the photo of
+ * SketchDataset) ----------------
+ * The one-plane sibling of adm_pair_resize_batch: one launch makes a batch from ONE uint8 pool of images with C = 3 (HWC) or C = 1
+ * bytes per pixel (adm_sr_batch's layout: packed, 4-byte aligned, a multiple of 4 bytes).  Sample b is image n = idx[b] (clamped
+ * to [0, n_images)): `out` [B][C][H][W] = (u8 / 255) * 2 - 1 of the hw[2n] x hw[2n+1] image at byte off[n] resized to H x W with
+ * PIL's 8-bit two-pass arithmetic, `out_u8` [B][H][W][C] (may be NULL) = the resized bytes.  flip[b] != 0 mirrors the columns of
+ * both outputs, after the resize.
+ *   tab / tab_dir: the table pool of adm_pair_resize_batch; img_tab [n_images][2] = table of the image's width -> W, of its
+ *   height -> H.  max_h / max_w / kh / kv size the LDS rectangle as there (adm_pair_resize_lds).
+ * ADM_EINVAL, without launching: a null pointer (out_u8 excepted), a pool that is not dword-aligned or not a multiple of 4 bytes,
+ * C not 1 or 3, B > 65535, more than 65535 rows of tiles, more than 64 KiB of LDS.
+ * A table or an image that lies about its size gives wrong pixels, never an access outside the pools. */
+int adm_image_resize_batch(const uint8_t* pool, long pool_bytes, const int64_t* off, const int* hw, int n_images, int C,
+                           const int* tab, long tab_ints, const int* tab_dir, int n_tables, const int* img_tab, int max_h,
+                           int max_w, int kh, int kv, const int* idx, const int* flip, float* out, uint8_t* out_u8, int B, int H,
+                           int W, hipStream_t stream);
+
 /* ---------------- in-painting batches (ddm/data.py:384-476, InpaintDataset.__getitem__ / random_mask / RandomBrush) ----------------
  * A mask is hole = 0 / keep = 1 on integer pixel coordinates of an S x S image, defined in integers: a pixel is a
  * hole when a clipped rectangle, a stroke segment (butt-ended band: 0 <= dot <= L2 and 4 cross^2 <= w^2 L2, int64) or a stroke

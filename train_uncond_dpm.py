@@ -90,7 +90,8 @@ class ImageStream:
 
     Sources, in this order: ``data.npy`` (uint8 [N,H,W,3]; must exist and match ``image_size``); ``data.class_name:
     ddm.data.CIFAR10`` + ``img_folder`` (the reference YAML, /root/reference/configs/cifar10/*.yaml); ``data.class_name:
-    synthetic`` = U(-1,1) images.  Anything else raises: a config that names a real dataset never trains on noise silently."""
+    synthetic`` = U(-1,1) images.  Anything else raises: a config that names a real dataset never trains on noise silently.
+    (``ddm.data.ImageDataset`` is served by ``adm_amd.ddm.image_data.ImageFolderStream``: see ``image_stream``.)"""
 
     def __init__(self, data_cfg, batch, image_size, device, seed):
         self.batch, self.size, self.device = batch, tuple(image_size), device
@@ -128,6 +129,16 @@ class ImageStream:
             return {"image": x}
         flip = torch.rand(self.batch, device=self.device, generator=self.gen) < 0.5
         return {"image": torch.where(flip[:, None, None, None], x.flip(-1), x)}
+
+
+def image_stream(data_cfg, batch, image_size, device, seed):
+    """The batch source of the unconditional drivers: ``data.class_name: ddm.data.ImageDataset`` (+ ``img_folder``; or ``synthetic``
+    with ``synthetic_of`` naming it) selects ``ImageFolderStream``, whose batches are resized on the device; everything else goes
+    to ``ImageStream``."""
+    from adm_amd.ddm.image_data import ImageFolderStream, stream_class
+    if stream_class(data_cfg) is ImageFolderStream:
+        return ImageFolderStream(data_cfg, batch, image_size, device, seed)
+    return ImageStream(data_cfg, batch, image_size, device, seed)
 
 
 def save_grid(img, path, nrow):
@@ -375,8 +386,8 @@ def main(args):
     dpm = build_model(model_cfg).to(device).train()
     global_batch = int(cfg.data.batch_size)
     assert global_batch % world == 0, "split_batches: the YAML batch_size is the global batch"
-    stream = ImageStream(cfg.data, global_batch // world, tuple(cfg.data.get("image_size") or model_cfg.image_size), device,
-                         seed=1000 + rank)
+    stream = image_stream(cfg.data, global_batch // world, tuple(cfg.data.get("image_size") or model_cfg.image_size), device,
+                          seed=1000 + rank)
     trainer = Trainer(dpm, stream, cfg, device, rank, world)
     trainer.test_in_train = bool((cfg.get("sampler") or {}).get("test_in_train", False))
     if cfg.trainer.get("test_before", False) and rank == 0:

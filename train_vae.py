@@ -18,8 +18,10 @@ data, trainer); the recipe it reproduces:
 
 What differs: single process (data-parallel first-stage training is not implemented); the optimisers are torch.optim.AdamW on
 ordinary parameters, not the fused flat-buffer optimiser; AutoencoderKL.training_step runs its own backward (see
-adm_amd/ddm/loss.py), so the loop calls no .backward().  Data comes from train_uncond_dpm.ImageStream: ``data.npy`` (uint8
-[N,H,W,3]) or ``data.class_name: synthetic``.  LPIPS weights are not shipped: ``model.lossconfig.lpips_ckpt`` or a checkpoint
+adm_amd/ddm/loss.py), so the loop calls no .backward().  Data comes from ``first_stage_stream``: the recipe's own dataset
+(``ddm.data.ImageDataset``, the maps of ``ddm.data.DUTSDataset``, the photos of ``ddm.data.SketchDataset``, the HR crops of
+``ddm.data.SRDataset``; three or ONE channel), or train_uncond_dpm.ImageStream: ``data.npy`` (uint8 [N,H,W,3]) or
+``data.class_name: synthetic``.  LPIPS weights are not shipped: ``model.lossconfig.lpips_ckpt`` or a checkpoint
 with ``loss.perceptual_loss.*`` keys provides them; without them the perceptual term is zero (a warning says so).
 """
 import argparse
@@ -60,6 +62,45 @@ def ema_action(ema_step: int, initted: bool, update_every: int = 10, update_afte
     if not initted:          # the first update after the warm-up copies, then averages: the copy makes the average a no-op
         return 0.0, True
     return ema_decay_at(ema_step + 1, beta=beta, update_after_step=update_after_step), True
+
+
+SR_CLASSES = ("ddm.data.SRDataset", "SRDataset")
+
+
+def first_stage_stream(data_cfg, batch, size, device, seed):
+    """The batch source of a first stage, by ``data.class_name`` (or ``synthetic_of`` under ``class_name: synthetic``):
+    ``ddm.data.ImageDataset`` / ``ddm.data.DUTSDataset`` (its maps, one channel) / ``ddm.data.SketchDataset`` (its photos) select the
+    one-plane streams of adm_amd/ddm/image_data.py; ``ddm.data.SRDataset`` selects ``SRBatchStream``, whose ``image`` -- the HR
+    crop -- is what the DIV2K first stage trains on (data.py:645-658); everything else goes to ``ImageStream``, which refuses what
+    it does not build.  The stream carries ``channels``."""
+    from adm_amd.ddm.image_data import stream_class
+    from adm_amd.ddm.sr_data import SRBatchStream
+    data_cfg = data_cfg or {}
+    cls = data_cfg.get("class_name")
+    picked = stream_class(data_cfg)
+    if picked is not None:
+        return picked(data_cfg, batch, size, device, seed)
+    if cls == "synthetic" and data_cfg.get("synthetic_of") is not None and data_cfg.get("synthetic_of") not in SR_CLASSES:
+        raise NotImplementedError(f"data.synthetic_of {data_cfg.get('synthetic_of')!r}: a synthetic first-stage pool is built for "
+                                  "ddm.data.ImageDataset, ddm.data.DUTSDataset, ddm.data.SketchDataset and ddm.data.SRDataset")
+    if cls in SR_CLASSES or (cls == "synthetic" and data_cfg.get("synthetic_of") in SR_CLASSES):
+        stream = SRBatchStream(data_cfg, batch, size, device, seed)
+    else:
+        stream = ImageStream(data_cfg, batch, size, device, seed)
+    stream.channels = 3
+    return stream
+
+
+def check_channels(stream_channels: int, model_cfg):
+    """Start-up checks: the stream's channel count against ``ddconfig.in_channels``, and ``lossconfig.disc_in_channels`` against
+    ``ddconfig.out_ch`` (the discriminator sees the reconstruction)."""
+    dd, lc = model_cfg.get("ddconfig") or {}, model_cfg.get("lossconfig") or {}
+    in_ch, out_ch, disc = int(dd.get("in_channels", 3)), int(dd.get("out_ch", 3)), int(lc.get("disc_in_channels", 3))
+    if int(stream_channels) != in_ch:
+        raise ValueError(f"the data stream yields {int(stream_channels)}-channel images but model.ddconfig.in_channels is {in_ch}")
+    if disc != out_ch:
+        raise ValueError(f"model.lossconfig.disc_in_channels is {disc} but model.ddconfig.out_ch is {out_ch}: the discriminator "
+                         "judges the reconstruction")
 
 
 def parse_args():
@@ -192,11 +233,12 @@ def main(args):
     local = int(os.environ.get("ADM_LOCAL_DEVICE", os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
+    size = tuple(cfg.data.get("image_size") or cfg.model.ddconfig.resolution)
+    stream = first_stage_stream(cfg.data, int(cfg.data.batch_size), size, device, seed=1000)
+    check_channels(stream.channels, cfg.model)
     model = construct_class_by_name(**{k: v for k, v in cfg.model.items()}).to(device)
     model.enable_training()
     model.train()
-    size = tuple(cfg.data.get("image_size") or cfg.model.ddconfig.resolution)
-    stream = ImageStream(cfg.data, int(cfg.data.batch_size), size, device, seed=1000)
     trainer = Trainer(model, stream, cfg, device, resume=args.resume)
     trainer.train(args.max_steps)
 
