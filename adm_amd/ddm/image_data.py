@@ -224,15 +224,10 @@ class SketchPhotoStream(ImageBatchStream):
     paths = staticmethod(lambda cfg: [p for p, _ in find_sketch_pairs(cfg.get("data_root"), cfg.get("split") or "train")])
 
 
-STREAMS = (ImageFolderStream, DUTSMapStream, SketchPhotoStream)
-
-
 def stream_class(data_cfg):
-    """The stream that serves ``data_cfg`` (its ``class_name``, or its ``synthetic_of`` under ``class_name: synthetic``), or None."""
-    data_cfg = data_cfg or {}
-    cls = data_cfg.get("class_name")
-    name = data_cfg.get("synthetic_of") if cls == "synthetic" else cls
-    for s in STREAMS:
-        if name in s.CLASSES:
-            return s
-    return None
+    """The stream of this module that serves ``data_cfg`` (its ``class_name``, or its ``synthetic_of`` under ``class_name:
+    synthetic``), or None: the ``first_stage`` column of ``datasets.DATASETS``, where it is one of the one-plane streams."""
+    from .datasets import DATASETS, dataset_of          # (the table imports this module's classes)
+    key = dataset_of(data_cfg)
+    picked = DATASETS[key].first_stage if key else None
+    return picked if picked is not None and issubclass(picked, ImageBatchStream) else None

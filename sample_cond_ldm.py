@@ -33,10 +33,13 @@ With ``data.class_name: ddm.data.SketchDataset`` and ``split: test`` (sketch-to-
 configs/sketch2img/sketchcoco_cond_ddm_const_ldm_sample.yaml) the condition is the ONE-channel sketch resized to ``image_size`` and the
 output a three-channel image, sampled in one window and written under the sketch's file name.  No PSNR is printed: a generated
 photo has no ground truth to score.
+
+Which of these a data section selects, and what differs between them, is the ``sampling`` column of adm_amd.ddm.datasets.DATASETS;
+``main`` is one loop over that entry.  ``class_name: synthetic`` + ``synthetic_of`` selects the sketch entry only: with any other
+``synthetic_of`` the items are CondStream's super-resolution pairs.
 """
 import argparse
 import importlib
-import math
 import os
 import sys
 import time
@@ -47,6 +50,7 @@ import yaml
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+from adm_amd.ddm.datasets import DATASETS, SR_SAMPLING, sampling_dataset  # noqa: E402
 from train_uncond_dpm import Cfg, build_model  # noqa: E402
 from sample_uncond import load_weights  # noqa: E402
 
@@ -188,78 +192,34 @@ class CondStream:
             yield {"image": pad, "cond": torch.nn.functional.avg_pool2d(pad, 4), "ori_size": (H, W), "img_name": f"{i: 010d}.png"}
 
 
-INPAINT_CLASSES = ("ddm.data.InpaintDataset", "InpaintDataset")
+class DatasetCondStream:
+    """The test items of an entry of adm_amd.ddm.datasets.DATASETS that has a ``sampling`` column (in-painting, saliency,
+    sketch-to-image), keyed as CondStream's: image or pair i of the pool in order, made one at a time by the kernel that makes the
+    training batches (``cond_stream`` with injected draws), never flipped.  The entry says whether ``split: test`` is required,
+    and how 'ori_size' and 'img_name' read (``item``); an item without a file name is numbered."""
 
-
-class InpaintCondStream:
-    """``data.class_name: ddm.data.InpaintDataset`` at sampling time (``split: test`` of ``img_folder``, or ``data.npy``): image i of
-    the pool with a mask drawn for it on the device, as the reference's test set draws one per item (ddm/data.py:395); the test
-    transform has no flip (:377-379).  Items are keyed as CondStream's."""
-
-    def __init__(self, data_cfg, n, image_size, device, seed):
-        from adm_amd.ddm.inpaint_data import InpaintBatchStream
-        self.n = n
-        self.stream = InpaintBatchStream(dict(data_cfg, augment_horizontal_flip=False), 1, image_size, device, seed)
+    def __init__(self, entry, data_cfg, n, image_size, device, seed):
+        sm = entry.sampling
+        if sm.split_test and (data_cfg.get("split") or "train") != "test":
+            raise ValueError(sm.split_test)
+        if sm.no_flip:          # the reference's test transform has no flip (ddm/data.py:377-379)
+            data_cfg = dict(data_cfg, augment_horizontal_flip=False)
+        self.n, self.item = n, sm.item
+        self.stream = entry.cond_stream(data_cfg, 1, image_size, device, seed)
 
     def __iter__(self):
         s = self.stream
         for i in range(self.n):
             k = i % s.pool.n
             batch = s.next_batch(idx=[k], flip=[0])
-            batch["ori_size"] = (s.size, s.size)
-            batch["img_name"] = s.names[k][:-4] + ".png" if s.names else f"{i: 010d}.png"          # reference :217: the name, as png
+            batch["ori_size"], name = self.item(s, k, batch)
+            batch["img_name"] = name or f"{i: 010d}.png"
             yield batch
 
 
-DUTS_CLASSES = ("ddm.data.DUTSDataset", "DUTSDataset")
-
-
-class DUTSCondStream:
-    """``data.class_name: ddm.data.DUTSDataset`` with ``split: test`` (``DUTS-TE`` below ``data_root``): pair i in sorted order, photo and
-    map resized to the model's resolution by the kernel that makes the training batches (adm_amd.ddm.pair_data), no flip (ddm/data.py:
-    987-991).  'cond' is the photo, 'image' the map; 'ori_size' is the photo's own size, as the reference records it (:1026)."""
-
-    def __init__(self, data_cfg, n, image_size, device, seed):
-        from adm_amd.ddm.pair_data import DUTSBatchStream
-        if (data_cfg.get("split") or "train") != "test":
-            raise ValueError("sampling ddm.data.DUTSDataset needs data.split: test (DUTS-TE, in order, unflipped)")
-        self.n = n
-        self.stream = DUTSBatchStream(data_cfg, 1, image_size, device, seed)
-
-    def __iter__(self):
-        s = self.stream
-        for i in range(self.n):
-            batch = s.next_batch(idx=[i % s.pool.n], flip=[0])
-            batch["ori_size"] = batch["ori_size"][0]
-            batch["img_name"] = batch["img_name"][0][:-4] + ".png"          # reference :215-216: the photo's name, as png
-            yield batch
-
-
-SKETCH_CLASSES = ("ddm.data.SketchDataset", "SketchDataset")
-
-
-class SketchCondStream:
-    """``data.class_name: ddm.data.SketchDataset`` with ``split: test`` (``GT/val`` and ``Sketch/val`` below ``data_root``; or
-    ``synthetic`` with ``synthetic_of: ddm.data.SketchDataset``, the uniform-draw pool of the training stream): pair i in sorted order, resized by the kernel that makes the training batches, no flip.  'cond' is the sketch [1,1,H,W]."""
-
-    def __init__(self, data_cfg, n, image_size, device, seed):
-        from adm_amd.ddm.pair_data import SketchBatchStream
-        if (data_cfg.get("split") or "train") != "test":
-            raise ValueError("sampling ddm.data.SketchDataset needs data.split: test (GT/val + Sketch/val, in order, unflipped)")
-        self.n = n
-        self.stream = SketchBatchStream(data_cfg, 1, image_size, device, seed)
-
-    def __iter__(self):
-        s = self.stream
-        for i in range(self.n):
-            batch = s.next_batch(idx=[i % s.pool.n], flip=[0])
-            batch["ori_size"] = batch["ori_size"][0]
-            batch["img_name"] = batch["img_name"][0]          # the sketch's file name (= the photo's: same relative path)
-            yield batch
-
-
-def main():
-    ap = argparse.ArgumentParser(description="sliding-window conditional latent sampler (MI355X hot path)")
+def start(description):
+    """The conditional samplers' preamble: (args, cfg, world, rank, device) of the command line, YAML and launcher; seed 42 + rank."""
+    ap = argparse.ArgumentParser(description=description)
     ap.add_argument("--cfg", required=True)
     ap.add_argument("--max-images", type=int, default=None)
     ap.add_argument("--random-init", action="store_true", help="smoke runs: sample without loading a checkpoint")
@@ -270,6 +230,73 @@ def main():
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.manual_seed(42 + rank)
+    return args, cfg, world, rank, device
+
+
+def load_checkpoint(model, s, random_init, device, lost_message, check=True):
+    """Loads ``sampler.ckpt_path`` (EMA weights when ``sampler.use_ema``) unless `random_init`; with `check`, a checkpoint that lacks
+    tensors of the condition encoder is refused with `lost_message` (formatted with path, n, first)."""
+    if s.get("ckpt_path") and not random_init:
+        if not os.path.exists(s.ckpt_path):
+            raise FileNotFoundError(f"sampler.ckpt_path {s.ckpt_path} does not exist (pass --random-init for a smoke run)")
+        missing, _ = load_weights(model, s.ckpt_path, s.get("use_ema", True), device)
+        # (norm.* / head.* of the encoder are holders its forward never reads; an EMA copy holds trained tensors only, so lacks them)
+        lost = [k for k in missing if ".init_conv_mask." in k and ".init_conv_mask.norm." not in k and ".init_conv_mask.head." not in k]
+        if check and lost:
+            raise RuntimeError(lost_message.format(path=s.ckpt_path, n=len(lost), first=lost[0]))
+    elif not random_init:
+        raise ValueError("sampler.ckpt_path is empty (pass --random-init for a smoke run)")
+
+
+def save_prediction(img, folder, img_name, world, index, gray=False):
+    """img [C,H,W] in [0,1] as an 8-bit png (mode L for one channel when `gray`) under the item's own name, or -- several ranks --
+    under its global index; returns the file name."""
+    from PIL import Image
+    arr = (img.clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0).cpu().numpy()
+    name = img_name if world == 1 else f"{index: 010d}.png"
+    Image.fromarray(arr[:, :, 0] if gray and arr.shape[2] == 1 else arr).save(os.path.join(folder, name))
+    return name
+
+
+def window_sampler(ldm, scale):
+    """c [B,C,h,w] -> the sample for the window c, `scale` times its size.  The encoder runs ONCE per window batch (the reference
+    re-runs it inside every denoising step, cond_unet_sd.py:821)."""
+    down = ldm.first_stage_model.down_ratio
+    return lambda c: ldm.sample(cond=list(ldm.model.init_conv_mask(c)), latent_hw=(c.shape[2] * scale // down, c.shape[3] * scale // down))
+
+
+def predict_composite(ldm, s, batch, crop, stride):
+    """In-painting: kept pixels from the masked image, holes from the sample (reference :175-186, ddm_const_2.py:629)."""
+    cond = batch["cond"]
+    return ldm.sample(cond=list(ldm.model.init_conv_mask(cond)), mask=batch["ori_mask"], cond_image=cond).to(torch.float32)
+
+
+def predict_window(ldm, s, batch, crop, stride):
+    """Sketch-to-image: one window, the whole one-channel condition."""
+    cond = batch["cond"]
+    if cond.shape[1] != 1 or int(s.get("out_channels", 3)) != 3:
+        raise ValueError(f"sketch-to-image takes a one-channel condition and makes three channels, got cond {tuple(cond.shape)}, "
+                         f"sampler.out_channels {s.get('out_channels', 3)}")
+    return window_sampler(ldm, 1)(cond).to(torch.float32)
+
+
+def predict_slide(ldm, s, batch, crop, stride, scale=1, out_channels=1, ori_size=None):
+    """Saliency: the reference's slide_sample (:220-283), windows over the condition at the output's own resolution.  With scale 4,
+    three channels and the item's ``ori_size``: super-resolution -- the frame the windows tile is the condition's, x4 (for
+    SRDatasetTest larger than the unpadded image: reference :324-332)."""
+    cond = batch["cond"]
+    return slide_sample_sr(window_sampler(ldm, scale), cond, (cond.shape[-2] * scale, cond.shape[-1] * scale), crop, stride,
+                           out_channels=int(s.get("out_channels", out_channels)), scale=scale, ori_size=ori_size,
+                           window_batch=int(s.get("window_batch", 0)), flip_test=bool(s.get("flip_test", False)))
+
+
+# Sampling.form of adm_amd.ddm.datasets -> (ldm, sampler cfg, item, crop, stride) -> the prediction [1,C,H,W] in [0,1]
+FORMS = {"composite": predict_composite, "window": predict_window, "slide": predict_slide,
+         "slide_x4": lambda ldm, s, batch, crop, stride: predict_slide(ldm, s, batch, crop, stride, 4, 3, batch["ori_size"])}
+
+
+def main():
+    args, cfg, world, rank, device = start("sliding-window conditional latent sampler (MI355X hot path)")
     mc, s = cfg.model, cfg.sampler
     assert mc.get("ldm"), "this driver is for latent models (reference :58)"
     ldm = build_model(mc).to(device).eval()
@@ -284,102 +311,43 @@ def main():
         raise ValueError("sampler.cond_encoder is required: 'swin_b' (the built-in encoder, weights from the checkpoint), "
                          "'module:callable' returning the four condition feature maps, or 'synthetic'")
     ldm.model.init_conv_mask = enc.to(device) if isinstance(enc, torch.nn.Module) else enc
-    if s.get("ckpt_path") and not args.random_init:
-        if not os.path.exists(s.ckpt_path):
-            raise FileNotFoundError(f"sampler.ckpt_path {s.ckpt_path} does not exist (pass --random-init for a smoke run)")
-        missing, _ = load_weights(ldm, s.ckpt_path, s.get("use_ema", True), device)
-        # (norm.* / head.* of the encoder are holders its forward never reads; an EMA copy holds trained tensors only, so lacks them)
-        lost = [k for k in missing if ".init_conv_mask." in k and ".init_conv_mask.norm." not in k and ".init_conv_mask.head." not in k]
-        if builtin and lost:
-            raise RuntimeError(f"sampler.cond_encoder: swin_b, but {s.ckpt_path} lacks {len(lost)} of the encoder's tensors "
-                               f"(first: {lost[0]}): the checkpoint must hold the trained init_conv_mask.* weights")
-    elif not args.random_init:
-        raise ValueError("sampler.ckpt_path is empty (pass --random-init for a smoke run)")
+    load_checkpoint(ldm, s, args.random_init, device, "sampler.cond_encoder: swin_b, but {path} lacks {n} of the encoder's tensors "
+                    "(first: {first}): the checkpoint must hold the trained init_conv_mask.* weights", check=builtin)
     out_dir = s.save_folder
     os.makedirs(out_dir, exist_ok=True)
-    from PIL import Image
     n_total = int(s.sample_num) if args.max_images is None else min(int(s.sample_num), args.max_images)
     per_rank = n_total // world
-    inpaint = cfg.data.get("class_name") in INPAINT_CLASSES
-    duts = cfg.data.get("class_name") in DUTS_CLASSES
-    sketch = cfg.data.get("class_name") in SKETCH_CLASSES or (cfg.data.get("class_name") == "synthetic"
-                                                               and cfg.data.get("synthetic_of") in SKETCH_CLASSES)
-    if inpaint:
-        size = tuple(cfg.data.get("image_size") or mc.image_size)
-        stream = InpaintCondStream(cfg.data, per_rank, size, device, seed=2000 + rank)
-        # the reference's in-painting sample YAML has neither key: one window, the image
-        crop, stride = tuple(s.get("crop_size") or size), tuple(s.get("stride") or size)
-        if crop != size:
-            raise NotImplementedError(f"in-painting samples the whole image in one window: sampler.crop_size {crop} must equal image_size {size}")
-        if bool(s.get("save_masks", False)):
-            os.makedirs(os.path.join(out_dir, "masks"), exist_ok=True)
-    elif duts:
-        size = tuple(cfg.data.get("image_size") or mc.image_size)
-        stream = DUTSCondStream(cfg.data, per_rank, size, device, seed=2000 + rank)
-        # The reference's saliency sample YAML has neither key, and its own driver would fail on them (cfg.sampler.crop_size, :190):
-        # they default to one window, the image at model resolution.
-        crop, stride = tuple(s.get("crop_size") or size), tuple(s.get("stride") or size)
-    elif sketch:
-        size = tuple(cfg.data.get("image_size") or mc.image_size)
-        stream = SketchCondStream(cfg.data, per_rank, size, device, seed=2000 + rank)
-        crop = tuple(s.get("crop_size") or size)
-        if crop != size:
-            raise NotImplementedError(f"sketch-to-image samples the whole image in one window: sampler.crop_size {crop} must equal image_size {size}")
-    else:
+    key = sampling_dataset(cfg.data)
+    if key is None:
+        sm = SR_SAMPLING
         stream = CondStream(cfg.data, per_rank, device, seed=2000 + rank)
         crop, stride = tuple(s.crop_size), tuple(s.stride)
+    else:
+        sm = DATASETS[key].sampling
+        size = tuple(cfg.data.get("image_size") or mc.image_size)
+        stream = DatasetCondStream(DATASETS[key], cfg.data, per_rank, size, device, seed=2000 + rank)
+        # The reference's in-painting and saliency sample YAMLs have neither key, and its own driver would fail on them
+        # (cfg.sampler.crop_size, :190): they default to one window, the image at model resolution.
+        crop = tuple(s.get("crop_size") or size)
+        stride = None if sm.form == "window" else tuple(s.get("stride") or size)
+        if sm.one_window and crop != size:
+            raise NotImplementedError(f"{sm.one_window} samples the whole image in one window: sampler.crop_size {crop} must equal image_size {size}")
+    masks = sm.save_masks and bool(s.get("save_masks", False))
+    if masks:
+        os.makedirs(os.path.join(out_dir, "masks"), exist_ok=True)
     psnr, done, t0 = 0.0, 0, time.time()
     for batch in stream:
-        cond, image = batch["cond"], (batch["image"] + 1) * 0.5
-        down = ldm.first_stage_model.down_ratio
-        if inpaint:          # the composite: kept pixels from the masked image, holes from the sample (reference :175-186, ddm_const_2.py:629)
-            mask = batch["ori_mask"]
-            pred = ldm.sample(cond=list(ldm.model.init_conv_mask(cond)), mask=mask, cond_image=cond).to(torch.float32)
-            psnr += float(-10.0 * torch.log10(torch.mean((pred - image) ** 2)))
-            arr = (pred[0].clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0).cpu().numpy()
-            name = batch["img_name"] if world == 1 else f"{rank * per_rank + done: 010d}.png"
-            Image.fromarray(arr).save(os.path.join(out_dir, name))
-            if bool(s.get("save_masks", False)):
-                Image.fromarray((mask[0, 0] * 255).to(torch.uint8).cpu().numpy()).save(os.path.join(out_dir, "masks", name))
-            done += 1
-            continue
-        if sketch:          # one window; the generated photo has no ground truth, so nothing is scored
-            if cond.shape[1] != 1 or int(s.get("out_channels", 3)) != 3:
-                raise ValueError(f"sketch-to-image takes a one-channel condition and makes three channels, got cond {tuple(cond.shape)}, "
-                                 f"sampler.out_channels {s.get('out_channels', 3)}")
-            pred = ldm.sample(cond=list(ldm.model.init_conv_mask(cond)),
-                              latent_hw=(cond.shape[2] // down, cond.shape[3] // down)).to(torch.float32)
-            arr = (pred[0].clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0).cpu().numpy()
-            name = batch["img_name"] if world == 1 else f"{rank * per_rank + done: 010d}.png"
-            Image.fromarray(arr).save(os.path.join(out_dir, name))
-            done += 1
-            continue
-        if duts:          # the reference's slide_sample (:220-283): windows over the condition at the output's own resolution
-            fn = lambda c: ldm.sample(cond=list(ldm.model.init_conv_mask(c)), latent_hw=(c.shape[2] // down, c.shape[3] // down))
-            pred = slide_sample_sr(fn, cond, tuple(cond.shape[-2:]), crop, stride, out_channels=int(s.get("out_channels", 1)), scale=1,
-                                   window_batch=int(s.get("window_batch", 0)), flip_test=bool(s.get("flip_test", False)))
-            psnr += float(-10.0 * torch.log10(torch.mean((pred - image) ** 2)))          # against the resized map (:195)
-            arr = (pred[0].clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0).cpu().numpy()
-            name = batch["img_name"] if world == 1 else f"{rank * per_rank + done: 010d}.png"
-            Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr).save(os.path.join(out_dir, name))
-            done += 1
-            continue
-        # the encoder runs ONCE per window batch (the reference re-runs it inside every denoising step, cond_unet_sd.py:821)
-        fn = lambda c: ldm.sample(cond=list(ldm.model.init_conv_mask(c)), latent_hw=(c.shape[2] * 4 // down, c.shape[3] * 4 // down))
-        # the frame the windows tile is the condition's, x4 (for SRDatasetTest larger than the unpadded image: reference :324-332)
-        pred = slide_sample_sr(fn, cond, (cond.shape[-2] * 4, cond.shape[-1] * 4), crop, stride,
-                               out_channels=int(s.get("out_channels", 3)), ori_size=batch["ori_size"],
-                               window_batch=int(s.get("window_batch", 0)), flip_test=bool(s.get("flip_test", False)))
-        H, W = batch["ori_size"]
-        mse = torch.mean((pred - image[:, :, :H, :W]) ** 2)
-        psnr += float(-10.0 * torch.log10(mse))
-        arr = (pred[0].clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0).cpu().numpy()
-        name = batch["img_name"] if world == 1 else f"{rank * per_rank + done: 010d}.png"
-        Image.fromarray(arr).save(os.path.join(out_dir, name))
+        pred = FORMS[sm.form](ldm, s, batch, crop, stride)
+        if sm.psnr:          # (reference :195) against the part of 'image' the prediction covers: SRDatasetTest cuts it to ori_size
+            image = (batch["image"] + 1) * 0.5
+            psnr += float(-10.0 * torch.log10(torch.mean((pred - image[:, :, :pred.shape[2], :pred.shape[3]]) ** 2)))
+        name = save_prediction(pred[0], out_dir, batch["img_name"], world, rank * per_rank + done, sm.gray)
+        if masks:
+            save_prediction(batch["ori_mask"][0], os.path.join(out_dir, "masks"), name, 1, 0, gray=True)          # 0 / 1 -> 0 / 255
         done += 1
     torch.cuda.synchronize()
     dt = time.time() - t0
-    score = "" if sketch else f"; PSNR: {psnr / max(done, 1):.2f}"
+    score = f"; PSNR: {psnr / max(done, 1):.2f}" if sm.psnr else ""
     print(f"rank {rank}: {done} images in {dt:.1f}s ({done / max(dt, 1e-9):.2f} images/sec incl. PNG writes){score}")
 
 

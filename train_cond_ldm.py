@@ -29,8 +29,7 @@ import torch
 import torch.distributed as dist
 
 from train_uncond_dpm import Cfg, Trainer, build_model, parse_args, save_grid
-from adm_amd.ddm.inpaint_data import InpaintBatchStream
-from adm_amd.ddm.pair_data import DUTS_CLASSES, SKETCH_CLASSES, DUTSBatchStream, SketchBatchStream
+from adm_amd.ddm.datasets import DATASETS, dataset_of
 from adm_amd.ddm.sr_data import SRBatchStream
 from adm_amd.optim import lr_lambda_cond
 
@@ -39,21 +38,14 @@ def grid_columns(batch):
     return 2 ** math.floor(math.log2(math.sqrt(batch)))          # train_cond_ldm.py:89, 309
 
 
-INPAINT_CLASSES = ("ddm.data.InpaintDataset", "InpaintDataset")
-
-
 def batch_stream(data_cfg, batch, image_size, device, seed):
-    """The batch source ``data.class_name`` names: in-painting triples for ddm.data.InpaintDataset, saliency pairs for
-    ddm.data.DUTSDataset, sketch-to-image pairs for ddm.data.SketchDataset, super-resolution pairs otherwise (SRBatchStream raises for what it does not know).  ``class_name:
-    synthetic`` stands for the dataset ``data.synthetic_of`` names."""
-    cls = data_cfg.get("class_name")
-    if cls in INPAINT_CLASSES or (cls == "synthetic" and data_cfg.get("synthetic_of") in INPAINT_CLASSES):
-        return InpaintBatchStream(data_cfg, batch, image_size, device, seed)
-    if cls in DUTS_CLASSES or (cls == "synthetic" and data_cfg.get("synthetic_of") in DUTS_CLASSES):
-        return DUTSBatchStream(data_cfg, batch, image_size, device, seed)
-    if cls in SKETCH_CLASSES or (cls == "synthetic" and data_cfg.get("synthetic_of") in SKETCH_CLASSES):
-        return SketchBatchStream(data_cfg, batch, image_size, device, seed)
-    return SRBatchStream(data_cfg, batch, image_size, device, seed)
+    """The batch source ``data.class_name`` names (the ``cond_stream`` column of adm_amd.ddm.datasets.DATASETS): in-painting triples
+    for ddm.data.InpaintDataset, saliency pairs for ddm.data.DUTSDataset, sketch-to-image pairs for ddm.data.SketchDataset,
+    super-resolution pairs otherwise (SRBatchStream raises for what it does not know).  ``class_name: synthetic`` stands for the
+    dataset ``data.synthetic_of`` names."""
+    key = dataset_of(data_cfg)
+    picked = (DATASETS[key].cond_stream if key else None) or SRBatchStream
+    return picked(data_cfg, batch, image_size, device, seed)
 
 
 class CondTrainer(Trainer):

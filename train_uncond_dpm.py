@@ -136,9 +136,8 @@ def image_stream(data_cfg, batch, image_size, device, seed):
     with ``synthetic_of`` naming it) selects ``ImageFolderStream``, whose batches are resized on the device; everything else goes
     to ``ImageStream``."""
     from adm_amd.ddm.image_data import ImageFolderStream, stream_class
-    if stream_class(data_cfg) is ImageFolderStream:
-        return ImageFolderStream(data_cfg, batch, image_size, device, seed)
-    return ImageStream(data_cfg, batch, image_size, device, seed)
+    picked = ImageFolderStream if stream_class(data_cfg) is ImageFolderStream else ImageStream
+    return picked(data_cfg, batch, image_size, device, seed)
 
 
 def save_grid(img, path, nrow):

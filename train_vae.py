@@ -64,30 +64,23 @@ def ema_action(ema_step: int, initted: bool, update_every: int = 10, update_afte
     return ema_decay_at(ema_step + 1, beta=beta, update_after_step=update_after_step), True
 
 
-SR_CLASSES = ("ddm.data.SRDataset", "SRDataset")
-
-
 def first_stage_stream(data_cfg, batch, size, device, seed):
-    """The batch source of a first stage, by ``data.class_name`` (or ``synthetic_of`` under ``class_name: synthetic``):
-    ``ddm.data.ImageDataset`` / ``ddm.data.DUTSDataset`` (its maps, one channel) / ``ddm.data.SketchDataset`` (its photos) select the
-    one-plane streams of adm_amd/ddm/image_data.py; ``ddm.data.SRDataset`` selects ``SRBatchStream``, whose ``image`` -- the HR
-    crop -- is what the DIV2K first stage trains on (data.py:645-658); everything else goes to ``ImageStream``, which refuses what
-    it does not build.  The stream carries ``channels``."""
-    from adm_amd.ddm.image_data import stream_class
-    from adm_amd.ddm.sr_data import SRBatchStream
+    """The batch source of a first stage, by ``data.class_name`` (or ``synthetic_of`` under ``class_name: synthetic``): the
+    ``first_stage`` column of adm_amd.ddm.datasets.DATASETS.  ``ddm.data.ImageDataset`` / ``ddm.data.DUTSDataset`` (its maps, one
+    channel) / ``ddm.data.SketchDataset`` (its photos) select the one-plane streams of adm_amd/ddm/image_data.py;
+    ``ddm.data.SRDataset`` selects ``SRBatchStream``, whose ``image`` -- the HR crop -- is what the DIV2K first stage trains on
+    (data.py:645-658); everything else goes to ``ImageStream``, which refuses what it does not build.  The stream carries ``channels``."""
+    from adm_amd.ddm.datasets import DATASETS, dataset_of
+    from adm_amd.ddm.image_data import ImageBatchStream
     data_cfg = data_cfg or {}
-    cls = data_cfg.get("class_name")
-    picked = stream_class(data_cfg)
-    if picked is not None:
-        return picked(data_cfg, batch, size, device, seed)
-    if cls == "synthetic" and data_cfg.get("synthetic_of") is not None and data_cfg.get("synthetic_of") not in SR_CLASSES:
+    key = dataset_of(data_cfg)
+    picked = DATASETS[key].first_stage if key else None
+    if picked is None and data_cfg.get("class_name") == "synthetic" and data_cfg.get("synthetic_of") is not None:
         raise NotImplementedError(f"data.synthetic_of {data_cfg.get('synthetic_of')!r}: a synthetic first-stage pool is built for "
                                   "ddm.data.ImageDataset, ddm.data.DUTSDataset, ddm.data.SketchDataset and ddm.data.SRDataset")
-    if cls in SR_CLASSES or (cls == "synthetic" and data_cfg.get("synthetic_of") in SR_CLASSES):
-        stream = SRBatchStream(data_cfg, batch, size, device, seed)
-    else:
-        stream = ImageStream(data_cfg, batch, size, device, seed)
-    stream.channels = 3
+    stream = (picked or ImageStream)(data_cfg, batch, size, device, seed)
+    if not isinstance(stream, ImageBatchStream):          # (the one-plane streams say their own)
+        stream.channels = 3
     return stream
 
 
