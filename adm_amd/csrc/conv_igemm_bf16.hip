@@ -260,6 +260,27 @@ extern "C" int adm_f32_to_bf16(const float* src, unsigned short* dst, long n, hi
   return ADM_OK;
 }
 
+// The form a launch with tile < 0 takes: 0 = 128x128, 1 = 128x96, 2 = 64x64 (the one copy of the rule: conv_fwd_bf16_impl calls it).
+static int conv_bf16_tile(long M, int N) {
+  struct Cand { int id, bm, bn, per_cu; double eff; };
+  const Cand cands[3] = {{0, 128, 128, 2, 1.00}, {1, 128, 96, 2, 0.95}, {2, 64, 64, 4, 0.80}};
+  double best = 1e300;
+  int tile = 0;
+  for (const Cand& c : cands) {
+    long tiles = ((M + c.bm - 1) / c.bm) * adm_cdiv(N, c.bn);
+    long slots = 256L * c.per_cu;
+    long rounds = (tiles + slots - 1) / slots;
+    double t = (double)rounds * c.per_cu * c.bm * c.bn / c.eff;
+    if (t < best) { best = t; tile = c.id; }
+  }
+  return tile;
+}
+
+extern "C" int adm_conv_bf16_tile(long M, int N) {
+  if (M <= 0 || N <= 0) return ADM_EINVAL;
+  return conv_bf16_tile(M, N);
+}
+
 static int conv_fwd_bf16_impl(const float* x, const unsigned short* wp, const float* bias, const float* res, float* y, int B, int H, int W,
                               int Cin, int ldx, int N, int wrows, int ldy, int ldr, int ks, int up, int tile, int abf,
                               hipStream_t stream);
@@ -295,18 +316,7 @@ static int conv_fwd_bf16_impl(const float* x, const unsigned short* wp, const fl
   const long xb = (long)B * p.Hin * p.Win * ldx * (abf ? 2 : 4), wb = (long)wrows * p.K * 2;
   if (xb >= (1L << 31) || wb >= (1L << 31)) return ADM_EINVAL;
   p.xbytes = (int)xb; p.wbytes = (int)wb;
-  if (tile < 0) {
-    struct Cand { int id, bm, bn, per_cu; double eff; };
-    const Cand cands[3] = {{0, 128, 128, 2, 1.00}, {1, 128, 96, 2, 0.95}, {2, 64, 64, 4, 0.80}};
-    double best = 1e300;
-    for (const Cand& c : cands) {
-      long tiles = (long)adm_cdiv(p.M, c.bm) * adm_cdiv(N, c.bn);
-      long slots = 256L * c.per_cu;
-      long rounds = (tiles + slots - 1) / slots;
-      double t = (double)rounds * c.per_cu * c.bm * c.bn / c.eff;
-      if (t < best) { best = t; tile = c.id; }
-    }
-  }
+  if (tile < 0) tile = conv_bf16_tile(p.M, N);
   switch (tile) {
     case 0: return launch_b<128, 128, 2, 2>(p, stream);
     case 1: return launch_b<128, 96, 4, 1>(p, stream);

@@ -222,6 +222,36 @@ int launch_wb(WgradBP p, int splits, hipStream_t st) {
 
 }  // namespace
 
+// Tile form, split count and pixels per split of a launch (the one copy of the rule: conv_wgrad_bf16_impl calls it).  splits <= 0:
+// chosen here; the count is then rounded so that every split but the last holds `chunk` pixels, a multiple of the 64-pixel stage.
+struct WgradBPlan { int TM, TN, splits, chunk; };
+static WgradBPlan wgrad_bf16_plan(long P, int Cin, int Cout, int ks, int splits) {
+  WgradBPlan r;
+  r.TM = (Cout % 128 == 0) ? 128 : 64;
+  r.TN = (Cin % 128 == 0) ? 128 : 64;
+  if (splits <= 0) {
+    const long tiles = (long)adm_cdiv(Cout, r.TM) * adm_cdiv(Cin, r.TN) * ks * ks;
+    const long slots = 256L * 2;
+    const int maxs = (int)((P + 1023) / 1024);
+    if (tiles >= slots) splits = 1;
+    else {
+      splits = (int)(slots / tiles);
+      if (splits > maxs) splits = maxs;
+      if (splits < 1) splits = 1;
+    }
+  }
+  r.chunk = (int)(((P + splits - 1) / splits + PK - 1) / PK * PK);
+  r.splits = (int)((P + r.chunk - 1) / r.chunk);
+  return r;
+}
+
+extern "C" int adm_conv_wgrad_bf16_plan(long P, int Cin, int Cout, int ks, int splits, int* out) {
+  if (!out || P <= 0 || P >= (1L << 31) || Cin <= 0 || Cout <= 0 || (Cin & 31) || (Cout & 31) || (ks != 1 && ks != 3)) return ADM_EINVAL;
+  const WgradBPlan r = wgrad_bf16_plan(P, Cin, Cout, ks, splits);
+  out[0] = r.TM; out[1] = r.TN; out[2] = r.splits; out[3] = r.chunk;
+  return ADM_OK;
+}
+
 static int conv_wgrad_bf16_impl(const float* x, const float* dy, float* dwp, int B, int H, int W, int Cin, int ldx, int Cout, int lddy,
                                 int ks, int up, int splits, int xbf, hipStream_t stream);
 
@@ -252,22 +282,10 @@ static int conv_wgrad_bf16_impl(const float* x, const float* dy, float* dwp, int
   auto ilog2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; };
   p.lw = ilog2(W); p.lh = ilog2(H);
   if (p.lw < 0 || p.lh < 0) p.lw = p.lh = -1;
-  const int TM = (Cout % 128 == 0) ? 128 : 64;
-  const int TN = (Cin % 128 == 0) ? 128 : 64;
   const bool prezeroed = splits == ADM_SPLITS_AUTO_PREZEROED;      // zero-at-rest workspace: no memset
-  if (splits <= 0) {
-    const long tiles = (long)adm_cdiv(Cout, TM) * adm_cdiv(Cin, TN) * ks * ks;
-    const long slots = 256L * 2;
-    const int maxs = (p.P + 1023) / 1024;
-    if (tiles >= slots) splits = 1;
-    else {
-      splits = (int)(slots / tiles);
-      if (splits > maxs) splits = maxs;
-      if (splits < 1) splits = 1;
-    }
-  }
-  int chunk = ((p.P + splits - 1) / splits + PK - 1) / PK * PK;
-  splits = (p.P + chunk - 1) / chunk;
+  const WgradBPlan plan = wgrad_bf16_plan(p.P, Cin, Cout, ks, splits);
+  const int TM = plan.TM, TN = plan.TN, chunk = plan.chunk;
+  splits = plan.splits;
   p.chunk = chunk;
   p.atomic = splits > 1;
   if (p.atomic && !prezeroed &&

@@ -69,6 +69,8 @@ _SIGS = {
     "adm_conv_wgrad_bf16a": [P, P, P, I, I, I, I, I, I, I, I, I, I, P],
     "adm_gn_fwd_bf16out": [P, P, P, P, P, P, L, P, I, I, I, I, F, I, F, U, P],
     "adm_f32_to_bf16": [P, P, L, P],
+    "adm_conv_bf16_tile": [L, I],
+    "adm_conv_wgrad_bf16_plan": [L, I, I, I, I, P],
     "adm_pack_weight": [P, P, P, I, I, I, I, I, I, P],
     "adm_pack_weight_table": [P, I, L, P],
     "adm_unpack_wgrad_table": [P, I, L, P],
@@ -241,7 +243,7 @@ def ptr(t) -> c_void_p:
 
 
 NO_STREAM = ("adm_version", "adm_conv_splitk", "adm_gn_splits", "adm_aug_workspace_floats", "adm_conv_wgrad_plan",
-             "adm_sumsq_blocks", "adm_lnc_blocks", "adm_bn_blocks", "adm_linattn_ws_floats", "adm_wino2d_splitk", "adm_wino2d_x6_splitk", "adm_wino2d_variant", "adm_wino2d_h3_wide", "adm_wgrad_h3_blocks", "adm_gn_fused", "adm_gn_plan", "adm_conv_wgrad_x6_plan", "adm_gemm_wgrad_x6_plan", "adm_lpips_head_blocks", "adm_ae_blocks", "adm_swin_attn_bwd_ws_floats", "adm_ln_bwd_ws_floats", "adm_sr_tile", "adm_pair_resize_lds", "adm_patch_embed_ln_bwd_ws_floats")      # host-side queries: no stream argument, called as lib().name(...)
+             "adm_sumsq_blocks", "adm_lnc_blocks", "adm_bn_blocks", "adm_linattn_ws_floats", "adm_wino2d_splitk", "adm_wino2d_x6_splitk", "adm_wino2d_variant", "adm_wino2d_h3_wide", "adm_wgrad_h3_blocks", "adm_gn_fused", "adm_gn_plan", "adm_conv_wgrad_x6_plan", "adm_gemm_wgrad_x6_plan", "adm_lpips_head_blocks", "adm_ae_blocks", "adm_swin_attn_bwd_ws_floats", "adm_ln_bwd_ws_floats", "adm_sr_tile", "adm_pair_resize_lds", "adm_patch_embed_ln_bwd_ws_floats", "adm_conv_bf16_tile", "adm_conv_wgrad_bf16_plan")      # host-side queries: no stream argument, called as lib().name(...)
 
 
 def call(name: str, *args):

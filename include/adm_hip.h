@@ -232,6 +232,13 @@ int adm_gn_fwd_bf16out(const float* x, float* stats, double* ws, const float* ga
                        long ss_bstride, void* y16, int B, int HW, int C, int G, float eps, int silu, float drop_p, uint64_t seed,
                        hipStream_t stream);
 int adm_f32_to_bf16(const float* src, unsigned short* dst, long n, hipStream_t stream);
+/* Host queries of the two launch plans above (no launch; the launchers call the same functions).  adm_conv_bf16_tile: the form
+ * adm_conv_fwd_bf16 / _bf16a take with tile = -1 at M = B*H*W output pixels and N couts: 0 = 128x128, 1 = 128x96, 2 = 64x64.
+ * adm_conv_wgrad_bf16_plan: out = {TM, TN, splits, chunk} of adm_conv_wgrad_bf16 / _bf16a at P = B*H*W pixels: the cout x cin tile,
+ * the number of pixel ranges after rounding (> 1: fp32 atomics) and the pixels per range (a multiple of 64); `splits` as passed to
+ * the launcher (<= 0: chosen by it). */
+int adm_conv_bf16_tile(long M, int N);
+int adm_conv_wgrad_bf16_plan(long P, int Cin, int Cout, int ks, int splits, int* out);
 
 /* OIHW [Co][Ci][ks][ks] (the reference's parameter layout, uncond_unet.py:85) ->
  *   wp_fwd [Co_pad][ks*ks][Ci_pad]            (B operand of adm_conv_fwd)

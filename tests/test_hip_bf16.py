@@ -3,7 +3,9 @@ reference config runs fp32), so the bar is the build's own: (1) against a torch 
 rounded to bf16 the kernels must agree to fp32-accumulation accuracy (rtol 2e-4): that isolates the kernel from
 the rounding; (2) against the un-rounded fp32 reference the error must stay at bf16 level (2e-2 of the output
 scale); (3) end to end on the reduced UNet: <= 3e-2 of the output scale for outputs, cosine >= 0.999 for the
-flattened gradient."""
+flattened gradient.  The storage mode at full width, GroupNorm -> conv with a residual, is held to bars A and B of
+tests/test_hip_accuracy.py against fp64 of the values as stored; the direct kernels per tile form are in
+tests/test_hip_bf16_accuracy.py."""
 import math
 
 import pytest
@@ -11,6 +13,9 @@ import torch
 import torch.nn.functional as F
 
 from oracle import fill, unet_ref
+
+import fp64ref
+import gn_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -30,9 +35,14 @@ def r16(t):
     return t.to(torch.bfloat16).to(torch.float32)
 
 
-@pytest.mark.parametrize("cin,cout,H,ks,up", [(64, 128, 16, 3, False), (192, 192, 32, 3, False), (128, 64, 8, 1, False),
-                                              (64, 64, 8, 3, True), (384, 96, 12, 3, False), (64, 3, 16, 3, False)])
-def test_conv_bf16_forward_backward(ops_bf16, cin, cout, H, ks, up):
+# the last two: a residual per kernel size (the epilogues read it with their own indexing).  The ids of the earlier cases are kept.
+_CONV_CASES = [(64, 128, 16, 3, False, False), (192, 192, 32, 3, False, False), (128, 64, 8, 1, False, False), (64, 64, 8, 3, True, False),
+               (384, 96, 12, 3, False, False), (64, 3, 16, 3, False, False), (64, 96, 12, 3, False, True), (128, 192, 12, 1, False, True)]
+
+
+@pytest.mark.parametrize("cin,cout,H,ks,up,with_res", _CONV_CASES,
+                         ids=["-".join(str(v) for v in c[:5]) + ("-res" if c[5] else "") for c in _CONV_CASES])
+def test_conv_bf16_forward_backward(ops_bf16, monkeypatch, cin, cout, H, ks, up, with_res):
     ops = ops_bf16
     B = 3
     x = fill.hash_tensor((B, cin, H, H), f"bx{cin}{cout}", 1.0)
@@ -40,36 +50,52 @@ def test_conv_bf16_forward_backward(ops_bf16, cin, cout, H, ks, up):
     b = fill.hash_tensor((cout,), f"bb{cin}{cout}", 0.5)
     Ho = 2 * H if up else H
     gy = fill.hash_tensor((B, cout, Ho, Ho), f"bg{cin}{cout}", 1.0)
+    r = fill.hash_tensor((B, cout, Ho, Ho), f"br{cin}{cout}", 1.0) if with_res else None
     cop = ops.ceil32(cout)
     pad = lambda t, c: torch.cat([t, torch.zeros(t.shape[0], c - t.shape[1], *t.shape[2:])], 1) if c > t.shape[1] else t
     xd = pad(x, ops.ceil32(cin)).permute(0, 2, 3, 1).contiguous().cuda().requires_grad_(True)
     wd, bd = w.cuda().requires_grad_(True), b.cuda().requires_grad_(True)
-    y = ops.conv2d(xd, wd, bd, None, up=up)
-    (y * pad(gy, cop).permute(0, 2, 3, 1).contiguous().cuda()).sum().backward()
+    rd = pad(r, cop).permute(0, 2, 3, 1).contiguous().cuda().requires_grad_(True) if with_res else None
+    names = []
+    orig_call = ops.call
+    monkeypatch.setattr(ops, "call", lambda name, *a: (names.append(name), orig_call(name, *a))[1])
+    y = ops.conv2d(xd, wd, bd, rd, up=up)
+    gyd = pad(gy, cop).permute(0, 2, 3, 1).contiguous().cuda()
+    (y * gyd).sum().backward()
     yh = y.detach().cpu().permute(0, 3, 1, 2)[:, :cout]
 
     def ref(xx, ww, gg):
         xr, wr, br = xx.clone().requires_grad_(True), ww.clone().requires_grad_(True), b.clone().requires_grad_(True)
         xin = F.interpolate(xr, scale_factor=2, mode="nearest") if up else xr
         yr = F.conv2d(xin, wr, br, padding=ks // 2)
+        if with_res:
+            yr = yr + r
         return yr, xr, wr
 
     # (1) operands rounded exactly as the kernel rounds them.  dgrad rounds dy and w; wgrad rounds dy and x.
     yr, xr, wr = ref(r16(x), r16(w), gy)
     torch.testing.assert_close(yh, yr.detach(), rtol=2e-4, atol=2e-4 * float(yr.detach().abs().max()))
     yr.backward(r16(gy))
-    if cop % 64 == 0:       # dgrad ran in bf16 (else the fp32 kernel handled it)
-        torch.testing.assert_close(xd.grad.cpu().permute(0, 3, 1, 2)[:, :cin], xr.grad, rtol=2e-4,
-                                   atol=2e-4 * float(xr.grad.abs().max()))
     y32, x32, w32 = ref(x, w, gy)
     y32.backward(gy)
+    dxh = xd.grad.cpu().permute(0, 3, 1, 2)[:, :cin]
+    if cop % 64 == 0:       # dgrad ran in bf16: forward and data gradient on the same entry point
+        assert names.count("adm_conv_fwd_bf16") == 2, names
+        torch.testing.assert_close(dxh, xr.grad, rtol=2e-4, atol=2e-4 * float(xr.grad.abs().max()))
+    else:                   # dy has a channel count the bf16 kernel does not take: the data gradient ran on the f32 kernel, on the
+        #                     un-rounded dy and w -- it meets the same fp32-accumulation tolerance against the UN-ROUNDED reference
+        assert names.count("adm_conv_fwd_bf16") == 1, names
+        torch.testing.assert_close(dxh, x32.grad, rtol=2e-4, atol=2e-4 * float(x32.grad.abs().max()))
     # (x is f32 here: the direct bf16 kernel, which rounds dy and x on load.  With bf16-STORED activations the 3x3 weight gradient
     #  runs on the split-bf16 Winograd kernel instead: test_wgrad_x6_bf16_activations_equal_f32_kernel_on_rounded_x)
+    assert names.count("adm_conv_wgrad_bf16") == 1, names
     torch.testing.assert_close(wd.grad.cpu(), wr.grad, rtol=2e-4, atol=3e-4 * float(wr.grad.abs().max()))
     # (2) versus full fp32: bf16-level error only
     assert float((yh - y32.detach()).abs().max()) <= 2e-2 * float(y32.abs().max())
     assert float((wd.grad.cpu() - w32.grad).abs().max()) <= 2e-2 * float(w32.grad.abs().max())
     torch.testing.assert_close(bd.grad.cpu(), gy.sum(dim=(0, 2, 3)), rtol=1e-4, atol=1e-4 * float(gy.sum(dim=(0, 2, 3)).abs().max()))
+    if with_res:            # the residual's gradient is dy itself
+        assert torch.equal(rd.grad, gyd)
 
 
 @pytest.mark.parametrize("B,cin,cout,H,W", [(1, 64, 64, 1, 2), (1, 64, 128, 2, 2), (2, 128, 64, 1, 1), (3, 64, 64, 3, 5)])
@@ -206,3 +232,148 @@ def test_wgrad_x6_bf16_activations_equal_f32_kernel_on_rounded_x(ops_bf16, B, ci
     assert scale > 0
     assert float((out[0][0] - out[1][0]).abs().max()) <= 2e-6 * scale
     assert float((out[0][1] - out[1][1]).abs().max()) <= 2e-6 * float(out[0][1].abs().max())
+
+
+# ------------------------------------------------------------------------------------------------ storage mode at full width
+BAR_A = 1e-5        # tests/test_hip_accuracy.py: e_max against fp64 (fp64ref.errors), every path
+
+
+def _f32_kernels(ops, mp, x, w, b, res, dy, ks):
+    """The same conv on the f32-MFMA kernels (no split format, no Winograd-domain 16-bit images), forward and backward, on the values
+    given: what bar B compares against."""
+    mp.setattr(ops, "COMPUTE", "f32")
+    mp.setattr(ops, "BF16X6", False)
+    mp.setattr(ops, "FP16X3", False)
+    xd, wd = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+    y = ops.conv2d(xd, wd, b, res)
+    y.backward(dy)
+    ops.flush_deferred_unpack()
+    torch.cuda.synchronize()
+    mp.undo()
+    return y.detach(), xd.grad, wd.grad
+
+
+@pytest.mark.parametrize("B,H,cout,ks,wgrad", [(8, 16, 192, 3, "adm_conv_wgrad_x6_bf16a"), (4, 16, 576, 1, "adm_conv_wgrad_bf16a"),
+                                               (4, 12, 192, 3, "adm_conv_wgrad_bf16a")],
+                         ids=["3x3-16x16", "1x1-qkv-shaped", "3x3-12x12"])
+def test_storage_mode_gn_into_conv_vs_fp64(ops_bf16, B, H, cout, ks, wgrad):
+    """group_norm_act(to_conv=True) -> conv2d with a residual at 192 channels, forward and backward, in the storage mode: the conv reads
+    the stored bf16 values (adm_conv_fwd_bf16a) and the weight gradient takes the split-bf16 Winograd kernel on a power-of-two map of
+    >= 2048 pixels, the direct adm_conv_wgrad_bf16a below the split-GEMM threshold and on a 12x12 map.  Output and gradients against
+    fp64 of the values AS STORED (and of the operands rounded as each kernel rounds them: the data gradient dy and w, the direct
+    weight gradient dy, the split one nothing), on bars A and B."""
+    ops = ops_bf16
+    assert ops.bf16_storage()
+    C = 192
+    tag = f"st{B}{H}{cout}{ks}"
+    x = fill.hash_tensor((B, H, H, C), tag + "x", 1.5).cuda().requires_grad_(True)
+    gam, bet = (1 + fill.hash_tensor((C,), tag + "g", 0.2)).cuda(), fill.hash_tensor((C,), tag + "b", 0.1).cuda()
+    w = fill.hash_tensor((cout, C, ks, ks), tag + "w", 1.0 / math.sqrt(C * ks * ks)).cuda()
+    b = fill.hash_tensor((cout,), tag + "c", 0.5).cuda()
+    res = fill.hash_tensor((B, H, H, cout), tag + "r", 1.0).cuda()
+    dy = fill.hash_tensor((B, H, H, cout), tag + "d", 1.0).cuda()
+    wd, bd, rd = w.clone().requires_grad_(True), b.clone().requires_grad_(True), res.clone().requires_grad_(True)
+    names, grads = [], {}
+    with pytest.MonkeyPatch.context() as mp:
+        orig_call = ops.call
+        mp.setattr(ops, "call", lambda name, *a: (names.append(name), orig_call(name, *a))[1])
+        h = ops.group_norm_act(x, gam, bet, None, silu=True, to_conv=True)
+        h16 = h._adm_bf16
+        h.register_hook(lambda g: grads.__setitem__("dh", g.clone()))
+        y = ops.conv2d(h, wd, bd, rd)
+        y.backward(dy)
+        ops.flush_deferred_unpack()
+        torch.cuda.synchronize()
+    assert "adm_gn_fwd_bf16out" in names and names.count("adm_conv_fwd_bf16a") == 1 and names.count("adm_conv_fwd_bf16") == 1, names
+    assert wgrad in names and not any(n.startswith("adm_conv_wgrad") and n != wgrad for n in names), names
+    assert torch.equal(rd.grad, dy) and bool(torch.isfinite(x.grad).all())
+    hf = h16.to(torch.float32)
+    dy_w = dy if wgrad == "adm_conv_wgrad_x6_bf16a" else r16(dy)          # the split kernel keeps dy exact (three-term split)
+    ref = fp64ref.conv(hf, r16(w), b, res)
+    ref_dx = fp64ref.conv(hf, r16(w), dy=r16(dy))["dx"]
+    ref_dw = fp64ref.conv(hf, w, dy=dy_w)["dw"]
+    ref_db = fp64ref.conv(hf, w, b, dy=dy)["db"]
+    with pytest.MonkeyPatch.context() as mp:
+        y32, dx32, _ = _f32_kernels(ops, mp, hf, r16(w), b, res, r16(dy), ks)
+    with pytest.MonkeyPatch.context() as mp:
+        dw32 = _f32_kernels(ops, mp, hf, w, b, res, dy_w, ks)[2]
+    bad = []
+    for out, got, rf, g32 in (("y", y.detach(), ref["y"], y32), ("dx", grads["dh"], ref_dx, dx32), ("dw", wd.grad, ref_dw, dw32),
+                              ("db", bd.grad, ref_db, None)):
+        e = fp64ref.errors(got, *rf)
+        line = f"{tag} {out}: e_max {e[0]:.2e} e_rms {e[1]:.2e}"
+        if e[0] > BAR_A:
+            bad.append("bar A: " + line)
+        if g32 is not None:
+            e32 = fp64ref.errors(g32, *rf)
+            ok, rm, rr = fp64ref.bar_b(e, e32)
+            line += f"  f32 {e32[0]:.2e}/{e32[1]:.2e}  ratios {rm:.2f}/{rr:.2f}"
+            if not ok:
+                bad.append("bar B: " + line)
+        print(line)
+    assert not bad, "\n".join(bad)
+
+
+@pytest.mark.parametrize("row", [r for r in gn_cases.GRID if r[2] % 64 == 0], ids=gn_cases.row_id)
+def test_group_norm_bf16_storage_output_over_the_plan_grid(ops_bf16, row):
+    """adm_gn_fwd_bf16out on every launch plan of the GroupNorm grid it can take (C % 64 == 0), with scale/shift, SiLU and dropout: the
+    stored values are the round-to-nearest-even bf16 of what adm_gn_fwd writes in f32 on the same plan."""
+    ops = ops_bf16
+    H, W, C, _, eps, B, _ = row
+    c = gn_cases.make_case(row, "plain")
+    x, g, b, ss = (c[k].cuda() for k in ("x", "gamma", "beta", "ss"))
+    kw = dict(silu=True, drop_p=0.1, seed=4321, groups=gn_cases.groups_of(row), eps=eps)
+    y32 = ops.group_norm_act(x, g, b, ss, **kw)
+    y16 = ops.group_norm_act(x, g, b, ss, to_conv=True, **kw)._adm_bf16
+    assert y16.dtype == torch.bfloat16 and y16.shape == x.shape
+    assert bool((y32 == 0).any()) and bool((y32 != 0).any())                      # the dropout really dropped
+    assert torch.equal(y16, y32.to(torch.bfloat16))
+
+
+@pytest.mark.parametrize("storage", [False, True], ids=["f32-storage", "bf16-storage"])
+def test_weight_change_in_place_reaches_the_bf16_operands(ops_bf16, monkeypatch, storage):
+    """The bf16 weight copies (fwd16 / bwd16) are rebuilt from the f32 operands, which repack_all() refreshes only if they were read:
+    after an in-place change of the weight as the optimiser makes it (through the storage, no version bump) and repack_all(), forward
+    and backward equal, bit for bit, a fresh layer built from the new values -- also when the step before the change ran no backward
+    (the data-gradient operand then goes stale and is refreshed on its next read)."""
+    ops = ops_bf16
+    monkeypatch.setattr(ops, "BF16_STORAGE", storage)
+    B, H, C, co = 2, 8, 64, 128
+    xv = fill.hash_tensor((B, H, H, C), "wrx", 1.0).cuda()
+    gam, bet = torch.ones(C, device="cuda"), torch.zeros(C, device="cuda")
+    dy = fill.hash_tensor((B, H, H, co), "wrd", 1.0).cuda()
+    w0 = fill.hash_tensor((co, C, 3, 3), "wrw", 1.0 / 24).cuda()
+    delta = fill.hash_tensor((co, C, 3, 3), "wru", 0.01).cuda()
+    bias = fill.hash_tensor((co,), "wrb", 0.5).cuda()
+
+    def step(weight, backward=True):
+        x = xv.clone().requires_grad_(True)
+        weight.grad = None
+        h = ops.group_norm_act(x, gam, bet, None, silu=True, to_conv=True)
+        assert (getattr(h, "_adm_bf16", None) is not None) == storage
+        y = ops.conv2d(h, weight, bias)
+        if backward:
+            y.backward(dy)
+            ops.flush_deferred_unpack()
+        torch.cuda.synchronize()
+        return (y.detach().clone(),) + ((x.grad.clone(), weight.grad.clone()) if backward else ())
+
+    layer = torch.nn.Parameter(w0.clone())
+    first = step(layer)
+    for backward_before in (True, False):
+        if not backward_before:                         # an optimiser step whose successor runs no backward: only the forward
+            ops.repack_all()                            # operand is read between the two repacks
+            step(layer, backward=False)
+        version = layer._version
+        layer.data.add_(delta)                          # as the fused optimiser: the values change, the version does not
+        assert layer._version == version
+        ops.repack_all()
+        ent = layer._adm_packed
+        assert ent.fwd16 is None and ent.bwd16 is None
+        assert bool(ent._stale & 2) == (not backward_before)      # the data-gradient operand was left out of the repack
+        got = step(layer)
+        assert layer._adm_packed is ent                 # the same entry, refreshed -- not a rebuild
+        fresh = step(torch.nn.Parameter(layer.detach().clone()))
+        for u, v in zip(got, fresh):
+            assert torch.equal(u, v)
+        assert not torch.equal(got[0], first[0])
