@@ -6,6 +6,7 @@ picks the class.
 """
 from collections import namedtuple
 
+from .depth_data import DEPTH_CLASSES, DepthBatchStream, DepthMapStream
 from .image_data import IMAGE_CLASSES, DUTSMapStream, ImageFolderStream, SketchPhotoStream
 from .inpaint_data import InpaintBatchStream
 from .pair_data import DUTS_CLASSES, SKETCH_CLASSES, DUTSBatchStream, SketchBatchStream
@@ -21,7 +22,8 @@ def dataset_of(data_cfg):
     data_cfg = data_cfg or {}
     cls = data_cfg.get("class_name")
     name = data_cfg.get("synthetic_of") if cls == "synthetic" else cls
-    return next((c[0] for c in (IMAGE_CLASSES, SR_CLASSES, INPAINT_CLASSES, DUTS_CLASSES, SKETCH_CLASSES) if name in c), None)
+    return next((c[0] for c in (IMAGE_CLASSES, SR_CLASSES, INPAINT_CLASSES, DUTS_CLASSES, SKETCH_CLASSES, DEPTH_CLASSES)
+                 if name in c), None)
 
 
 # What sample_cond_ldm.py does with a dataset's items:
@@ -32,8 +34,10 @@ def dataset_of(data_cfg):
 #   one_window  the recipe's name in the NotImplementedError for sampler.crop_size != image_size, or None where windows slide
 #   psnr / gray / save_masks   score against 'image'; one channel is a mode-L png; ``sampler.save_masks`` writes masks/<name>
 #   synthetic   whether ``class_name: synthetic`` + ``synthetic_of`` selects this entry at sampling time
-Sampling = namedtuple("Sampling", "form item split_test no_flip one_window psnr gray save_masks synthetic",
-                      defaults=(None, None, False, None, True, False, False, False))
+#   depth       the prediction is a depth fraction: written as a 16-bit png of round(clip(p, 0, 1) * 10000) (8 bits with
+#               ``sampler.depth_png8``) and scored with adm_amd.metrics.depth against 'image' into <save_folder>/depth_metrics.json
+Sampling = namedtuple("Sampling", "form item split_test no_flip one_window psnr gray save_masks synthetic depth",
+                      defaults=(None, None, False, None, True, False, False, False, False))
 # every data section that selects no entry below: the super-resolution items of sample_cond_ldm.CondStream
 SR_SAMPLING = Sampling("slide_x4")
 
@@ -51,7 +55,12 @@ DATASETS = {
         "window", lambda s, k, b: (b["ori_size"][0], b["img_name"][0]),          # the sketch's file name (= the photo's)
         split_test="sampling ddm.data.SketchDataset needs data.split: test (GT/val + Sketch/val, in order, unflipped)",
         one_window="sketch-to-image", psnr=False,
-        synthetic=True)),          # the ONLY entry synthetic_of reaches at sampling time: kept as found, not a decision (README)
+        synthetic=True)),          # reached by synthetic_of at sampling time: kept as found, not a decision (README)
+    DEPTH_CLASSES[0]: Dataset(DepthBatchStream, DepthMapStream, Sampling(
+        "slide", lambda s, k, b: (b["ori_size"][0], b["img_name"][0][:-4] + ".png"),          # the photo's name, as png
+        split_test="sampling ddm.data.NYUDv2DepthDataset needs data.split: test (whole 426x560 frames, in order, unflipped)",
+        gray=True, psnr=False, depth=True,
+        synthetic=True)),          # a decision: the committed sample YAML runs without data (README)
 }
 
 

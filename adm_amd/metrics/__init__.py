@@ -1,4 +1,5 @@
 """FID and Inception score on the HIP hot path: the InceptionV3 extractor (inception.py), the streaming float64 statistics and the
-metrics (fid.py), and the folder evaluation the drivers share (evaluate.py)."""
+metrics (fid.py), and the folder evaluation the drivers share (evaluate.py); the depth-estimation score (depth.py: abs-rel, RMSE,
+delta ... from per-image float64 sums made on the device)."""
 from .fid import FeatureStats, Stats, fid_from_stats, inception_score, load_stats, save_stats  # noqa: F401
 from .inception import FeatureExtractorInceptionV3  # noqa: F401

@@ -925,6 +925,42 @@ int adm_tf1_resize_norm_u8(const unsigned char* img, float* y, int B, int H, int
  * the same bits every run.  The host forms mu = shift + sum / N and sigma = (outer - sum sum^T / N) / (N - 1). */
 int adm_feat_stats_accum(const float* x, int n, int D, double* shift, double* sum, double* outer, int first, hipStream_t stream);
 
+/* ================================================================================================
+ * Depth estimation (csrc/depth_data.hip): the batches of ddm.data.NYUDv2DepthDataset (ddm/data.py:869-887) and the depth score.
+ * ================================================================================================ */
+
+/* One launch makes a batch from a uint8 HWC photo pool (adm_sr_batch's layout) and a 16-BIT depth pool: little-endian, two bytes
+ * per pixel, 2-byte aligned, depth_bytes even, every depth_off[n] even.  Image n of either pool starts at byte *_off[n] and is
+ * *_hw[2n] x *_hw[2n+1] pixels.  Sample b is image n = idx[b] (clamped to [0, n_images)); output pixel (y, x) is the source pixel
+ *   (box_top + top[b] + y,  box_left + left[b] + (flip[b] ? W - 1 - x : x))
+ * of both planes, top / left clamped to [0, box height - H] / [0, box width - W]; the box is PIL's (left, upper, right, lower).
+ *   image [B][1][H][W] = (u16 / 10000) * 2 - 1 (no clipping), cond [B][3][H][W] = (u8 / 255) * 2 - 1: IEEE float32 operations in
+ *   that order, equal bit for bit to NumPy's.
+ * `image` or `cond` may be NULL (not both); the pool of a NULL output is not read and may be NULL too.  idx / top / left / flip:
+ * int32 [B], read on the device.  With W % 4 == 0 and 16-byte aligned outputs every thread writes 16 bytes per plane, otherwise one
+ * pixel.  ADM_EINVAL, without launching: a missing pointer, an odd depth_bytes or depth pointer, B > 65535, a box smaller than
+ * H x W or with a negative corner.  A source pixel outside its image or its pool reads as 0: wrong tables give wrong pixels, never an
+ * access outside the pools. */
+int adm_depth_batch(const uint8_t* rgb_pool, long rgb_bytes, const int64_t* rgb_off, const int* rgb_hw, const uint8_t* depth_pool,
+                    long depth_bytes, const int64_t* depth_off, const int* depth_hw, int n_images, int box_left, int box_top,
+                    int box_right, int box_bottom, const int* idx, const int* top, const int* left, const int* flip, float* image,
+                    float* cond, int B, int H, int W, hipStream_t stream);
+
+/* Per-image float64 sums of the depth score from pred / gt [B][hw] float32, depth as a FRACTION of 10 m (metres = 10 x): over the
+ * pixels with min_depth < gt_m < max_depth, with pred_m clamped to [min_depth, max_depth],
+ *   sums[b] = { n, S|p-g|/g, S(p-g)^2/g, S(p-g)^2, S(ln p - ln g)^2, S(ln p - ln g), S|log10 p - log10 g|,
+ *               #[r < 1.25], #[r < 1.25^2], #[r < 1.25^3] },  r = max(p/g, g/p)          (ADM_DEPTH_SUMS doubles, counts as doubles)
+ * One launch of adm_depth_metrics_blocks(hw) workgroups per image (one per ADM_DEPTH_CHUNK pixels, at most ADM_DEPTH_MAX_BLOCKS); each
+ * writes its partial sums to partial [B][blocks][ADM_DEPTH_SUMS], and the last one of an image to finish (ticket[b], an integer
+ * counter) adds them in index order: no float atomics, the same bits every run.  ticket: int32 [B], ZERO on entry and zero again on
+ * return.  ADM_EINVAL: a null pointer, B > 65535, min_depth <= 0 or max_depth <= min_depth. */
+#define ADM_DEPTH_SUMS 10
+#define ADM_DEPTH_CHUNK 4096
+#define ADM_DEPTH_MAX_BLOCKS 64
+int adm_depth_metrics_blocks(long hw);
+int adm_depth_metrics(const float* pred, const float* gt, double* sums, double* partial, int* ticket, int B, long hw,
+                      double min_depth, double max_depth, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,9 +34,17 @@ configs/sketch2img/sketchcoco_cond_ddm_const_ldm_sample.yaml) the condition is t
 output a three-channel image, sampled in one window and written under the sketch's file name.  No PSNR is printed: a generated
 photo has no ground truth to score.
 
+With ``data.class_name: ddm.data.NYUDv2DepthDataset`` and ``split: test`` (depth estimation,
+configs/depth_estimation/nyud_cond_ddm_const_ldm_sample.yaml) the condition is the whole 426x560 boxed photo, sampled in overlapping
+windows of ``sampler.crop_size`` at ``sampler.stride`` (2 x 3 windows of 320x320 at stride 160), each twice with ``flip_test``.  The
+one-channel prediction is a depth fraction (1.0 = 10 m): it is written as a 16-BIT png of round(clip(p, 0, 1) * 10000) under the
+photo's name -- the reference writes 8 bits through save_image; ``sampler.depth_png8: True`` keeps that -- and scored against the
+ground truth with adm_amd.metrics.depth (abs-rel, RMSE, delta ...): printed at the end and written to
+``<save_folder>/depth_metrics.json``.
+
 Which of these a data section selects, and what differs between them, is the ``sampling`` column of adm_amd.ddm.datasets.DATASETS;
-``main`` is one loop over that entry.  ``class_name: synthetic`` + ``synthetic_of`` selects the sketch entry only: with any other
-``synthetic_of`` the items are CondStream's super-resolution pairs.
+``main`` is one loop over that entry.  ``class_name: synthetic`` + ``synthetic_of`` selects the sketch and the depth entries only:
+with any other ``synthetic_of`` the items are CondStream's super-resolution pairs.
 """
 import argparse
 import importlib
@@ -258,6 +266,17 @@ def save_prediction(img, folder, img_name, world, index, gray=False):
     return name
 
 
+def save_depth_prediction(img, folder, img_name, world, index):
+    """img [1,H,W] depth fraction as a 16-bit png (mode I;16) of round(clip(p, 0, 1) * 10000) raw units -- millimetres, as the
+    dataset's own depth files -- under the item's own name, or -- several ranks -- under its global index; returns the file name."""
+    import numpy as np
+    from adm_amd.ddm.depth_data import DEPTH_UNITS, write_depth_png
+    units = (img[0].to(torch.float32).clamp(0, 1) * DEPTH_UNITS).round().to(torch.int32).cpu().numpy().astype(np.uint16)
+    name = img_name if world == 1 else f"{index: 010d}.png"
+    write_depth_png(os.path.join(folder, name), units)
+    return name
+
+
 def window_sampler(ldm, scale):
     """c [B,C,h,w] -> the sample for the window c, `scale` times its size.  The encoder runs ONCE per window batch (the reference
     re-runs it inside every denoising step, cond_unet_sd.py:821)."""
@@ -335,13 +354,22 @@ def main():
     masks = sm.save_masks and bool(s.get("save_masks", False))
     if masks:
         os.makedirs(os.path.join(out_dir, "masks"), exist_ok=True)
+    depth_score = None
+    if sm.depth:
+        from adm_amd.metrics.depth import KEYS, DepthScore
+        depth_score = DepthScore(float(s.get("min_depth", 1e-3)), float(s.get("max_depth", 10.0)))
     psnr, done, t0 = 0.0, 0, time.time()
     for batch in stream:
         pred = FORMS[sm.form](ldm, s, batch, crop, stride)
         if sm.psnr:          # (reference :195) against the part of 'image' the prediction covers: SRDatasetTest cuts it to ori_size
             image = (batch["image"] + 1) * 0.5
             psnr += float(-10.0 * torch.log10(torch.mean((pred - image[:, :, :pred.shape[2], :pred.shape[3]]) ** 2)))
-        name = save_prediction(pred[0], out_dir, batch["img_name"], world, rank * per_rank + done, sm.gray)
+        if depth_score is not None:          # on the device; the sums are copied to the host once, at the end
+            depth_score.add(pred.to(torch.float32).contiguous(), ((batch["image"] + 1) * 0.5).contiguous())
+        if sm.depth and not bool(s.get("depth_png8", False)):
+            name = save_depth_prediction(pred[0], out_dir, batch["img_name"], world, rank * per_rank + done)
+        else:
+            name = save_prediction(pred[0], out_dir, batch["img_name"], world, rank * per_rank + done, sm.gray)
         if masks:
             save_prediction(batch["ori_mask"][0], os.path.join(out_dir, "masks"), name, 1, 0, gray=True)          # 0 / 1 -> 0 / 255
         done += 1
@@ -349,6 +377,13 @@ def main():
     dt = time.time() - t0
     score = f"; PSNR: {psnr / max(done, 1):.2f}" if sm.psnr else ""
     print(f"rank {rank}: {done} images in {dt:.1f}s ({done / max(dt, 1e-9):.2f} images/sec incl. PNG writes){score}")
+    if depth_score is not None:
+        import json
+        res = depth_score.result()
+        print(f"rank {rank}: depth score over {res['images']} images ({res['skipped']} without a valid pixel): "
+              + " ".join(f"{k}={res[k]:.4f}" for k in KEYS))
+        with open(os.path.join(out_dir, "depth_metrics.json" if world == 1 else f"depth_metrics_rank{rank}.json"), "w") as f:
+            json.dump(res, f)
 
 
 if __name__ == "__main__":

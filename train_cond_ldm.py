@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """MI355X counterpart of the reference's conditional LATENT trainer (its train_cond_ldm.py): the 4x super-resolution
 recipe (configs/super-resolution/div2k_cond_ddm_const_ldm_train.yaml), the in-painting recipe
-(configs/inpainting/celebahq_cond_ddm_const_ldm.yaml), the saliency recipe (configs/saliency/duts_cond_ddm_const_ldm.yaml) and the
-sketch-to-image recipe (configs/sketch2img/sketchcoco_cond_ddm_const_ldm.yaml).
+(configs/inpainting/celebahq_cond_ddm_const_ldm.yaml), the saliency recipe (configs/saliency/duts_cond_ddm_const_ldm.yaml), the
+sketch-to-image recipe (configs/sketch2img/sketchcoco_cond_ddm_const_ldm.yaml) and the depth recipe
+(configs/depth_estimation/nyud_cond_ddm_const_ldm.yaml).
 
 Same command line and YAML schema as the other drivers (``--cfg``, ``--max-steps``); model construction, gradient accumulation,
 clip-norm, EMA, the checkpoint layout and the multi-GPU launch are the shared Trainer of train_uncond_dpm.py.  What differs from
@@ -11,7 +12,8 @@ that driver (reference lines of train_cond_ldm.py in brackets):
     image pool (adm_amd.ddm.sr_data.SRBatchStream) instead of PIL in dataloader workers; with ``data.class_name:
     ddm.data.InpaintDataset`` the {'image', 'cond', 'ori_mask'} triples of adm_amd.ddm.inpaint_data.InpaintBatchStream; with
     ``ddm.data.DUTSDataset`` the {'image': map, 'cond': photo} pairs of adm_amd.ddm.pair_data.DUTSBatchStream; with
-    ``ddm.data.SketchDataset`` the {'image': photo, 'cond': sketch} pairs of its SketchBatchStream;
+    ``ddm.data.SketchDataset`` the {'image': photo, 'cond': sketch} pairs of its SketchBatchStream; with
+    ``ddm.data.NYUDv2DepthDataset`` the {'image': depth, 'cond': photo} crops of adm_amd.ddm.depth_data.DepthBatchStream;
   * LR schedule: ratio max((1 - it/N)^0.96, min_lr/lr) from step 0, no warm-up [:150];
   * weight decay defaults to 1e-2 [:72];
   * the periodic and ``test_before`` samples are conditioned on a training batch: sample(batch_size=cond.shape[0], cond=..., mask=

@@ -20,7 +20,7 @@ What differs: single process (data-parallel first-stage training is not implemen
 ordinary parameters, not the fused flat-buffer optimiser; AutoencoderKL.training_step runs its own backward (see
 adm_amd/ddm/loss.py), so the loop calls no .backward().  Data comes from ``first_stage_stream``: the recipe's own dataset
 (``ddm.data.ImageDataset``, the maps of ``ddm.data.DUTSDataset``, the photos of ``ddm.data.SketchDataset``, the HR crops of
-``ddm.data.SRDataset``; three or ONE channel), or train_uncond_dpm.ImageStream: ``data.npy`` (uint8 [N,H,W,3]) or
+``ddm.data.SRDataset``, the depth planes of ``ddm.data.NYUDv2DepthDataset``; three or ONE channel), or train_uncond_dpm.ImageStream: ``data.npy`` (uint8 [N,H,W,3]) or
 ``data.class_name: synthetic``.  LPIPS weights are not shipped: ``model.lossconfig.lpips_ckpt`` or a checkpoint
 with ``loss.perceptual_loss.*`` keys provides them; without them the perceptual term is zero (a warning says so).
 """
@@ -68,6 +68,7 @@ def first_stage_stream(data_cfg, batch, size, device, seed):
     """The batch source of a first stage, by ``data.class_name`` (or ``synthetic_of`` under ``class_name: synthetic``): the
     ``first_stage`` column of adm_amd.ddm.datasets.DATASETS.  ``ddm.data.ImageDataset`` / ``ddm.data.DUTSDataset`` (its maps, one
     channel) / ``ddm.data.SketchDataset`` (its photos) select the one-plane streams of adm_amd/ddm/image_data.py;
+    ``ddm.data.NYUDv2DepthDataset`` selects the one-channel ``DepthMapStream`` of adm_amd/ddm/depth_data.py;
     ``ddm.data.SRDataset`` selects ``SRBatchStream``, whose ``image`` -- the HR crop -- is what the DIV2K first stage trains on
     (data.py:645-658); everything else goes to ``ImageStream``, which refuses what it does not build.  The stream carries ``channels``."""
     from adm_amd.ddm.datasets import DATASETS, dataset_of
@@ -79,7 +80,7 @@ def first_stage_stream(data_cfg, batch, size, device, seed):
         raise NotImplementedError(f"data.synthetic_of {data_cfg.get('synthetic_of')!r}: a synthetic first-stage pool is built for "
                                   "ddm.data.ImageDataset, ddm.data.DUTSDataset, ddm.data.SketchDataset and ddm.data.SRDataset")
     stream = (picked or ImageStream)(data_cfg, batch, size, device, seed)
-    if not isinstance(stream, ImageBatchStream):          # (the one-plane streams say their own)
+    if not isinstance(stream, ImageBatchStream) and not hasattr(stream, "channels"):          # (the one-plane streams say their own)
         stream.channels = 3
     return stream
 
