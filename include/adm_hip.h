@@ -961,6 +961,30 @@ int adm_depth_metrics_blocks(long hw);
 int adm_depth_metrics(const float* pred, const float* gt, double* sums, double* partial, int* ticket, int B, long hw,
                       double min_depth, double max_depth, hipStream_t stream);
 
+/* ================================================================================================
+ * Kernel Inception distance (csrc/kid.hip): the polynomial-kernel MMD sums of every subset, in one launch.
+ * ================================================================================================ */
+
+/* f1 [n1][D], f2 [n2][D] float32, rows contiguous (ld = D), 16-byte aligned; idx1, idx2 int32 [S][m], read on the device.  For
+ * subset s with X = f1[idx1[s]], Y = f2[idx2[s]] and k(a, b) = (gamma <a, b> + coef0)^degree:
+ *   sums[s] = { sum_{i != j} k(X_i, X_j), sum_{i != j} k(Y_i, Y_j), sum_{i, j} k(X_i, Y_j) }              (float64 [S][3])
+ * i, j are subset POSITIONS: a feature row drawn twice into one subset counts as two rows.  The unbiased MMD^2 of the subset is
+ * (sums[0] + sums[1]) / (m (m - 1)) - 2 sums[2] / m^2.
+ * One launch of S * adm_kid_sums_blocks(m) workgroups covers all subsets and all three blocks: each gathers its rows through the
+ * index tables, forms an ADM_KID_TILE-square tile of dot products on the exact f32 MFMA (an fmaf chain over k), and sums
+ * (double(dot) * gamma + coef0)^degree (repeated multiplication) in float64 into partial [S][blocks]; no Gram matrix is written.  XX
+ * and YY are computed as upper triangles, off-diagonal tiles counted twice.  A second small launch adds each subset's partials in
+ * index order: no float atomics, the same bits every run.
+ * adm_kid_sums_tile(which): the workgroup tile edge of form `which` (0 ..), 0 past the last form -- there is one, ADM_KID_TILE.
+ * ADM_EINVAL, without launching: a null or misaligned pointer, D % 4 != 0, m < 2, m > min(n1, n2), S < 1, degree outside 1..8, a
+ * feature matrix of 2^31 bytes or more.  The caller checks 0 <= idx < n; an index outside reads as a zero row: wrong tables give
+ * wrong sums, never an access outside the features. */
+#define ADM_KID_TILE 128
+int adm_kid_sums_tile(int which);
+long adm_kid_sums_blocks(int m);
+int adm_kid_sums(const float* f1, int n1, const float* f2, int n2, int D, const int* idx1, const int* idx2, int S, int m, int degree,
+                 double gamma, double coef0, double* sums, double* partial, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

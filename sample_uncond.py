@@ -13,6 +13,10 @@ lets every rank write the same names).
 local InceptionV3 state dict) scores the samples after the PNGs are written, as the reference's ``Sampler.cal_fid`` does through
 ``fidelity -f -i``: FID against the target and the Inception score, on the HIP extractor (adm_amd/metrics), from the same uint8
 bytes that went into the files.  The result goes to ``<save_folder>/result.json``.  One process only.
+
+``sampler.cal_kid: True`` (the same two paths; ``sampler.kid_subsets`` / ``sampler.kid_subset_size``, default 100 / 1000) adds the
+kernel Inception distance to that file, with or without ``cal_fid``: the samples' features are kept on the device and the target's
+are cached as ``<target_path>.features.npz``.  The target is then a folder or saved features; saved statistics hold no features.
 """
 import argparse
 import os
@@ -45,14 +49,16 @@ def load_weights(model, path, use_ema, device):
 
 
 def check_cal_fid(cfg):
-    """Start-up refusals of ``sampler.cal_fid``, before any device work: one process only; the weights file and the target exist."""
+    """Start-up refusals of ``sampler.cal_fid`` and ``sampler.cal_kid``, before any device work: one process only; the weights file
+    and the target exist."""
     s = cfg.get("sampler") or {}
-    if not s.get("cal_fid", False):
+    if not s.get("cal_fid", False) and not s.get("cal_kid", False):
         return
+    key = "sampler.cal_fid" if s.get("cal_fid", False) else "sampler.cal_kid"
     from adm_amd.metrics import evaluate
-    evaluate.check_startup(s.get("inception_weights"), "sample_uncond.py (sampler.cal_fid)")
+    evaluate.check_startup(s.get("inception_weights"), f"sample_uncond.py ({key})")
     if not s.get("target_path") or not os.path.exists(s["target_path"]):
-        raise FileNotFoundError(f"sampler.cal_fid: sampler.target_path {s.get('target_path')!r} does not exist")
+        raise FileNotFoundError(f"{key}: sampler.target_path {s.get('target_path')!r} does not exist")
 
 
 def main():
@@ -91,10 +97,11 @@ def main():
     if args.max_batches is not None:
         n_batches = min(n_batches, args.max_batches)
     img_id, t0, done = rank * per_rank, time.time(), 0
-    if s.get("cal_fid", False):
+    cal_fid, cal_kid = bool(s.get("cal_fid", False)), bool(s.get("cal_kid", False))
+    if cal_fid or cal_kid:
         from adm_amd.metrics import evaluate
-        scorer = evaluate.Scorer(s.inception_weights, isc=True, device=device)
-        run = scorer.begin()
+        scorer = evaluate.Scorer(s.inception_weights, isc=cal_fid, device=device)
+        run = scorer.begin(keep_features=cal_kid)
     for _ in range(n_batches):
         real_bs = min(bs, per_rank - done)
         batch = dpm.sample(batch_size=real_bs)
@@ -109,11 +116,21 @@ def main():
     torch.cuda.synchronize()
     print(f"rank {rank}: {done} images in {time.time() - t0:.1f}s ({done / (time.time() - t0):.1f} images/sec incl. PNG writes)")
     if scorer is not None:
-        st, logits = run.finish()
-        target = scorer.target_stats(s.target_path, int(s.get("fid_batch_size", 64)))
-        res = evaluate.score(st, target, logits, os.path.join(out, "result.json"))
-        print(f"FID {res['frechet_inception_distance']:.4f}  Inception score {res['inception_score_mean']:.4f} +- "
-              f"{res['inception_score_std']:.4f} ({done} samples)")
+        st, logits, *feats = run.finish()
+        fid_bs, target, kid_res = int(s.get("fid_batch_size", 64)), None, None
+        if cal_kid:
+            from adm_amd.metrics import kid
+            kid_res = kid.kid_from_features(feats[0], scorer.target_features(s.target_path, fid_bs),
+                                            subsets=int(s.get("kid_subsets", kid.SUBSETS)),
+                                            subset_size=int(s.get("kid_subset_size", kid.SUBSET_SIZE)))
+        if cal_fid:
+            target = scorer.target_stats(s.target_path, fid_bs)
+        res = evaluate.score(st, target, logits, os.path.join(out, "result.json"), extra=kid_res)
+        if cal_fid:
+            print(f"FID {res['frechet_inception_distance']:.4f}  Inception score {res['inception_score_mean']:.4f} +- "
+                  f"{res['inception_score_std']:.4f} ({done} samples)")
+        if cal_kid:
+            print(f"KID {res[kid.KEY_KID_MEAN]:.6f} +- {res[kid.KEY_KID_STD]:.6f} ({done} samples)")
 
 
 if __name__ == "__main__":
