@@ -11,16 +11,25 @@
 //   * the matrix pipe is no longer the bound, the data path is.  The f32 kernel's stages are as long as a global load takes
 //     (every barrier of a __syncthreads also drains vmcnt), which the 2048-cycle f32 MFMA phase used to cover; a 768-cycle bf16
 //     phase does not.  So the roles are split (512 threads, one workgroup per CU):
-//       - waves 4-7 PRODUCE the A operand: thread = (tile, 16-byte channel quad); the loads of a stage (2 rows x 4 pixels, raw
-//         buffer loads, range check = zero padding) are issued FOUR stages ahead into one of four register sets -- these waves hold
-//         no accumulators, so they have the registers for it -- then y-combined and B^T-transformed in f32 exactly as before, split
-//         into three bf16 terms (and / sub / and / sub per element, v_perm packing) and written to LDS (twelve ds_write_b64);
-//       - waves 0-3 CONSUME: 32 tiles x 32 couts each, six MFMAs per ex plane and stage.  Stages are ordered K block (4 chunks) >
-//         ey > chunk: inside a (block, ey) group the accumulators run on (<= 24 matrix adds each, the first from C = 0), at its
+//       - waves 4-7 PRODUCE the A operand: thread = (tile, 16-byte channel quad); one register set per chunk of a K block holds
+//         two rows of the tile's 4 x 4 patch (4 pixels each, raw buffer loads, range check = zero padding) -- these waves hold no
+//         accumulators, so they have the registers for it.  A pass ey y-combines the two rows (r0 - r2, r1 + r2, r2 - r1, r1 - r3),
+//         B^T-transforms in f32 exactly as before, splits into three bf16 terms (and / sub / and / sub per element, v_perm
+//         packing) and writes to LDS (twelve ds_write_b64).  In whole K blocks every patch row is fetched ONCE per chunk: (r0, r2)
+//         before pass 0, r1 over r0 after pass 0, nothing after pass 1, r3 over r2 after pass 2, the next block's (r0, r2) after
+//         pass 3 -- four row loads (16 buffer_load_dwordx4) per chunk and tile, each one block pass (KB stages) ahead of its
+//         first use.  A partial last block, the fused up-sampling (three passes; r1 and r2 are one source row) and the REUSE = 0
+//         instantiations (adm_wino2d_x6_row_reuse(0): the A/B switch, bit-identical results) fetch the two rows of every stage
+//         KB stages ahead instead: eight row loads per chunk, r1 and r2 three times each.  Measured against the kernel without the
+//         reuse (B = 128): -5..9 % on the 64-cout fp16 form, -1..2 % on the bf16 form at 32 x 32, within +-3 % on the 96- and
+//         128-cout forms, whose consumer waves are the critical path (their producers wait at the barrier for more than half
+//         of a stage); DESIGN.md section 4;
+//       - waves 0-3 CONSUME: 32 tiles x 32 couts each, six MFMAs per ex plane and stage.  Stages are ordered K block (KB chunks:
+//         4 in the 64-cout forms, 3 in the 96- and 128-cout forms = their producer register sets) > ey > chunk: inside a
+//         (block, ey) group the accumulators run on (<= 6 KB matrix adds each, the first from C = 0), at its
 //         end the x / y output transforms are applied and the result is added to the output rows held in registers with f32 adds
 //         -- the long-running sums see rounded f32 adds, not truncating matrix adds: measured against fp64 the error is at or
-//         below the f32 MFMA kernel's (tests/test_hip_ops.py::test_conv_x6_error_vs_fp64).  The four passes over a block also
-//         re-read the input rows 4 stages apart (L2 hits) instead of a whole Cin pass apart.
+//         below the f32 MFMA kernel's (tests/test_hip_ops.py::test_conv_x6_error_vs_fp64).
 //         These waves also issue the weight DMA (their only global accesses: the explicit vmcnt wait before a barrier
 //         never touches the producers' prefetch);
 //       - barriers are s_barrier with LDS-scoped fences (lgkmcnt only): the producers' loads stay in flight across them.
@@ -37,8 +46,8 @@
 #ifndef X6_TL
 #define X6_TL 0      // diagnostic build: per-stage timeline of one consumer and one producer wave of workgroup 0 into p.ws (tools/bench_wino2d_x6.cpp)
 #endif
-#ifndef X6_SHARE
-#define X6_SHARE 0   // 1: patch columns shared between neighbouring tiles by cross-lane moves (measured slower: see the producer)
+#ifndef X6_KB_N
+#define X6_KB_N 4    // chunks per K block of the 64-cout forms (the row reuse is compiled in only at 4 = their producer register sets)
 #endif
 #ifndef X6_ABL
 #define X6_ABL 0     // diagnostic builds (tools/bench_wino2d_x6.cpp): 1 no A global loads, 2 no A transform / split / LDS stores, 4 no B DMA, 8 no MFMAs, 16 no LDS fragment reads
@@ -79,6 +88,7 @@ template <int FMT, int NB = 2> struct X6Fmt {
   static constexpr int DMA_PER_WAVE = 2 * TERMS;     // 4 ex x TERMS images x NB 32-row blocks / CONS consumer waves
   static constexpr int RB = NB > 2 ? 3 : 4;         // weight ring depth (LDS: 2 x 16 + 3 x 32 KB wide; 2 x 16 + 4 x 16 KB fp16, 2 x 24 + 4 x 24 KB bf16)
   static constexpr int PD = NB > 2 ? 3 : 4;         // producer register sets = stages of loads in flight
+  static constexpr int KB = NB > 2 ? 3 : X6_KB_N;   // chunks per K block: one producer register set per chunk of a block (the row reuse needs KB == PD)
 };
 constexpr int X6_RA = 2;                           // A ring depth (the weights' is X6Fmt::RB: RB - 1 stages ahead, a DMA queues behind the producers' loads)
 
@@ -114,18 +124,15 @@ __device__ __forceinline__ void x6_store(const f32x4 (&e)[4], unsigned short* la
   }
 }
 
-// Stage order shared by both roles: K blocks of X6_KB chunks outermost, the four ey passes inside a block, chunks innermost
-// (a stage = one (ey, chunk) pair).  Inside a (block, ey) group the MFMA accumulators run on (<= 24 matrix adds each); at its end
-// they are transformed and added to the output rows with f32 adds.
-#ifndef X6_KB_N
-#define X6_KB_N 4
-#endif
-constexpr int X6_KB = X6_KB_N;
+// Stage order shared by all three roles: K blocks of KB chunks (X6Fmt::KB: 4 for the 64-cout forms, 3 for the 96- and 128-cout
+// forms) outermost, the four ey passes inside a block, chunks innermost (a stage = one (ey, chunk) pair).  Inside a (block, ey)
+// group the MFMA accumulators run on (<= 6 KB matrix adds each); at its end they are transformed and added to the output rows with
+// f32 adds.
 // With the fused nearest x2 up-sampling the patch rows r1 and r2 are the SAME source row, so the pass ey = 2 (r2 - r1) is
 // identically zero and is skipped (three passes per block).
-struct X6Seq {
+template <int KB> struct X6Seq {
   int k0, len, ey, cc, skip2;   // block start (chunk), block length, pass, chunk inside the block, skip pass 2
-  __device__ __forceinline__ void init(int chunks, int up) { k0 = 0; len = min(X6_KB, chunks); ey = 0; cc = 0; skip2 = up; }
+  __device__ __forceinline__ void init(int chunks, int up, int start = 0) { k0 = start; len = min(KB, chunks - start); ey = 0; cc = 0; skip2 = up; }
   __device__ __forceinline__ int chunk() const { return k0 + cc; }
   __device__ __forceinline__ bool done() const { return len <= 0; }
   __device__ __forceinline__ void next(int chunks) {
@@ -133,14 +140,15 @@ struct X6Seq {
       cc = 0;
       ++ey;
       if (skip2 && ey == 2) ++ey;
-      if (ey == 4) { ey = 0; k0 += len; len = min(X6_KB, chunks - k0); }
+      if (ey == 4) { ey = 0; k0 += len; len = min(KB, chunks - k0); }
     }
   }
 };
 
-template <int FMT, int NB>
+template <int FMT, int NB, int REUSE>
 __global__ __launch_bounds__((2 * NB + 4) * 64) void wino2d_x6_kernel(X6P p) {
   using F = X6Fmt<FMT, NB>;
+  using Seq = X6Seq<F::KB>;
   constexpr int TERMS = F::TERMS;
   float sa = 1.f, inv_scale = 1.f;                     // fp16 format: operand scale and the factor that undoes both scales in the epilogue
   if (FMT) { sa = split_scale(adm_amax_read(p.amax_x)); inv_scale = 1.f / (sa * p.wscale); }
@@ -166,14 +174,6 @@ __global__ __launch_bounds__((2 * NB + 4) * 64) void wino2d_x6_kernel(X6P p) {
     const int ptid = wid * 64 + lane;
     const int pl = ptid >> 2, aq = ptid & 3;          // tile, channel quad
     unsigned a_base = 0, colmask = 0, rowmask = 0;
-    // Patch columns shared between neighbouring tiles: tile xp reads input columns 2xp - 1 .. 2xp + 2, so its column 0 is column 2 of
-    // tile xp - 1 and its column 3 is column 1 of tile xp + 1 -- tiles that sit FOUR LANES away in this wave (thread = (tile, quad)).
-    // With X6_SHARE a lane whose neighbour is in its wave and its tile row takes the y-combined value from it with one cross-lane
-    // move per dword instead of asking for the same bytes again: half the activation requests of a stage.  Correct (the parity suite
-    // passes with it) and SLOWER on every shape (tools/bench_wino2d_x6.cpp, 128 x 32 x 32 x 384 -> 384: 0.905 -> 1.106 ms with 64
-    // couts, 0.789 -> 0.865 with 128): the repeated columns were L1 hits, and the eight ds_bpermute per thread and stage are LDS
-    // operations, which do not overlap with the MFMAs of the SIMD's other waves.  Off by default; not for the fused up-sampling.
-    bool take_l = false, take_r = false;
     {
       const int t = mt0 + pl;
       if (t < p.Mt) {
@@ -184,18 +184,95 @@ __global__ __launch_bounds__((2 * NB + 4) * 64) void wino2d_x6_kernel(X6P p) {
                       : (unsigned)((((long)b * p.H + 2 * ty) * p.W + 2 * xp) * p.ldx + aq * 4) * 4u;
         colmask = (xp > 0 ? 1u : 0u) | 6u | (2 * xp + 2 < p.W ? 8u : 0u);
         rowmask = (ty > 0 ? 1u : 0u) | 6u | (2 * ty + 2 < p.H ? 8u : 0u);
-        if (X6_SHARE && !p.up) {
-          take_l = xp > 0 && (pl & 15) != 0;                // (tile pl - 1 = lane - 4 of this wave, same tile row)
-          take_r = xp + 1 < p.Wh && (pl & 15) != 15 && t + 1 < p.Mt;
-          if (take_l) colmask &= ~1u;                       // no request for what the neighbour loads
-          if (take_r) colmask &= ~8u;
-        }
       }
     }
     // rows are 32 bytes; a 16-lane group of a fragment read covers 16 rows at one 16-byte half, i.e. only half of the banks, unless
     // the halves of rows 8-15 (mod 16) are swapped: physical half = logical half ^ ((row >> 3) & 1), for A and B alike
     unsigned short* la = As + pl * X6K + ((((aq >> 1) ^ (pl >> 3)) & 1) << 3) + (aq & 1) * 4;
-    X6Seq ld; ld.init(chunks, p.up);
+    constexpr int D = F::PD;                          // register sets
+    f32x4 dA[D][4], dB[D][4];
+    // y-combination of pass ey: 0: r0 - r2   1: r1 + r2   2: r2 - r1   3: r1 - r3, from the (A, B) halves of a register set
+    auto combine = [&](int ey, const f32x4 (&a)[4], const f32x4 (&b)[4], f32x4 (&e)[4]) {
+      if (ey == 1) {                                  // (wave-uniform, or a constant)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) e[j] = plain_add4(a[j], b[j]);
+      } else if (ey == 2) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) e[j] = plain_sub4(b[j], a[j]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) e[j] = plain_sub4(a[j], b[j]);
+      }
+    };
+    int k_done = 0, t_done = 0;                       // chunks / stages the whole-block loop below has finished
+    if constexpr (REUSE != 0 && F::KB == D) {
+      // ---- whole K blocks, each patch row fetched once.  Set cc holds rows of chunk k0 + cc for the whole block: (r0, r2) when pass 0
+      // starts; r1 replaces r0 in the A half after pass 0 (passes 1 and 2 combine r1 and r2 as they lie); r3 replaces r2 in the B half
+      // after pass 2; the next block's (r0, r2) follow pass 3.  Every load is KB stages ahead of its first use, as in the generic body
+      // below, which asks for two rows per stage (eight per chunk instead of four).  Every load of the loop is unconditional, so
+      // the compiler's vmcnt in front of a stage's transform counts the later loads of the other sets and leaves them in flight.
+      // Offsets: four registers for the columns at patch row 1 (column mask baked in) and four for row 0 (row mask too); rows 2
+      // and 3 and the chunk go into the scalar offset.  Not for the fused up-sampling (three passes, r1 and r2 one source row).
+      constexpr int KB = F::KB;
+      const int nwhole = p.up ? 0 : chunks / KB;
+      if (nwhole > 0) {
+        const int rstride = p.W * p.ldx * 4;          // bytes per input row
+        unsigned v0[4], vc[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const bool cv = (colmask >> j) & 1u;
+          const int cj = (j - 1) * p.ldx * 4;
+          vc[j] = cv ? a_base + (unsigned)cj : OOB;
+          v0[j] = (cv && (rowmask & 1u)) ? a_base + (unsigned)(cj - rstride) : OOB;
+        }
+        const unsigned k3 = (rowmask & 8u) ? 0u : OOB;     // row 3 below the image: out of range
+        auto row = [&](f32x4 (&dst)[4], const unsigned (&vo)[4], unsigned kill, int soff) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (X6_ABL & 1) { dst[j] = f32x4{1.f, 2.f, (float)j, (float)soff}; continue; }
+            dst[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)(vo[j] | kill), soff, 0));
+          }
+        };
+#pragma unroll
+        for (int cc = 0; cc < KB; ++cc) {
+          row(dA[cc], v0, 0u, (c_begin + cc) << 6);   // 16 floats = 64 bytes per chunk
+          row(dB[cc], vc, 0u, ((c_begin + cc) << 6) + rstride);
+          __builtin_amdgcn_sched_barrier(0);          // (in the loop's order: the waits at its head are merged over both ways in)
+        }
+        for (int blk = 0; blk < nwhole; ++blk) {
+          const int cb = (c_begin + blk * KB) << 6;
+          const unsigned nx = blk + 1 < nwhole ? 0u : OOB;      // (uniform) no whole block follows: its rows are not asked for
+#pragma unroll
+          for (int ey = 0; ey < 4; ++ey) {
+#pragma unroll
+            for (int cc = 0; cc < KB; ++cc) {
+              const int k = ey * KB + cc, ts = blk * 4 * KB + k;
+              const bool tl = X6_TL && p.ws && blockIdx.x == 0 && tid == F::CONS * 64 && ts < 48;
+              unsigned long long* TL = reinterpret_cast<unsigned long long*>(p.ws) + 1024 + ts * 4;
+              if (tl) TL[0] = __builtin_readcyclecounter();
+              f32x4 e[4];
+              combine(ey, dA[cc], dB[cc], e);
+              if (FMT) h3_store(e, la + (k & 1) * F::A_STAGE, sa);     // (4 * KB stages per block: an even number, so static slots)
+              else x6_store(e, la + (k & 1) * F::A_STAGE);
+              __builtin_amdgcn_sched_barrier(0);
+              if (tl) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); TL[1] = __builtin_readcyclecounter(); }
+              const int so = cb + (cc << 6);
+              if (ey == 0) row(dA[cc], vc, 0u, so);
+              if (ey == 2) row(dB[cc], vc, k3, so + 2 * rstride);
+              if (ey == 3) { row(dA[cc], v0, nx, so + (KB << 6)); row(dB[cc], vc, nx, so + (KB << 6) + rstride); }
+              __builtin_amdgcn_sched_barrier(0);
+              if (tl) TL[2] = __builtin_readcyclecounter();
+              adm_lds_barrier();
+              if (tl) TL[3] = __builtin_readcyclecounter();
+            }
+          }
+        }
+        k_done = nwhole * KB; t_done = nwhole * 4 * KB;
+      }
+    }
+    // ---- generic body: a partial last block, the fused up-sampling, REUSE = 0.  The loads of a stage (2 rows x 4 pixels) are issued
+    // D stages ahead into register set (stage mod D).
+    Seq ld; ld.init(chunks, p.up, k_done);
     unsigned a_voff[2][4];
     int voff_ey = -1;
     auto set_rows = [&]() {     // pass ey combines input rows (iA, iB): 0: +r0 -r2   1: +r1 +r2   2: -r1 +r2   3: +r1 -r3; past the end: nothing
@@ -215,8 +292,6 @@ __global__ __launch_bounds__((2 * NB + 4) * 64) void wino2d_x6_kernel(X6P p) {
       }
       voff_ey = live ? ey : 4;
     };
-    constexpr int D = F::PD;                          // stages in flight
-    f32x4 dA[D][4], dB[D][4];
     int set_ey[D];
     auto issue = [&](int d) {                         // next stage of the sequence -> register set d
       if (voff_ey != (ld.done() ? 4 : ld.ey)) set_rows();
@@ -232,38 +307,24 @@ __global__ __launch_bounds__((2 * NB + 4) * 64) void wino2d_x6_kernel(X6P p) {
     };
     auto store = [&](int d, int slot) {
       f32x4 e[4];
-      if (set_ey[d] == 1) {                           // wave-uniform
-#pragma unroll
-        for (int j = 0; j < 4; ++j) e[j] = plain_add4(dA[d][j], dB[d][j]);
-      } else if (set_ey[d] == 2) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) e[j] = plain_sub4(dB[d][j], dA[d][j]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) e[j] = plain_sub4(dA[d][j], dB[d][j]);
-      }
-      if (X6_SHARE && !p.up) {                          // (uniform) every lane takes part in the moves
-        f32x4 el, er;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { el[i] = __shfl_up(e[2][i], 4, 64); er[i] = __shfl_down(e[1][i], 4, 64); }
-        if (take_l) e[0] = el;
-        if (take_r) e[3] = er;
-      }
+      combine(set_ey[d], dA[d], dB[d], e);
       if (FMT) h3_store(e, la + slot * F::A_STAGE, sa);
       else x6_store(e, la + slot * F::A_STAGE);
     };
+    const int S_gen = S - t_done;                     // (even, like t_done: slots stay static)
+    if (S_gen <= 0) return;
 #pragma unroll
     for (int d = 0; d < D; ++d) issue(d);
     __builtin_amdgcn_sched_barrier(0);
     // barrier t separates "A(t) written" from compute(t); A(t) lives in slot t & 1; set t % D is refilled with stage t + D
     constexpr int TRIP = (D & 1) ? 2 * D : D;         // stages per trip: static register sets AND static slots
-    for (int t = 0; t < S; t += TRIP) {
+    for (int t = 0; t < S_gen; t += TRIP) {
 #pragma unroll
       for (int k = 0; k < TRIP; ++k) {
         const int d = k % D;
-        if (t + k < S) {                              // (uniform; S is even, a multiple of 4 without the up-sampling)
-          const bool tl = X6_TL && p.ws && blockIdx.x == 0 && tid == F::CONS * 64 && t + k < 48;
-          unsigned long long* TL = reinterpret_cast<unsigned long long*>(p.ws) + 1024 + (t + k) * 4;
+        if (t + k < S_gen) {                          // (uniform; S_gen is even, a multiple of 4 without the up-sampling)
+          const bool tl = X6_TL && p.ws && blockIdx.x == 0 && tid == F::CONS * 64 && t_done + t + k < 48;
+          unsigned long long* TL = reinterpret_cast<unsigned long long*>(p.ws) + 1024 + (t_done + t + k) * 4;
           if (tl) TL[0] = __builtin_readcyclecounter();
           store(d, k & 1);
           __builtin_amdgcn_sched_barrier(0);
@@ -301,7 +362,7 @@ __global__ __launch_bounds__((2 * NB + 4) * 64) void wino2d_x6_kernel(X6P p) {
     const int half = (lane ^ (row >> 3)) & 1;           // logical half stored at physical half (lane & 1)
     b_voff[i] = (n < p.wrows) ? (unsigned)((((long)pt * p.wrows + n) * 16 + half * 8) * 2) : OOB;
   }
-  X6Seq lb; lb.init(chunks, p.up);
+  Seq lb; lb.init(chunks, p.up);
   int ld_slot = 0;
   auto issue_b = [&]() {                              // weights of the next stage of the sequence -> next ring slot
     const int kb = ((lb.ey * (p.Cin >> 4) + c_begin + lb.chunk()) * (4 * TERMS) * p.wrows) << 5;   // (ey, chunk) block of twelve [ex][term] images of wrows x 32 bytes
@@ -327,7 +388,7 @@ __global__ __launch_bounds__((2 * NB + 4) * 64) void wino2d_x6_kernel(X6P p) {
   const int b_foff = (wn * 32 + lr) * X6K + ((lh ^ (lr >> 3)) & 1) * 8;
   const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
-  X6Seq cs; cs.init(chunks, p.up);
+  Seq cs; cs.init(chunks, p.up);
   int slot_b = 0;
 #pragma unroll
   for (int i = 0; i < F::RB - 1; ++i) issue_b();
@@ -572,6 +633,24 @@ extern "C" int adm_split2_f16(const float* src, void* dst, int rows, int cols, f
 // wrows x Cin).
 static int g_h3_wide = -1;      // -1: chosen per launch, 0: never, 1: whenever the launch qualifies (fp16 format, no split-K)
 extern "C" int adm_wino2d_h3_wide(int v) { const int old = g_h3_wide; g_h3_wide = v; return old; }
+static int g_row_reuse = 1;     // 1: whole K blocks fetch each patch row once (REUSE = 1 instantiations), 0: two rows per stage everywhere
+extern "C" int adm_wino2d_x6_row_reuse(int v) { const int old = g_row_reuse; if (v >= 0) g_row_reuse = v ? 1 : 0; return old; }
+
+// one form of the kernel: both instantiations (row reuse on / off) get their LDS size once, the switch picks one per launch
+template <int FMT, int NB> static int x6_launch_form(const X6P& p, unsigned gx, unsigned gy, hipStream_t stream) {
+  using F = X6Fmt<FMT, NB>;
+  constexpr int smem = (X6_RA * F::A_STAGE + F::RB * F::B_STAGE) * (int)sizeof(unsigned short);
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wino2d_x6_kernel<FMT, NB, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&wino2d_x6_kernel<FMT, NB, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
+      return ADM_ELAUNCH;
+    attr_set = true;
+  }
+  if (g_row_reuse) hipLaunchKernelGGL((wino2d_x6_kernel<FMT, NB, 1>), dim3(gx, gy), dim3(F::THREADS), smem, stream, p);
+  else hipLaunchKernelGGL((wino2d_x6_kernel<FMT, NB, 0>), dim3(gx, gy), dim3(F::THREADS), smem, stream, p);
+  return ADM_OK;
+}
 
 static int wino2d_x6_launch(const float* x, const void* wq6, const float* bias, const float* res, float* y, float* ws, long ws_floats,
                             int B, int H, int W, int Cin, int ldx, int N, int wrows, int ldy, int ldr, int up, hipStream_t stream,
@@ -602,25 +681,15 @@ static int wino2d_x6_launch(const float* x, const void* wq6, const float* bias, 
     p.splitk = (chunks + p.chunks_per_split - 1) / p.chunks_per_split;
     p.ws = ws;
   }
-  constexpr int smem0 = (X6_RA * X6Fmt<0>::A_STAGE + X6Fmt<0>::RB * X6Fmt<0>::B_STAGE) * (int)sizeof(unsigned short);
-  constexpr int smem1 = (X6_RA * X6Fmt<1>::A_STAGE + X6Fmt<1>::RB * X6Fmt<1>::B_STAGE) * (int)sizeof(unsigned short);
-  constexpr int smemw = (X6_RA * X6Fmt<1, 4>::A_STAGE + X6Fmt<1, 4>::RB * X6Fmt<1, 4>::B_STAGE) * (int)sizeof(unsigned short);
-  constexpr int smem3 = (X6_RA * X6Fmt<1, 3>::A_STAGE + X6Fmt<1, 3>::RB * X6Fmt<1, 3>::B_STAGE) * (int)sizeof(unsigned short);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wino2d_x6_kernel<0, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, smem0) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&wino2d_x6_kernel<1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, smem1) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&wino2d_x6_kernel<1, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, smemw) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&wino2d_x6_kernel<1, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, smem3) != hipSuccess)
-      return ADM_ELAUNCH;
-    attr_set = true;
-  }
   // 64, 96 or 128 couts per workgroup (four, six, eight consumer waves).  What a CU fetches per stage bounds all three forms: 32 KB of
   // activations + 16 / 24 / 32 KB of weights, 24 B/clk at the measured stage times against the ~30 B/clk a CU gets out of its L2; one
   // workgroup per CU, so a launch takes (rounds of 256 workgroups) x (bytes per stage) -- the 96 form priced a little above its bytes
   // (its six consumer waves load two SIMDs more than the others).  This model orders every shape of tools/bench_wino2d_x6.cpp
   // correctly (B = 128, ms for 64 / 96 / 128 couts: 32x32 384->384 0.91 / 0.90 / 0.81, 192->192 0.27 / 0.26 / 0.29, 576->192
   // 0.72 / 0.60 / 0.65, 192->576 0.75 / 0.63 / 0.59; 16x16 384->384 0.26 / 0.20 / 0.22; 8x8 384->384 0.083 / 0.100 / 0.108).
+  // The table was fitted before the row reuse (16 instead of 32 KB of activations per stage since); it was not re-fitted, and it
+  // still orders those shapes correctly (0.84 / 0.78 / 0.68, 0.25 / 0.22 / 0.25, 0.65 / 0.60 / 0.66, 0.67 / 0.61 / 0.58;
+  // 0.23 / 0.20 / 0.22; 0.078 / 0.097 / 0.107).
   int form = 2;
   if (h3 && p.splitk == 1 && g_h3_wide != 0 && N > X6N) {
     if (g_h3_wide == 1) form = 4;
@@ -634,18 +703,19 @@ static int wino2d_x6_launch(const float* x, const void* wq6, const float* bias, 
       }
     }
   }
-  const bool three = form == 3, wide = form == 4;
-  if (three) {
+  int rc;
+  if (form == 3) {
     p.tilesN = adm_cdiv(N, X6Fmt<1, 3>::NT);
-    hipLaunchKernelGGL((wino2d_x6_kernel<1, 3>), dim3((unsigned)(mtiles * p.tilesN), 1), dim3(X6Fmt<1, 3>::THREADS), smem3, stream, p);
-  } else if (wide) {
+    rc = x6_launch_form<1, 3>(p, (unsigned)(mtiles * p.tilesN), 1, stream);
+  } else if (form == 4) {
     p.tilesN = adm_cdiv(N, X6Fmt<1, 4>::NT);
-    hipLaunchKernelGGL((wino2d_x6_kernel<1, 4>), dim3((unsigned)(mtiles * p.tilesN), 1), dim3(X6Fmt<1, 4>::THREADS), smemw, stream, p);
+    rc = x6_launch_form<1, 4>(p, (unsigned)(mtiles * p.tilesN), 1, stream);
   } else if (h3) {
-    hipLaunchKernelGGL((wino2d_x6_kernel<1, 2>), dim3((unsigned)(mtiles * p.tilesN), p.splitk), dim3(512), smem1, stream, p);
+    rc = x6_launch_form<1, 2>(p, (unsigned)(mtiles * p.tilesN), (unsigned)p.splitk, stream);
   } else {
-    hipLaunchKernelGGL((wino2d_x6_kernel<0, 2>), dim3((unsigned)(mtiles * p.tilesN), p.splitk), dim3(512), smem0, stream, p);
+    rc = x6_launch_form<0, 2>(p, (unsigned)(mtiles * p.tilesN), (unsigned)p.splitk, stream);
   }
+  if (rc != ADM_OK) return rc;
   ADM_CHECK_LAUNCH();
   if (p.splitk > 1) return adm_splitk_reduce(ws, bias, res, y, Mt * 4, N, ldy, ldr, p.splitk, stream);
   return ADM_OK;

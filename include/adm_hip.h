@@ -187,6 +187,11 @@ int adm_wino2d_variant(int ws);
 /* form of adm_conv_fwd_wino2d_h3's kernel: -1 (default) chosen per launch, 1 the 128-cout workgroups (eight consumer waves) / 3 the 96-cout
  * workgroups (six) wherever the launch qualifies (no split-K), 0 always 64-cout workgroups; returns the old value */
 int adm_wino2d_h3_wide(int v);
+/* producer of adm_conv_fwd_wino2d_x6 / _h3's kernel: 1 (default) whole K blocks fetch each of the four patch rows of a tile and
+ * 16-channel chunk once and keep it in registers across the four ey passes, 0 every pass fetches its two rows (eight row loads per
+ * chunk).  Both settings run the same arithmetic in the same order: outputs are bit-identical.  Returns the old value; a negative v
+ * only queries. */
+int adm_wino2d_x6_row_reuse(int v);
 /* form of adm_conv_wgrad_x6_h3 / adm_gemm_wgrad_x6_h3's kernel: -1 (default) / 2: 128 couts per workgroup (sixteen waves) where the launch
  * qualifies (more than 64 couts, not the deterministic workspace mode), 1: always 64; returns the old value */
 int adm_wgrad_h3_blocks(int v);

@@ -70,11 +70,19 @@ static void run(int B, int H, int Cin, int N, bool check) {
   hipFree(x); hipFree(w); hipFree(y); hipFree(y2); hipFree(w6);
 }
 int main() {
+  // X6_REUSE=0: every ey pass fetches its two patch rows (adm_wino2d_x6_row_reuse); default: whole K blocks fetch each row once
+  if (getenv("X6_REUSE")) adm_wino2d_x6_row_reuse(atoi(getenv("X6_REUSE")));
+  printf("row reuse %d\n", adm_wino2d_x6_row_reuse(-1));
 #if X6_ABL
   run(128, 32, 384, 384, false);
   return 0;
 #endif
   if (getenv("X6_ONLY")) { run(128, 32, 384, 384, false); return 0; }
+  if (getenv("X6_SHAPES")) {       // the shapes of the form table, timings only
+    run(128, 32, 384, 384, false); run(128, 32, 192, 192, false); run(128, 32, 576, 192, false); run(128, 32, 192, 576, false);
+    run(128, 16, 384, 384, false); run(128, 16, 768, 384, false); run(128, 8, 384, 384, false);
+    return 0;
+  }
   run(2, 8, 32, 64, true);
   run(3, 8, 64, 160, true);
   run(128, 32, 384, 384, true);
