@@ -36,8 +36,10 @@ def dataset_of(data_cfg):
 #   synthetic   whether ``class_name: synthetic`` + ``synthetic_of`` selects this entry at sampling time
 #   depth       the prediction is a depth fraction: written as a 16-bit png of round(clip(p, 0, 1) * 10000) (8 bits with
 #               ``sampler.depth_png8``) and scored with adm_amd.metrics.depth against 'image' into <save_folder>/depth_metrics.json
-Sampling = namedtuple("Sampling", "form item split_test no_flip one_window psnr gray save_masks synthetic depth",
-                      defaults=(None, None, False, None, True, False, False, False, False))
+#   saliency    the prediction is a saliency map: ``sampler.cal_saliency: True`` (off by default) scores its bytes against the resized
+#               map's bytes with adm_amd.metrics.saliency into <save_folder>/saliency_metrics.json
+Sampling = namedtuple("Sampling", "form item split_test no_flip one_window psnr gray save_masks synthetic depth saliency",
+                      defaults=(None, None, False, None, True, False, False, False, False, False))
 # every data section that selects no entry below: the super-resolution items of sample_cond_ldm.CondStream
 SR_SAMPLING = Sampling("slide_x4")
 
@@ -50,7 +52,8 @@ DATASETS = {
         no_flip=True, one_window="in-painting", save_masks=True)),
     DUTS_CLASSES[0]: Dataset(DUTSBatchStream, DUTSMapStream, Sampling(
         "slide", lambda s, k, b: (b["ori_size"][0], b["img_name"][0][:-4] + ".png"),          # reference :215-216: the photo's name, as png
-        split_test="sampling ddm.data.DUTSDataset needs data.split: test (DUTS-TE, in order, unflipped)", gray=True)),
+        split_test="sampling ddm.data.DUTSDataset needs data.split: test (DUTS-TE, in order, unflipped)", gray=True,
+        saliency=True)),
     SKETCH_CLASSES[0]: Dataset(SketchBatchStream, SketchPhotoStream, Sampling(
         "window", lambda s, k, b: (b["ori_size"][0], b["img_name"][0]),          # the sketch's file name (= the photo's)
         split_test="sampling ddm.data.SketchDataset needs data.split: test (GT/val + Sketch/val, in order, unflipped)",

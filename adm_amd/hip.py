@@ -208,6 +208,7 @@ _SIGS = {
     "adm_kid_sums_tile": [I],
     "adm_kid_sums_blocks": [I],
     "adm_kid_sums": [P, I, P, I, I, P, P, I, I, I, D, D, P, P, P],
+    "adm_saliency_tables": [P, I, P, P, P, I, I, I, P],
 }
 EXPORTS = tuple(_SIGS)
 

@@ -990,6 +990,25 @@ long adm_kid_sums_blocks(int m);
 int adm_kid_sums(const float* f1, int n1, const float* f2, int n2, int D, const int* idx1, const int* idx2, int S, int m, int degree,
                  double gamma, double coef0, double* sums, double* partial, hipStream_t stream);
 
+/* ================================================================================================
+ * Saliency score (csrc/saliency_metrics.hip): the integer tables behind MAE, F-, E- and S-measure, in one launch.
+ * ================================================================================================ */
+
+/* pred [B][H][W] uint8, or float32 with pred_is_f32 != 0 (quantised as rintf(fminf(fmaxf(p, 0), 1) * 255), ties to even, NaN -> 0:
+ * the bytes of the samplers' 8-bit PNGs); map [B][H][W] uint8, foreground g = [map > 128].  Per image:
+ *   head   [B][5]         int64 = { nF, sum x g, sum y g, cx, cy }, x / y 0-based; cx = X + 1 with X = (2 sum x g + nF) / (2 nF) in
+ *                                 integers (round half up), X = W / 2 when nF = 0; cy likewise from y and H: 1 <= cx <= W, 1 <= cy <= H
+ *   tables [B][4][2][256] int64 = the number of pixels with prediction byte v and class c = g in quadrant q = 2 [y >= cy] + [x >= cx]
+ * One workgroup per image: an integer reduction over the map, then a 4 x 2 x 256 uint32 histogram in LDS (LDS integer atomics, one per
+ * run of equal keys), stored widened.  Nothing passes between workgroups and no float is added: the same integers every run, equal to
+ * a bincount.  Both outputs are overwritten whole.  Images need no alignment (image k starts at byte k H W); 16-byte loads are used
+ * where the addresses allow.  ADM_EINVAL, without launching: a null pointer, B outside 1 .. 65535, H or W < 1, H W >
+ * ADM_SALIENCY_MAX_PIXELS, a float32 pred off a 4-byte or an output off an 8-byte boundary. */
+#define ADM_SALIENCY_BINS 2048
+#define ADM_SALIENCY_MAX_PIXELS (1L << 24)
+int adm_saliency_tables(const void* pred, int pred_is_f32, const uint8_t* map, int64_t* tables, int64_t* head, int B, int H, int W,
+                        hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,9 @@ With ``data.class_name: ddm.data.DUTSDataset`` and ``split: test`` (saliency, co
 condition is the photo resized to the model's resolution and the windows run at the output's own scale (the reference's
 ``slide_sample``, :220-283: ``slide_sample_sr`` with ``scale=1``); ``sampler.out_channels`` defaults to 1, ``crop_size`` / ``stride`` to
 ``image_size``; each one-channel prediction is written as a mode-L png under the photo's name, and the PSNR is against the resized map.
+``sampler.cal_saliency: True`` (off by default; ``sampler.saliency_normalize``, default True) also scores the prediction's bytes against
+the resized map's bytes with adm_amd.metrics.saliency (MAE, F-, S- and E-measure): printed at the end and written to
+``<save_folder>/saliency_metrics.json``; on any other data set the key raises.
 
 With ``data.class_name: ddm.data.SketchDataset`` and ``split: test`` (sketch-to-image,
 configs/sketch2img/sketchcoco_cond_ddm_const_ldm_sample.yaml) the condition is the ONE-channel sketch resized to ``image_size`` and the
@@ -206,20 +209,22 @@ class DatasetCondStream:
     training batches (``cond_stream`` with injected draws), never flipped.  The entry says whether ``split: test`` is required,
     and how 'ori_size' and 'img_name' read (``item``); an item without a file name is numbered."""
 
-    def __init__(self, entry, data_cfg, n, image_size, device, seed):
+    def __init__(self, entry, data_cfg, n, image_size, device, seed, want_u8=False):
+        """`want_u8`: the items also carry the planes' bytes ('image_u8', 'cond_u8'); asked for by a saliency-scoring run only."""
         sm = entry.sampling
         if sm.split_test and (data_cfg.get("split") or "train") != "test":
             raise ValueError(sm.split_test)
         if sm.no_flip:          # the reference's test transform has no flip (ddm/data.py:377-379)
             data_cfg = dict(data_cfg, augment_horizontal_flip=False)
         self.n, self.item = n, sm.item
+        self.extra = {"want_u8": True} if want_u8 else {}
         self.stream = entry.cond_stream(data_cfg, 1, image_size, device, seed)
 
     def __iter__(self):
         s = self.stream
         for i in range(self.n):
             k = i % s.pool.n
-            batch = s.next_batch(idx=[k], flip=[0])
+            batch = s.next_batch(idx=[k], flip=[0], **self.extra)
             batch["ori_size"], name = self.item(s, k, batch)
             batch["img_name"] = name or f"{i: 010d}.png"
             yield batch
@@ -275,6 +280,30 @@ def save_depth_prediction(img, folder, img_name, world, index):
     name = img_name if world == 1 else f"{index: 010d}.png"
     write_depth_png(os.path.join(folder, name), units)
     return name
+
+
+def saliency_scorer(data_cfg, s):
+    """The SaliencyScore of ``sampler.cal_saliency: True`` (``sampler.saliency_normalize``, default True), or None without the key.
+    The key on a data set whose ``sampling`` entry is not a saliency one raises."""
+    if not bool(s.get("cal_saliency", False)):
+        return None
+    key = sampling_dataset(data_cfg)
+    if key is None or not DATASETS[key].sampling.saliency:
+        raise ValueError(f"sampler.cal_saliency: True scores saliency maps, but data.class_name {(data_cfg or {}).get('class_name')!r} "
+                         "has none: only ddm.data.DUTSDataset is scored (drop the key)")
+    from adm_amd.metrics.saliency import SaliencyScore
+    return SaliencyScore(bool(s.get("saliency_normalize", True)))
+
+
+def report_saliency(score, out_dir, world, rank):
+    """Prints the eight values and writes <out_dir>/saliency_metrics.json (several ranks: saliency_metrics_rank{r}.json)."""
+    import json
+    from adm_amd.metrics.saliency import KEYS
+    res = score.result()
+    print(f"rank {rank}: saliency score over {res['images']} images: " + " ".join(f"{k}={res[k]:.4f}" for k in KEYS))
+    with open(os.path.join(out_dir, "saliency_metrics.json" if world == 1 else f"saliency_metrics_rank{rank}.json"), "w") as f:
+        json.dump(res, f)
+    return res
 
 
 def window_sampler(ldm, scale):
@@ -337,6 +366,7 @@ def main():
     n_total = int(s.sample_num) if args.max_images is None else min(int(s.sample_num), args.max_images)
     per_rank = n_total // world
     key = sampling_dataset(cfg.data)
+    saliency_score = saliency_scorer(cfg.data, s)
     if key is None:
         sm = SR_SAMPLING
         stream = CondStream(cfg.data, per_rank, device, seed=2000 + rank)
@@ -344,7 +374,7 @@ def main():
     else:
         sm = DATASETS[key].sampling
         size = tuple(cfg.data.get("image_size") or mc.image_size)
-        stream = DatasetCondStream(DATASETS[key], cfg.data, per_rank, size, device, seed=2000 + rank)
+        stream = DatasetCondStream(DATASETS[key], cfg.data, per_rank, size, device, seed=2000 + rank, want_u8=saliency_score is not None)
         # The reference's in-painting and saliency sample YAMLs have neither key, and its own driver would fail on them
         # (cfg.sampler.crop_size, :190): they default to one window, the image at model resolution.
         crop = tuple(s.get("crop_size") or size)
@@ -366,6 +396,8 @@ def main():
             psnr += float(-10.0 * torch.log10(torch.mean((pred - image[:, :, :pred.shape[2], :pred.shape[3]]) ** 2)))
         if depth_score is not None:          # on the device; the sums are copied to the host once, at the end
             depth_score.add(pred.to(torch.float32).contiguous(), ((batch["image"] + 1) * 0.5).contiguous())
+        if saliency_score is not None:          # the bytes the png below holds against the resized map's bytes; tables stay on the device
+            saliency_score.add(pred[:, :1].to(torch.float32).contiguous(), batch["image_u8"])
         if sm.depth and not bool(s.get("depth_png8", False)):
             name = save_depth_prediction(pred[0], out_dir, batch["img_name"], world, rank * per_rank + done)
         else:
@@ -384,6 +416,8 @@ def main():
               + " ".join(f"{k}={res[k]:.4f}" for k in KEYS))
         with open(os.path.join(out_dir, "depth_metrics.json" if world == 1 else f"depth_metrics_rank{rank}.json"), "w") as f:
             json.dump(res, f)
+    if saliency_score is not None:
+        report_saliency(saliency_score, out_dir, world, rank)
 
 
 if __name__ == "__main__":
