@@ -326,22 +326,52 @@ int launch_attn(int which, const float* qkv, const float* out, const float* dout
   return ADM_OK;
 }
 
+// The form a sequence length runs on (the one copy of the rule: dispatch_attn and both entry points of attention_h3.hip choose their
+// instantiation from what this answers).  form = (waves per workgroup, rows per LDS fill, grid.y, chunked).
+int attn_form(int family, int L, int (&form)[4]) {
+  if (L <= 0) return ADM_EINVAL;
+  if (family == 0) {                                    // attention.hip: L <= 32 or a multiple of 32
+    if (L > 65536 || (L > 32 && (L % 32) != 0)) return ADM_EINVAL;
+    const int nkt = L > 256 ? 8 : (L + 31) / 32;        // longer sequences: 256-row chunks, flash-style
+    form[0] = nkt; form[1] = nkt * 32; form[2] = (L + nkt * 32 - 1) / (nkt * 32); form[3] = form[2] > 1;
+    return ADM_OK;
+  }
+  if (family != 1 && family != 2) return ADM_EINVAL;    // attention_h3.hip: {32, 64, 128, 256} or a multiple of 256
+  const bool chunked = L > 256;
+  if (chunked ? (L % 256 != 0 || L > 16384) : (L != 32 && L != 64 && L != 128 && L != 256)) return ADM_EINVAL;
+  const int nw = chunked ? 8 : L / 32;
+  form[0] = nw; form[1] = family == 1 ? nw * 32 : (nw >= 4 ? 128 : nw * 32); form[2] = chunked ? L / 256 : 1; form[3] = chunked;
+  return ADM_OK;
+}
+
 int dispatch_attn(int which, const float* qkv, const float* out, const float* dout, float* o_out, float* lse,
                   float* dqkv, float* delta, int B, int L, int heads, hipStream_t st, float* amax = nullptr) {
-  if (!qkv || B <= 0 || heads <= 0 || L <= 0 || L > 65536) return ADM_EINVAL;
-  if (L > 32 && (L % 32) != 0) return ADM_EINVAL;
+  int form[4];
+  if (!qkv || B <= 0 || heads <= 0 || attn_form(0, L, form) != ADM_OK) return ADM_EINVAL;
   if ((uintptr_t)qkv & 15) return ADM_EINVAL;
-  const int nkt = L > 256 ? 8 : (L + 31) / 32;        // longer sequences: 256-row chunks, flash-style
-  switch (nkt) {
+  switch (form[0]) {
     case 1: return launch_attn<1>(which, qkv, out, dout, o_out, lse, dqkv, delta, B, L, heads, st, amax);
     case 2: return launch_attn<2>(which, qkv, out, dout, o_out, lse, dqkv, delta, B, L, heads, st, amax);
+    case 3: return launch_attn<3>(which, qkv, out, dout, o_out, lse, dqkv, delta, B, L, heads, st, amax);
     case 4: return launch_attn<4>(which, qkv, out, dout, o_out, lse, dqkv, delta, B, L, heads, st, amax);
+    case 5: return launch_attn<5>(which, qkv, out, dout, o_out, lse, dqkv, delta, B, L, heads, st, amax);
+    case 6: return launch_attn<6>(which, qkv, out, dout, o_out, lse, dqkv, delta, B, L, heads, st, amax);
+    case 7: return launch_attn<7>(which, qkv, out, dout, o_out, lse, dqkv, delta, B, L, heads, st, amax);
     case 8: return launch_attn<8>(which, qkv, out, dout, o_out, lse, dqkv, delta, B, L, heads, st, amax);
     default: return ADM_EINVAL;
   }
 }
 
 }  // namespace
+
+extern "C" int adm_attn_form(int family, int L, int* out) {
+  int form[4];
+  if (!out) return ADM_EINVAL;
+  const int rc = attn_form(family, L, form);
+  if (rc == ADM_OK)
+    for (int i = 0; i < 4; ++i) out[i] = form[i];
+  return rc;
+}
 
 extern "C" int adm_attn_fwd(const float* qkv, float* out, float* lse, int B, int L, int heads, hipStream_t stream) {
   if (!out) return ADM_EINVAL;

@@ -451,29 +451,29 @@ extern "C" int adm_attn_bwd_h3(const float* qkv, const float* out, const float* 
                                const float* amax_qkv, const float* amax_dout, float* amax_dqkv, int B, int L, int heads, hipStream_t stream) {
   if (!qkv || !out || !dout || !lse || !dqkv || !delta || !amax_qkv || !amax_dout || B <= 0 || heads <= 0) return ADM_EINVAL;
   if (((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)dout) & 15) return ADM_EINVAL;
-  switch (L) {
-    case 32: return launch_bwd_h3<1>(qkv, out, dout, lse, dqkv, delta, amax_qkv, amax_dout, amax_dqkv, B, L, heads, stream);
-    case 64: return launch_bwd_h3<2>(qkv, out, dout, lse, dqkv, delta, amax_qkv, amax_dout, amax_dqkv, B, L, heads, stream);
-    case 128: return launch_bwd_h3<4>(qkv, out, dout, lse, dqkv, delta, amax_qkv, amax_dout, amax_dqkv, B, L, heads, stream);
-    case 256: return launch_bwd_h3<8>(qkv, out, dout, lse, dqkv, delta, amax_qkv, amax_dout, amax_dqkv, B, L, heads, stream);
-    default:
-      if (L > 256 && L % 256 == 0 && L <= 16384)
-        return launch_bwd_h3<8>(qkv, out, dout, lse, dqkv, delta, amax_qkv, amax_dout, amax_dqkv, B, L, heads, stream);
-      return ADM_EINVAL;
+  int form[4];                                         // (waves, rows per LDS fill, grid.y, chunked): the chunked form is the 8-wave one
+  if (adm_attn_form(2, L, form) != ADM_OK) return ADM_EINVAL;
+  switch (form[0]) {
+    case 1: return launch_bwd_h3<1>(qkv, out, dout, lse, dqkv, delta, amax_qkv, amax_dout, amax_dqkv, B, L, heads, stream);
+    case 2: return launch_bwd_h3<2>(qkv, out, dout, lse, dqkv, delta, amax_qkv, amax_dout, amax_dqkv, B, L, heads, stream);
+    case 4: return launch_bwd_h3<4>(qkv, out, dout, lse, dqkv, delta, amax_qkv, amax_dout, amax_dqkv, B, L, heads, stream);
+    case 8: return launch_bwd_h3<8>(qkv, out, dout, lse, dqkv, delta, amax_qkv, amax_dout, amax_dqkv, B, L, heads, stream);
+    default: return ADM_EINVAL;
   }
 }
 
 // adm_attn_fwd on the fp16 split format: amax = bound vector (include/adm_hip.h) of |qkv| (the qkv conv's epilogue wrote it).  L in
-// {32, 64, 128, 256} only (ADM_EINVAL otherwise: the caller stays on adm_attn_fwd); same outputs to f32 rounding.
+// {32, 64, 128, 256} or a multiple of 256 (ADM_EINVAL otherwise: the caller stays on adm_attn_fwd); same outputs to f32 rounding.
 extern "C" int adm_attn_fwd_h3(const float* qkv, float* out, float* lse, const float* amax, int B, int L, int heads, hipStream_t stream) {
   if (!qkv || !out || !amax || B <= 0 || heads <= 0 || ((uintptr_t)qkv & 15)) return ADM_EINVAL;
-  switch (L) {
-    case 32: return launch_fwd_h3<1, false>(qkv, out, lse, amax, B, L, heads, stream);
-    case 64: return launch_fwd_h3<2, false>(qkv, out, lse, amax, B, L, heads, stream);
-    case 128: return launch_fwd_h3<4, false>(qkv, out, lse, amax, B, L, heads, stream);
-    case 256: return launch_fwd_h3<8, false>(qkv, out, lse, amax, B, L, heads, stream);
-    default:
-      if (L > 256 && L % 256 == 0 && L <= 16384) return launch_fwd_h3<8, true>(qkv, out, lse, amax, B, L, heads, stream);
-      return ADM_EINVAL;
+  int form[4];                                         // (waves, rows per LDS fill, grid.y, chunked)
+  if (adm_attn_form(1, L, form) != ADM_OK) return ADM_EINVAL;
+  if (form[3]) return launch_fwd_h3<8, true>(qkv, out, lse, amax, B, L, heads, stream);
+  switch (form[0]) {
+    case 1: return launch_fwd_h3<1, false>(qkv, out, lse, amax, B, L, heads, stream);
+    case 2: return launch_fwd_h3<2, false>(qkv, out, lse, amax, B, L, heads, stream);
+    case 4: return launch_fwd_h3<4, false>(qkv, out, lse, amax, B, L, heads, stream);
+    case 8: return launch_fwd_h3<8, false>(qkv, out, lse, amax, B, L, heads, stream);
+    default: return ADM_EINVAL;
   }
 }

@@ -395,6 +395,12 @@ int adm_attn_bwd_h3(const float* qkv, const float* out, const float* dout, const
 /* ... that also raises the bound vector amax to max |dqkv| (the qkv conv's gradients then run on the fp16 format) */
 int adm_attn_bwd_amax(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, float* delta, float* amax,
                       int B, int L, int heads, hipStream_t stream);
+/* Host query of the form a sequence length runs on (no launch; the entry points above choose their kernel through the same
+ * function).  family 0 = adm_attn_fwd / adm_attn_bwd / adm_attn_bwd_amax, 1 = adm_attn_fwd_h3, 2 = adm_attn_bwd_h3.  out[0] = waves
+ * per workgroup (32 queries or keys each), out[1] = rows of the other side per LDS fill, out[2] = grid.y (workgroups per (b, head)),
+ * out[3] = 1 for the chunked form (L > 256: a workgroup owns one of grid.y 256-row chunks and passes all chunks of the other side
+ * through LDS), else 0.  ADM_EINVAL for an L the family refuses. */
+int adm_attn_form(int family, int L, int* out);
 
 /* ---------------- resampling / layout / elementwise ------------------------------------------ */
 
