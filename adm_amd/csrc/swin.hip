@@ -224,17 +224,39 @@ __global__ __launch_bounds__(LN_ROWS * 64) void ln_affine_kernel(const float* __
   }
 }
 
-// NQ = float4 per lane, the smallest of 1, 2, 4, 8 that covers the row: a 128-float row then holds 4 values per lane, not 32 slots
+// NQ = float4 per lane, the smallest of 1, 2, 4, 8 that covers the row: a 128-float row then holds 4 values per lane, not 32 slots.
+// The one place the rule is written: ln_launch and ln_bwd_launch (plain and MERGE, whose row is 4 Cin floats) choose through it.
+// form = (NQ, float4 of the row in its last used trip: 64 when the row fills that trip, fewer when lanes sit past the row's end);
+// the row uses ceil(C / 256) of the NQ trips, the others are empty.  Supported C: 32 <= C <= 2048, C % 4 == 0.
+static int ln_form(int C, int form[2]) {
+  if (C < 32 || C > 64 * LN_MAXQ * 4 || (C & 3)) return ADM_EINVAL;
+  const int C4 = C / 4, trips = (C4 + 63) / 64;
+  form[0] = trips <= 1 ? 1 : trips <= 2 ? 2 : trips <= 4 ? 4 : 8;
+  form[1] = C4 - 64 * (trips - 1);
+  return ADM_OK;
+}
+
+extern "C" int adm_ln_form(int C, int* out) {
+  int form[2];
+  if (!out || ln_form(C, form) != ADM_OK) return ADM_EINVAL;
+  out[0] = form[0]; out[1] = form[1];
+  return ADM_OK;
+}
+
 template <bool MERGE>
-static void ln_launch(const float* x, const float* w, const float* b, float* y, long M, int C, float eps, int H, int W, int Cin,
-                      unsigned blocks, hipStream_t stream) {
-  const int q = (C / 4 + 63) / 64;
+static int ln_launch(const float* x, const float* w, const float* b, float* y, long M, int C, float eps, int H, int W, int Cin,
+                     unsigned blocks, hipStream_t stream) {
+  int form[2];
+  if (ln_form(C, form) != ADM_OK) return ADM_EINVAL;
 #define LN_GO(NQ) hipLaunchKernelGGL((ln_affine_kernel<MERGE, NQ>), dim3(blocks), dim3(LN_ROWS * 64), 0, stream, x, w, b, y, M, C, eps, H, W, Cin)
-  if (q <= 1) LN_GO(1);
-  else if (q <= 2) LN_GO(2);
-  else if (q <= 4) LN_GO(4);
-  else LN_GO(8);
+  switch (form[0]) {
+    case 1: LN_GO(1); break;
+    case 2: LN_GO(2); break;
+    case 4: LN_GO(4); break;
+    default: LN_GO(8); break;
+  }
 #undef LN_GO
+  return ADM_OK;
 }
 
 extern "C" int adm_ln_affine_fwd(const float* x, const float* w, const float* b, float* y, long M, int C, float eps,
@@ -243,7 +265,7 @@ extern "C" int adm_ln_affine_fwd(const float* x, const float* w, const float* b,
   if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)b | (uintptr_t)y) & 15) return ADM_EINVAL;
   const long blocks = (M + LN_ROWS - 1) / LN_ROWS;
   if (blocks > 0x7fffffffL) return ADM_EINVAL;
-  ln_launch<false>(x, w, b, y, M, C, eps, 0, 0, 0, (unsigned)blocks, stream);
+  if (ln_launch<false>(x, w, b, y, M, C, eps, 0, 0, 0, (unsigned)blocks, stream) != ADM_OK) return ADM_EINVAL;
   ADM_CHECK_LAUNCH();
   return ADM_OK;
 }
@@ -255,7 +277,7 @@ extern "C" int adm_swin_merge_ln_fwd(const float* x, const float* w, const float
   const long M = (long)B * ((H + 1) / 2) * ((W + 1) / 2);
   const long blocks = (M + LN_ROWS - 1) / LN_ROWS;
   if (blocks > 0x7fffffffL) return ADM_EINVAL;
-  ln_launch<true>(x, w, b, y, M, 4 * C, eps, H, W, C, (unsigned)blocks, stream);
+  if (ln_launch<true>(x, w, b, y, M, 4 * C, eps, H, W, C, (unsigned)blocks, stream) != ADM_OK) return ADM_EINVAL;
   ADM_CHECK_LAUNCH();
   return ADM_OK;
 }
@@ -663,15 +685,19 @@ __global__ __launch_bounds__(256) void ln_bwd_reduce(const float* __restrict__ p
 }
 
 template <bool MERGE>
-static void ln_bwd_launch(const float* x, const float* w, const float* dy, float* dx, float* part, long M, int C, float eps, int H,
-                          int W, int Cin, unsigned blocks, hipStream_t stream) {
-  const int q = (C / 4 + 63) / 64;
+static int ln_bwd_launch(const float* x, const float* w, const float* dy, float* dx, float* part, long M, int C, float eps, int H,
+                         int W, int Cin, unsigned blocks, hipStream_t stream) {
+  int form[2];
+  if (ln_form(C, form) != ADM_OK) return ADM_EINVAL;
 #define LN_GO(NQ) hipLaunchKernelGGL((ln_affine_bwd_kernel<MERGE, NQ>), dim3(blocks), dim3(LN_ROWS * 64), 0, stream, x, w, dy, dx, part, M, C, eps, H, W, Cin)
-  if (q <= 1) LN_GO(1);
-  else if (q <= 2) LN_GO(2);
-  else if (q <= 4) LN_GO(4);
-  else LN_GO(8);
+  switch (form[0]) {
+    case 1: LN_GO(1); break;
+    case 2: LN_GO(2); break;
+    case 4: LN_GO(4); break;
+    default: LN_GO(8); break;
+  }
 #undef LN_GO
+  return ADM_OK;
 }
 
 extern "C" int adm_ln_affine_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, float* ws,
@@ -679,7 +705,7 @@ extern "C" int adm_ln_affine_bwd(const float* x, const float* w, const float* dy
   if (!x || !w || !dy || !dx || !dw || !db || !ws || M <= 0 || C < 32 || C > 64 * LN_MAXQ * 4 || (C & 3)) return ADM_EINVAL;
   if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)ws) & 15) return ADM_EINVAL;
   const long blocks = ln_bwd_blocks(M);
-  ln_bwd_launch<false>(x, w, dy, dx, ws, M, C, eps, 0, 0, 0, (unsigned)blocks, stream);
+  if (ln_bwd_launch<false>(x, w, dy, dx, ws, M, C, eps, 0, 0, 0, (unsigned)blocks, stream) != ADM_OK) return ADM_EINVAL;
   ADM_CHECK_LAUNCH();
   hipLaunchKernelGGL(ln_bwd_reduce, dim3((unsigned)adm_cdiv(2L * C, 256)), dim3(256), 0, stream, ws, dw, db, blocks * LN_ROWS, C,
                      accumulate);
@@ -694,7 +720,7 @@ extern "C" int adm_swin_merge_ln_bwd(const float* x, const float* w, const float
   if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)ws) & 15) return ADM_EINVAL;
   const long M = (long)B * ((H + 1) / 2) * ((W + 1) / 2);
   const long blocks = ln_bwd_blocks(M);
-  ln_bwd_launch<true>(x, w, dy, dx, ws, M, 4 * C, eps, H, W, C, (unsigned)blocks, stream);
+  if (ln_bwd_launch<true>(x, w, dy, dx, ws, M, 4 * C, eps, H, W, C, (unsigned)blocks, stream) != ADM_OK) return ADM_EINVAL;
   ADM_CHECK_LAUNCH();
   hipLaunchKernelGGL(ln_bwd_reduce, dim3((unsigned)adm_cdiv(8L * C, 256)), dim3(256), 0, stream, ws, dw, db, blocks * LN_ROWS, 4 * C,
                      accumulate);
@@ -883,19 +909,42 @@ static int pe_params(PatchP& p, const float* x, int B, int H, int W, int E) {
   return ADM_OK;
 }
 
+// The one place the lane layout is chosen: PE_DISPATCH and pe_token_groups go through it.  form = (G, Q, E / 4 = float4 per token);
+// G * Q > E / 4 means lanes past the row.  Supported E: E % 32 == 0, 32 <= E <= 512.
+static int pe_form(int E, int form[3]) {
+  if (E < 32 || E > PE_MAXE || (E & 31)) return ADM_EINVAL;
+  form[0] = E <= 32 ? 8 : E <= 64 ? 16 : E <= 128 ? 32 : 64;
+  form[1] = E <= 256 ? 1 : 2;
+  form[2] = E / 4;
+  return ADM_OK;
+}
+
+extern "C" int adm_patch_embed_form(int E, int* out) {
+  int form[3];
+  if (!out || pe_form(E, form) != ADM_OK) return ADM_EINVAL;
+  for (int i = 0; i < 3; ++i) out[i] = form[i];
+  return ADM_OK;
+}
+
 // G lanes per token, Q float4 per lane: 32 -> (8, 1), 64 -> (16, 1), 96 / 128 -> (32, 1), 160 .. 256 -> (64, 1), above -> (64, 2)
-#define PE_DISPATCH(E)                          \
-  do {                                          \
-    if ((E) <= 32) PE_GO(8, 1);                 \
-    else if ((E) <= 64) PE_GO(16, 1);           \
-    else if ((E) <= 128) PE_GO(32, 1);          \
-    else if ((E) <= 256) PE_GO(64, 1);          \
-    else PE_GO(64, 2);                          \
+#define PE_DISPATCH(E)                                           \
+  do {                                                           \
+    int form_[3];                                                \
+    if (pe_form((E), form_) != ADM_OK) return ADM_EINVAL;        \
+    switch (form_[0] * 4 + form_[1]) {                           \
+      case 8 * 4 + 1: PE_GO(8, 1); break;                        \
+      case 16 * 4 + 1: PE_GO(16, 1); break;                      \
+      case 32 * 4 + 1: PE_GO(32, 1); break;                      \
+      case 64 * 4 + 1: PE_GO(64, 1); break;                      \
+      case 64 * 4 + 2: PE_GO(64, 2); break;                      \
+      default: return ADM_EINVAL;                                \
+    }                                                            \
   } while (0)
 
 static long pe_token_groups(long T, int E) {
-  const int G = E <= 32 ? 8 : E <= 64 ? 16 : E <= 128 ? 32 : 64;
-  const int tpw = 64 / G;
+  int form[3];
+  if (pe_form(E, form) != ADM_OK) return 0;
+  const int tpw = 64 / form[0];
   return (T + tpw - 1) / tpw;
 }
 

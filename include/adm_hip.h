@@ -855,8 +855,13 @@ int adm_swin_attn_fwd(const float* qkv, const float* qkv_bias, const float* tabl
 /* nn.LayerNorm(C) with weight and bias over the rows of x [M][C]; 32 <= C <= 2048, C % 4 == 0.  Two passes over the row in
  * registers (mean, then squared deviations). */
 int adm_ln_affine_fwd(const float* x, const float* w, const float* b, float* y, long M, int C, float eps, hipStream_t stream);
+/* The register form the LayerNorm kernels (plain and merged, forward and backward) take for a row of C floats (merged: C = 4 Cin):
+ * out[0] = NQ, the float4 slots per lane (1, 2, 4 or 8; the row uses ceil(C / 256) of them), out[1] = the float4 of the row in its
+ * last used trip over the 64 lanes (64: the trip is whole; fewer: lanes past the row's end).  The function the launches choose
+ * through.  -22 for a C they refuse. */
+int adm_ln_form(int C, int* out);
 /* PatchMerging's gather fused with its LayerNorm(4C): x [B][H][W][C] -> y [B][ceil(H/2)][ceil(W/2)][4C], the 2x2 cell's pixels in
- * the order (0,0), (1,0), (0,1), (1,1) as (dy, dx), zeros past an odd edge; w, b [4C]; C % 4 == 0, C <= 512. */
+ * the order (0,0), (1,0), (0,1), (1,1) as (dy, dx), zeros past an odd edge; w, b [4C]; C % 4 == 0, 8 <= C <= 512. */
 int adm_swin_merge_ln_fwd(const float* x, const float* w, const float* b, float* y, int B, int H, int W, int C, float eps,
                           hipStream_t stream);
 
@@ -896,6 +901,9 @@ int adm_rowscale_add(const float* x, const float* r, const float* s, float* y, i
  * x is read in 16-byte pieces when it is aligned and W % 4 == 0, else by element. */
 int adm_patch_embed_ln_fwd(const float* x, const float* w, const float* cb, const float* gamma, const float* beta, float* y, int B,
                            int H, int W, int E, float eps, hipStream_t stream);
+/* The lane layout the stem kernels (forward and backward) take for a width E: out = (G lanes per token, Q float4 per lane, E / 4
+ * float4 per token); G Q > E / 4 means lanes past the row.  The function the launches choose through.  -22 for an E they refuse. */
+int adm_patch_embed_form(int E, int* out);
 /* Parameter gradients of adm_patch_embed_ln_fwd from x and dy [B][H/4][W/4][E]: dW [E][16], db, dgamma, dbeta [E].  There is no dX.
  * The conv outputs and the token statistics are recomputed from x (the forward saves nothing).  The sums over tokens go through one
  * partial per workgroup in ws and a second kernel that adds them in workgroup order: no float atomics, the same bits every run.

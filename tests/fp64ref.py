@@ -442,6 +442,211 @@ def col2im(col, B, Hin, Win, ks, stride, pad):
     return {"dx": tuple(res)}
 
 
+# ------------------------------------------------------------------------------------------------ the Swin condition encoder's family
+def _ln_rows(x, w, b, eps, dy):
+    """LayerNorm with weight and bias over the last axis of fp64 x: (y, y_mag, xh, rstd) and, given dy, (dx, dx_mag, dw, dw_mag, db,
+    db_mag).  y = xh w + b -> |xh w| + |b|; dx = rstd (g - mean g - xh mean(g xh)), g = dy w -> the same sum over |terms|; dw = sum_rows
+    dy xh, db = sum_rows dy -> sums of |summands|."""
+    C = x.shape[-1]
+    mean = x.mean(dim=-1, keepdim=True)
+    var = (x - mean).square().mean(dim=-1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    xh = (x - mean) * rstd
+    fwd = (xh * w + b, (xh * w).abs() + b.abs(), xh, rstd)
+    if dy is None:
+        return fwd, None
+    g = dy * w
+    m = lambda t: t.mean(dim=-1, keepdim=True)
+    dx = rstd * (g - m(g) - xh * m(g * xh))
+    dxm = rstd * (g.abs() + m(g.abs()) + xh.abs() * m((g * xh).abs()))
+    r = lambda t: t.reshape(-1, C).sum(dim=0)
+    return fwd, (dx, dxm, r(dy * xh), r((dy * xh).abs()), r(dy), r(dy.abs()))
+
+
+def layer_norm_affine(x, w, b, eps=1e-5, dy=None):
+    """{"y"} and, given dy, "dx", "dw", "db" of ops_swin.layer_norm (adm_ln_affine_fwd / _bwd): nn.LayerNorm(C) with weight and bias over
+    the rows of x [..., C], biased variance.  mag as in _ln_rows.  The results keep x's row layout, so a test can take errors() over a
+    class of rows."""
+    x = _d(x)
+    fwd, bwd = _ln_rows(x, _d(w, x), _d(b, x), eps, None if dy is None else _d(dy, x))
+    out = {"y": fwd[:2]}
+    if bwd is not None:
+        out.update(dx=bwd[0:2], dw=bwd[2:4], db=bwd[4:6])
+    return out
+
+
+def merge_index(H, W, Cin, device=None):
+    """The PatchMerging gather as index arithmetic: for output row (oy, ox) and channel c of 4 Cin, quad = c // Cin, ci = c % Cin, the
+    source pixel is (2 oy + (quad & 1), 2 ox + (quad >> 1)) -- quads in the order (0,0), (1,0), (0,1), (1,1) as (dy, dx).  Returns
+    (iy [Ho, 1, 4Cin], ix [1, Wo, 4Cin], ci [4Cin], inside [Ho, Wo, 4Cin])."""
+    Ho, Wo = (H + 1) // 2, (W + 1) // 2
+    c = torch.arange(4 * Cin, device=device)
+    quad, ci = c // Cin, c % Cin
+    iy = 2 * torch.arange(Ho, device=device).reshape(Ho, 1, 1) + (quad & 1).reshape(1, 1, -1)
+    ix = 2 * torch.arange(Wo, device=device).reshape(1, Wo, 1) + (quad >> 1).reshape(1, 1, -1)
+    return iy, ix, ci, (iy < H) & (ix < W)
+
+
+def merge_layer_norm(x, w, b, eps=1e-5, dy=None):
+    """{"y"} and, given dy, "dx", "dw", "db" of ops_swin.merge_layer_norm: x [B, H, W, Cin] -> the 2x2 gather of merge_index (zeros
+    past an odd edge, which count in the mean's divisor 4 Cin) -> LayerNorm(4 Cin).  dx goes back through the same gather: every source
+    pixel has one destination, a position past the edge none.  mag as in _ln_rows."""
+    x = _d(x)
+    B, H, W, Cin = x.shape
+    iy, ix, ci, inside = merge_index(H, W, Cin, x.device)
+    Ho, Wo = iy.shape[0], ix.shape[1]
+    xp = torch.zeros(B, 2 * Ho, 2 * Wo, Cin, dtype=_f64, device=x.device)
+    xp[:, :H, :W] = x
+    g = xp[:, iy, ix, ci]                                          # [B, Ho, Wo, 4 Cin]
+    fwd, bwd = _ln_rows(g, _d(w, x), _d(b, x), eps, None if dy is None else _d(dy, x))
+    out = {"y": fwd[:2]}
+    if bwd is not None:
+        back = []
+        for t in bwd[0:2]:
+            full = torch.zeros_like(xp)
+            full[:, iy, ix, ci] = t
+            back.append(full[:, :H, :W].contiguous())
+        out.update(dx=tuple(back), dw=bwd[2:4], db=bwd[4:6])
+    return out
+
+
+SWIN_WIN, SWIN_HEAD_DIM = 7, 32
+
+
+def window_index(H, W, shift, device=None):
+    """The shifted-window partition as index arithmetic.  shift = (sh, sw); an axis whose padded size is one window takes no shift.
+    Rolled-frame coordinate r = w 7 + t, source coordinate (padded frame) s = (r + shift) mod P, region label along an axis with a shift
+    (r >= P - 7) + (r >= P - shift).  Returns (Y, X [windows, 49] source coordinates of token t = ty 7 + tx of every window (row-major
+    windows), lab [windows, 49] = 3 ly + lx, rel [49, 49] = (dy + 6) 13 + (dx + 6) with (dy, dx) = query - key position, (sh, sw) used)."""
+    Wn = SWIN_WIN
+    Ph, Pw = -(-H // Wn) * Wn, -(-W // Wn) * Wn
+    sh, sw = (shift, shift) if isinstance(shift, int) else shift
+    sh, sw = (sh if Ph > Wn else 0), (sw if Pw > Wn else 0)
+
+    def axis(P, s):
+        r = torch.arange(P, device=device)
+        lab = torch.zeros(P, dtype=torch.long, device=device) if s == 0 else (r >= P - Wn).long() + (r >= P - s).long()
+        return (r + s) % P, lab
+
+    (sy, ly), (sx, lx) = axis(Ph, sh), axis(Pw, sw)
+    nh, nw = Ph // Wn, Pw // Wn
+    rows = lambda t: t.reshape(nh, 1, Wn, 1).expand(nh, nw, Wn, Wn).reshape(nh * nw, Wn * Wn)
+    cols = lambda t: t.reshape(1, nw, 1, Wn).expand(nh, nw, Wn, Wn).reshape(nh * nw, Wn * Wn)
+    p = torch.arange(Wn * Wn, device=device)
+    py, px = p // Wn, p % Wn
+    rel = (py[:, None] - py[None, :] + Wn - 1) * (2 * Wn - 1) + (px[:, None] - px[None, :] + Wn - 1)
+    return rows(sy), cols(sx), rows(ly) * 3 + cols(lx), rel, (sh, sw)
+
+
+def window_attention(qkv, qkv_bias, table, heads, shift, dout=None):
+    """{"out"} and, given dout, "d_qkv", "d_table", "d_qkv_bias" of ops_swin.window_attention (adm_swin_attn_fwd / _bwd): qkv [B, H, W,
+    3C] with the last axis ordered [3][heads][32], qkv_bias [3C], table [169, heads], shift an int or (sh, sw).  Per window and head
+
+        S = 32^-1/2 q k^T + table[rel][head] - 100 [labels differ],  P = softmax(S),  O = P v
+
+    over the 49 tokens of window_index; a token outside H x W is a key / value equal to qkv_bias and is never a query (its dout is 0).
+    dP = dO v^T, dS = P (dP - rowsum(P dP)), dq = 32^-1/2 dS k, dk = 32^-1/2 dS^T q, dv = P^T dO; d_qkv takes them at the real tokens,
+    d_qkv_bias the sums of dk, dv (and dq, which is zero) over the padding tokens, d_table[rel] the sums of dS.
+    mag keeps P (non-negative) and takes every other product on |operands|: out -> P |v|; dP -> |dO| |v|^T; dS -> P (|dP| + rowsum(P
+    |dP|)); dq, dk, dv, d_table and d_qkv_bias -> the same sums over |summands|."""
+    qkv = _d(qkv)
+    dev = qkv.device
+    B, H, W, C3 = qkv.shape
+    C, D, T = C3 // 3, SWIN_HEAD_DIM, SWIN_WIN * SWIN_WIN
+    assert C == heads * D
+    Y, X, lab, rel, _ = window_index(H, W, shift, dev)
+    nW = Y.shape[0]
+    Ph, Pw = int(Y.max()) + 1, int(X.max()) + 1
+    real = ((Y < H) & (X < W)).to(_f64)                                     # [nW, 49]
+    bias = _d(qkv_bias, qkv)
+    full = bias.expand(B, Ph, Pw, C3).clone()
+    full[:, :H, :W] = qkv
+    tok = full[:, Y, X].reshape(B, nW, T, 3, heads, D).permute(3, 0, 1, 4, 2, 5)      # [3][B][nW][heads][49][32]
+    q, k, v = tok[0], tok[1], tok[2]
+    scale = D ** -0.5
+    tb = _d(table, qkv)[rel].permute(2, 0, 1)                               # [heads, 49, 49]
+    mask = (lab[:, :, None] != lab[:, None, :]).to(_f64) * -100.0          # [nW, 49, 49]
+    S = scale * torch.matmul(q, k.transpose(-1, -2)) + tb + mask[:, None]
+    P = torch.softmax(S, dim=-1)
+
+    def to_map(t, ch):          # [B][nW][heads][49][32] per third -> [B, H, W, ch]
+        m = torch.zeros(B, Ph, Pw, ch, dtype=_f64, device=dev)
+        m[:, Y, X] = t
+        return m[:, :H, :W].contiguous()
+
+    tokens = lambda t: t.permute(0, 1, 3, 2, 4).reshape(B, nW, T, C)       # heads next to the channel
+    res = {"out": (to_map(tokens(torch.matmul(P, v)), C), to_map(tokens(torch.matmul(P, v.abs())), C))}
+    if dout is None:
+        return res
+    dfull = torch.zeros(B, Ph, Pw, C, dtype=_f64, device=dev)
+    dfull[:, :H, :W] = _d(dout, qkv)
+    do = dfull[:, Y, X].reshape(B, nW, T, heads, D).permute(0, 1, 3, 2, 4)
+    Tr = lambda t: t.transpose(-1, -2)
+    dP = torch.matmul(do, Tr(v))
+    dS = P * (dP - (P * dP).sum(-1, keepdim=True))
+    dPm = torch.matmul(do.abs(), Tr(v.abs()))
+    dSm = P * (dPm + (P * dPm).sum(-1, keepdim=True))
+    outs = {"d_qkv": [], "d_table": [], "d_qkv_bias": []}
+    for s_, qq, kk, dd in ((dS, q, k, do), (dSm, q.abs(), k.abs(), do.abs())):
+        thirds = torch.cat([tokens(scale * torch.matmul(s_, kk)), tokens(scale * torch.matmul(Tr(s_), qq)),
+                            tokens(torch.matmul(Tr(P), dd))], dim=-1)      # [B, nW, 49, 3C]
+        outs["d_qkv"].append(to_map(thirds, C3))
+        outs["d_qkv_bias"].append((thirds * (1.0 - real)[None, :, :, None]).sum(dim=(0, 1, 2)))
+        dt = torch.zeros(rel.max().item() + 1, heads, dtype=_f64, device=dev)
+        dt.index_add_(0, rel.reshape(-1), s_.sum(dim=(0, 1)).reshape(heads, T * T).t().contiguous())
+        outs["d_table"].append(dt)
+    res.update({n: tuple(v_) for n, v_ in outs.items()})
+    return res
+
+
+def patch_embed_ln(x, w, cb, gamma, beta, eps=1e-5, dy=None):
+    """{"y"} and, given dy, "dW", "db", "dgamma", "dbeta" of ops_swin's fused one-channel stem (adm_patch_embed_ln_fwd / _bwd):
+    x [B, 1, H, W] -> the 4x4 patches p [B, H//4, W//4, 16] (trailing rows / columns unread) -> c = p w^T + cb with w [E, 1, 4, 4]
+    -> LayerNorm over E with gamma, beta.  There is no dx.  mag: c -> |p| |w|^T + |cb|; y = (c - mean c) rstd gamma + beta ->
+    rstd |gamma| (mag c + mean mag c) + |beta|; dgamma = sum dy xh, dbeta = sum dy -> sums of |summands|; dc = rstd (g - mean g - xh
+    mean(g xh)), g = dy gamma -> the sum over |terms|; db = sum_tokens dc, dW = dc^T p -> the same sums over |dc| terms and |p|."""
+    x = _d(x)
+    B, _, H, W = x.shape
+    Ht, Wt = H // 4, W // 4
+    E = w.shape[0]
+    p = x[:, 0, :4 * Ht, :4 * Wt].reshape(B, Ht, 4, Wt, 4).permute(0, 1, 3, 2, 4).reshape(B, Ht, Wt, 16)
+    wm, cbv, ga, be = _d(w, x).reshape(E, 16), _d(cb, x), _d(gamma, x), _d(beta, x)
+    c = torch.matmul(p, wm.t()) + cbv
+    cm = torch.matmul(p.abs(), wm.abs().t()) + cbv.abs()
+    m = lambda t: t.mean(dim=-1, keepdim=True)
+    mean = m(c)
+    rstd = 1.0 / torch.sqrt(m((c - mean).square()) + eps)
+    xh = (c - mean) * rstd
+    out = {"y": (xh * ga + be, rstd * ga.abs() * (cm + m(cm)) + be.abs())}
+    if dy is None:
+        return out
+    d = _d(dy, x)
+    g = d * ga
+    dc = rstd * (g - m(g) - xh * m(g * xh))
+    dcm = rstd * (g.abs() + m(g.abs()) + xh.abs() * m((g * xh).abs()))
+    r = lambda t: t.reshape(-1, E).sum(dim=0)
+    P2 = p.reshape(-1, 16)
+    out["dgamma"] = (r(d * xh), r((d * xh).abs()))
+    out["dbeta"] = (r(d), r(d.abs()))
+    out["db"] = (r(dc), r(dcm))
+    out["dW"] = (torch.matmul(dc.reshape(-1, E).t(), P2).reshape(w.shape), torch.matmul(dcm.reshape(-1, E).t(), P2.abs()).reshape(w.shape))
+    return out
+
+
+def row_scale_add(x, r, s):
+    """{"y"} of ops_swin.row_scale_add (adm_rowscale_add): y[b] = x[b] + s[b] r[b], or s[b] r[b] when x is None.  A sample with
+    s[b] == 0 copies x (so a -0.0 stays -0.0) or, without x, is +0.0.  From fp32 operands the fp64 value is the exact product plus one
+    rounding: rounded once more to fp32 it is what one fused multiply-add gives."""
+    r_ = _d(r)
+    sv = _d(s, r).reshape(-1, *([1] * (r_.dim() - 1)))
+    if x is None:
+        y = torch.where(sv == 0, torch.zeros_like(r_), sv * r_)
+        return {"y": (y, y.abs())}
+    x_ = _d(x, r)
+    y = torch.where(sv == 0, x_, x_ + sv * r_)
+    return {"y": (y, x_.abs() + (sv * r_).abs())}
+
+
 def errors(got, ref, mag):
     """(e_max, e_rms) of got against the fp64 reference, relative to max / rms of mag (0 where mag is all zero and got exact)."""
     d = got.detach().to(device=ref.device, dtype=_f64) - ref
