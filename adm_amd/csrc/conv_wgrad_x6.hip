@@ -433,6 +433,56 @@ int g_wgrad_cb = -1;      // -1: chosen per launch, 1 / 2: 64-cout blocks per wo
 // 128 couts per workgroup: fp16 format, not the deterministic workspace mode (its split plan is made without the format), > 64 couts
 inline int wgrad_cb(int fmt, bool det, int Cout) { return (fmt && !det && Cout > XT && g_wgrad_cb != 1) ? 2 : 1; }
 
+// ---- split count of the 3x3 launch over its Pp 2x2 tiles (one workgroup per CU: 256 slots; >= 96 tiles = 6 stages per split; <= 64)
+// The fill rule: the count whose workgroup total fills whole rounds of 256 best, with a mild preference for fewer splits.  It prices
+// a split's epilogue at nothing.
+int wgrad_x6_fill_splits(long tiles, int maxs) {
+  const long slots = 256;
+  double best = -1.0;
+  int splits = 1;
+  for (int sN = 1; sN <= maxs; ++sN) {
+    const long wgs = tiles * sN;
+    const long rounds = (wgs + slots - 1) / slots;
+    const double fill = (double)wgs / (double)(rounds * slots) - 0.002 * sN;
+    if (fill > best + 1e-9) { best = fill; splits = sN; }
+  }
+  return splits;
+}
+// The time model, in stages: a launch takes (rounds of 256 workgroups) x (stages of a split + the epilogue).  With more than one
+// split a 128 x 64 workgroup adds 128 x 3 x 64 floats with float atomics, 256 contiguous bytes per wave instruction: at the chip-wide
+// atomic rate (~1.3 TB/s, one such instruction per ~50 ns and CU) that is ~19 us when every CU of a round reaches it together, ~15 of
+// the ~1.3 us stages; one split stores the same bytes plainly, at about three times that rate (5).  The forced-split sweep of
+// tools/bench_wgrad_x6.cpp (XW_SWEEP=1, B = 128, the fp16 format's 128-cout form; profiles/small_map_plan_kernel_stats.md) puts
+// every shape's fastest count, or one within 3 % of it, at this model's minimum for any epilogue between 8 and 20 stages, provided
+// the model only overrules the fill rule where it is more than 5 % ahead: rounds are not synchronised and a stage is not one length
+// (it grows with the number of workgroups that share the L2s), so the model does not resolve less than that.  8x8 384->384: 7 -> 3
+// splits (0.083 -> 0.072 ms), 8x8 768->384: 7 -> 3 (0.158 -> 0.138), 4x4 768->384: 5 -> 1 (0.082 -> 0.047), 16x16 192->192: 21 -> 10
+// (0.090 -> 0.078); the other 16x16 and the 32x32 plans stay.
+constexpr int XW_EPI_ATOMIC = 15, XW_EPI_STORE = 5;
+long wgrad_x6_model_time(long tiles, int Pp, int splits) {      // (splits: a count with no empty split)
+  const int stages = adm_cdiv(adm_cdiv(Pp, splits), XK);
+  return (tiles * splits + 255) / 256 * (stages + (splits > 1 ? XW_EPI_ATOMIC : XW_EPI_STORE));
+}
+// by_time: only the launches the sweep covers (fp16 format, 128-cout workgroups, atomic mode); the deterministic workspace mode, whose
+// plan the caller sizes its workspace by, and the other forms keep the fill rule
+int wgrad_x6_auto_splits(int Pp, int Cin, int Cout, int cb, bool by_time) {
+  const long tiles = (long)adm_cdiv(Cout, XT * cb) * adm_cdiv(Cin, XT) * 4;
+  const int maxs = (int)std::min<long>((Pp + 95) / 96, 64);
+  auto real = [&](int s) { const int chunk = ((Pp + s - 1) / s + XK - 1) / XK * XK; return (Pp + chunk - 1) / chunk; };
+  const int fill_nominal = wgrad_x6_fill_splits(tiles, maxs);      // (the launcher drops its empty splits, as before)
+  if (!by_time) return fill_nominal;
+  const int fill = real(fill_nominal);
+  int best = fill;
+  long best_t = wgrad_x6_model_time(tiles, Pp, fill);
+  const long fill_t = best_t;
+  for (int s = 1; s <= maxs; ++s) {
+    if (real(s) != s) continue;                     // (an empty split would be dropped: the same launch as a smaller count)
+    const long t = wgrad_x6_model_time(tiles, Pp, s);
+    if (t < best_t) { best_t = t; best = s; }
+  }
+  return best_t * 21 < fill_t * 20 ? best : fill_nominal;   // more than 5 % ahead
+}
+
 template <int MODE>
 int wgrad_x6_launch(const WxP& p, dim3 grid, int xbf, int fmt, int cb, hipStream_t stream) {
   static bool attr_set = false;
@@ -479,22 +529,8 @@ int wgrad_x6_impl(const float* x, const float* dy, float* dwp, float* dbias, int
   p.xbytes = (int)xb; p.dybytes = (int)db;
   p.tilesN = adm_cdiv(Cin, XT);
   const int cb = wgrad_cb(fmt, det, Cout);
-  const long tiles = (long)adm_cdiv(Cout, XT * cb) * p.tilesN * 4;
   const bool prezeroed = splits == ADM_SPLITS_AUTO_PREZEROED;      // zero-at-rest workspace: no memset
-  if (splits <= 0) {
-    // one workgroup per CU: 256 slots.  The split count whose workgroup total fills whole rounds best, with a mild preference for
-    // fewer splits; >= 96 tiles (6 stages) per split
-    const long slots = 256;
-    const int maxs = (int)std::min<long>((p.Pp + 95) / 96, 64);
-    double best = -1.0;
-    splits = 1;
-    for (int sN = 1; sN <= maxs; ++sN) {
-      const long wgs = tiles * sN;
-      const long rounds = (wgs + slots - 1) / slots;
-      const double fill = (double)wgs / (double)(rounds * slots) - 0.002 * sN;
-      if (fill > best + 1e-9) { best = fill; splits = sN; }
-    }
-  }
+  if (splits <= 0) splits = wgrad_x6_auto_splits(p.Pp, Cin, Cout, cb, fmt && cb == 2 && !det);
   int chunk = ((p.Pp + splits - 1) / splits + XK - 1) / XK * XK;
   splits = (p.Pp + chunk - 1) / chunk;
   if (plan_only) return splits;
@@ -572,6 +608,16 @@ extern "C" int adm_conv_wgrad_x6_ws(const float* x, const float* dy, float* ws, 
 }
 extern "C" int adm_conv_wgrad_x6_plan(int B, int H, int W, int Cin, int Cout) {
   return wgrad_x6_impl(nullptr, nullptr, nullptr, nullptr, B, H, W, Cin, Cin, Cout, Cout, 0, false, true, 0, nullptr);
+}
+// The split count adm_conv_wgrad_x6_h3 takes for splits <= 0 outside the deterministic mode (float atomics into dwp2): a host query
+extern "C" int adm_conv_wgrad_x6_h3_plan(int B, int H, int W, int Cin, int Cout) {
+  if (B <= 0 || H < 2 || W < 2 || (H & (H - 1)) || (W & (W - 1)) || (Cin & 31) || (Cout & 31)) return ADM_EINVAL;
+  const long Pp = (long)B * H * W / 4;
+  if (Pp >= (1L << 29)) return ADM_EINVAL;
+  const int cb = wgrad_cb(1, false, Cout);
+  const int s = wgrad_x6_auto_splits((int)Pp, Cin, Cout, cb, cb == 2);
+  const int chunk = (((int)Pp + s - 1) / s + XK - 1) / XK * XK;
+  return ((int)Pp + chunk - 1) / chunk;
 }
 
 // Weight gradient of a 1x1 conv / pixel-wise linear map on the same kernel (MODE 1): dwp[Cout][Cin] (+)= sum over P pixels of

@@ -181,6 +181,10 @@ int adm_conv_wgrad_x6_h3(const float* x, const float* dy, float* dwp2, float* db
                          int lddy, int splits, int up, int det, const float* amax_x, const float* amax_dy, hipStream_t stream);
 int adm_gemm_wgrad_x6_h3(const float* x, const float* dy, float* dwp, float* dbias, long P, int Cin, int ldx, int Cout, int lddy,
                          int splits, int det, const float* amax_x, const float* amax_dy, hipStream_t stream);
+/* the split count adm_conv_wgrad_x6_h3 takes for splits <= 0 and det == 0: where its 128-cout workgroups qualify, the minimum of a time
+ * model (rounds of 256 workgroups x (stages of a split + the atomic epilogue)) where that beats the fill rule of adm_conv_wgrad_x6_plan
+ * by more than 5 %, else the fill rule's count; >= 6 stages of 16 tiles per split, <= 64 */
+int adm_conv_wgrad_x6_h3_plan(int B, int H, int W, int Cin, int Cout);
 /* kernel variant of adm_conv_fwd_wino2d: -1 (default) chosen per launch, 1 wave-specialised (producer / consumer waves), 0 symmetric;
  * returns the old value */
 int adm_wino2d_variant(int ws);

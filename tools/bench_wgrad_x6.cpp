@@ -46,7 +46,60 @@ static void run(int B, int H, int Cin, int Cout) {
          B, H, Cin, Cout, ms[0], fl / ms[0] / 1e9, ms[1], fl / ms[1] / 1e9, ms[2], fl / ms[2] / 1e9, adm_conv_wgrad_x6_plan(B, H, H, Cin, Cout), ms[3], fl / ms[3] / 1e9, mx, sc, bm, bs);
   hipFree(x); hipFree(dy); hipFree(w0); hipFree(w1); hipFree(b0); hipFree(b1);
 }
+// XW_SWEEP=1: the fp16-format kernel (128-cout workgroups where they qualify) at forced split counts, every figure twice; the line
+// "auto" is the launcher's own plan.  A forced count > 1 zeroes dwp before each launch (the product's workspace is zero at rest), so
+// the memset alone is timed too.
+static void sweep(int B, int H, int Cin, int Cout) {
+  size_t nx = (size_t)B * H * H * Cin, ny = (size_t)B * H * H * Cout, nw = (size_t)Cout * 12 * Cin;
+  std::vector<float> hx(nx), hy(ny);
+  for (auto& v : hx) v = (rand() / (float)RAND_MAX) * 2 - 1;
+  for (auto& v : hy) v = ((rand() / (float)RAND_MAX) * 2 - 1) * 0.05f;
+  float *x, *dy, *w, *b, *am;
+  hipMalloc(&x, nx * 4); hipMalloc(&dy, ny * 4); hipMalloc(&w, nw * 4); hipMalloc(&b, Cout * 4); hipMalloc(&am, 2 * ADM_AMAX_FLOATS * 4);
+  hipMemset(am, 0, 2 * ADM_AMAX_FLOATS * 4); hipMemset(w, 0, nw * 4); hipMemset(b, 0, Cout * 4);
+  { const float hx1 = 1.0f, hy1 = 0.05f; hipMemcpy(am, &hx1, 4, hipMemcpyHostToDevice); hipMemcpy(am + ADM_AMAX_FLOATS, &hy1, 4, hipMemcpyHostToDevice); }
+  hipMemcpy(x, hx.data(), nx * 4, hipMemcpyHostToDevice); hipMemcpy(dy, hy.data(), ny * 4, hipMemcpyHostToDevice);
+  hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+  adm_wgrad_h3_blocks(-1);
+  const int reps = H <= 8 ? 40 : 12;
+  auto timed = [&](auto&& f) {
+    for (int i = 0; i < 3; ++i) f();
+    hipDeviceSynchronize();
+    hipEventRecord(e0);
+    for (int i = 0; i < reps; ++i) f();
+    hipEventRecord(e1); hipEventSynchronize(e1);
+    float ms; hipEventElapsedTime(&ms, e0, e1);
+    return ms / reps;
+  };
+  const int Pp = B * H * H / 4, maxs = std::min((Pp + 95) / 96, 64);
+  printf("sweep B=%d H=%d Cin=%d Cout=%d (%d stages of 16 tiles, at most %d splits), ms twice\n", B, H, Cin, Cout, (Pp + 15) / 16, maxs);
+  auto memset_only = [&]() { hipMemsetAsync(w, 0, nw * 4, 0); };
+  { const float m0 = timed(memset_only), m1 = timed(memset_only); printf("  memset of dwp alone  %.4f %.4f\n", m0, m1); }
+  auto launch = [&](int splits) { return adm_conv_wgrad_x6_h3(x, dy, w, b, B, H, H, Cin, Cin, Cout, Cout, splits, 0, 0, am, am + ADM_AMAX_FLOATS, 0); };
+  {   // the launcher's plan on the zero-at-rest contract (no memset; the sums run on, the time does not depend on them)
+    const float a0 = timed([&]() { launch(ADM_SPLITS_AUTO_PREZEROED); }), a1 = timed([&]() { launch(ADM_SPLITS_AUTO_PREZEROED); });
+    printf("  auto                 %.4f %.4f\n", a0, a1);
+  }
+  int last = 0;
+  for (int s : {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 18, 21, 24, 28, 32, 42, 64}) {
+    if (s > maxs) break;
+    const int chunk = ((Pp + s - 1) / s + XK - 1) / XK * XK, real = (Pp + chunk - 1) / chunk;
+    if (real == last) continue;      // (an empty split was dropped: the same launch as the line before)
+    last = real;
+    if (launch(s) != 0) { printf("  splits %d: failed\n", s); continue; }
+    const float a0 = timed([&]() { launch(s); }), a1 = timed([&]() { launch(s); });
+    printf("  splits %2d (%3d stages) %.4f %.4f\n", real, chunk / XK, a0, a1);
+  }
+  hipFree(x); hipFree(dy); hipFree(w); hipFree(b); hipFree(am);
+}
 int main() {
+  if (getenv("XW_SWEEP")) {
+    sweep(128, 8, 384, 384); sweep(128, 8, 768, 384); sweep(128, 4, 384, 384); sweep(128, 4, 768, 384);
+    sweep(128, 16, 384, 384); sweep(128, 16, 768, 384); sweep(128, 16, 192, 384); sweep(128, 16, 576, 384); sweep(128, 16, 192, 192);
+    sweep(128, 32, 192, 192); sweep(128, 32, 384, 192); sweep(128, 32, 576, 192); sweep(128, 32, 384, 384);
+    sweep(32, 32, 384, 256); sweep(16, 64, 384, 256);      // the two shapes of the other shipped configs whose plan the model moves
+    return 0;
+  }
 #if XW_ABL
   printf("ABL=%d ", XW_ABL); run(128, 32, 192, 192); return 0;
 #endif
