@@ -213,6 +213,8 @@ _SIGS = {
     "adm_kid_sums_blocks": [I],
     "adm_kid_sums": [P, I, P, I, I, P, P, I, I, I, D, D, P, P, P],
     "adm_saliency_tables": [P, I, P, P, P, I, I, I, P],
+    "adm_restoration_blocks": [I, I],
+    "adm_restoration_sums": [P, I, P, I, P, P, P, P, I, I, I, I, I, P],
 }
 EXPORTS = tuple(_SIGS)
 
@@ -258,7 +260,7 @@ def ptr(t) -> c_void_p:
 
 
 NO_STREAM = ("adm_version", "adm_conv_splitk", "adm_gn_splits", "adm_aug_workspace_floats", "adm_conv_wgrad_plan",
-             "adm_sumsq_blocks", "adm_lnc_blocks", "adm_bn_blocks", "adm_linattn_ws_floats", "adm_wino2d_splitk", "adm_wino2d_x6_splitk", "adm_wino2d_variant", "adm_wino2d_h3_wide", "adm_wino2d_x6_row_reuse", "adm_wgrad_h3_blocks", "adm_gn_fused", "adm_gn_plan", "adm_conv_wgrad_x6_plan", "adm_conv_wgrad_x6_h3_plan", "adm_gemm_wgrad_x6_plan", "adm_lpips_head_blocks", "adm_ae_blocks", "adm_swin_attn_bwd_ws_floats", "adm_ln_bwd_ws_floats", "adm_sr_tile", "adm_pair_resize_lds", "adm_patch_embed_ln_bwd_ws_floats", "adm_conv_bf16_tile", "adm_conv_wgrad_bf16_plan", "adm_depth_metrics_blocks", "adm_kid_sums_tile", "adm_kid_sums_blocks", "adm_attn_form", "adm_ln_form", "adm_patch_embed_form")      # host-side queries: no stream argument, called as lib().name(...)
+             "adm_sumsq_blocks", "adm_lnc_blocks", "adm_bn_blocks", "adm_linattn_ws_floats", "adm_wino2d_splitk", "adm_wino2d_x6_splitk", "adm_wino2d_variant", "adm_wino2d_h3_wide", "adm_wino2d_x6_row_reuse", "adm_wgrad_h3_blocks", "adm_gn_fused", "adm_gn_plan", "adm_conv_wgrad_x6_plan", "adm_conv_wgrad_x6_h3_plan", "adm_gemm_wgrad_x6_plan", "adm_lpips_head_blocks", "adm_ae_blocks", "adm_swin_attn_bwd_ws_floats", "adm_ln_bwd_ws_floats", "adm_sr_tile", "adm_pair_resize_lds", "adm_patch_embed_ln_bwd_ws_floats", "adm_conv_bf16_tile", "adm_conv_wgrad_bf16_plan", "adm_depth_metrics_blocks", "adm_kid_sums_tile", "adm_kid_sums_blocks", "adm_attn_form", "adm_ln_form", "adm_patch_embed_form", "adm_restoration_blocks")      # host-side queries: no stream argument, called as lib().name(...)
 
 
 def call(name: str, *args):

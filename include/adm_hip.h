@@ -1027,6 +1027,32 @@ int adm_kid_sums(const float* f1, int n1, const float* f2, int n2, int D, const 
 int adm_saliency_tables(const void* pred, int pred_is_f32, const uint8_t* map, int64_t* tables, int64_t* head, int B, int H, int W,
                         hipStream_t stream);
 
+/* ================================================================================================
+ * Restoration score (csrc/restoration_metrics.hip): the sums behind PSNR and SSIM, on RGB and on Y, in one launch.
+ * ================================================================================================ */
+
+/* pred / target [B][C][H][W], C = 1 or 3, each uint8 or -- with its own *_is_f32 != 0 -- float32 (quantised as
+ * rintf(fminf(fmaxf(v, 0), 1) * 255), ties to even, NaN -> 0: the bytes of the samplers' 8-bit PNGs).  crop_border = s >= 0 pixels are
+ * skipped on every side by addressing: the scored area is H' x W' = (H - 2s) x (W - 2s).  Planes P: for C = 3 four -- R, G, B and
+ * Y = 16 + N / 255000 with the integer N = 65481 R + 128553 G + 24966 B --, for C = 1 one.  Per image and plane:
+ *   sse  [B][P][2] int64  = {lo, hi}, hi 2^32 + lo = the sum over the area of d^2 as an exact integer, 0 <= lo < 2^32; d = p - g on a
+ *                           byte plane, N_p - N_g on Y (the caller scales by 255000^-2)
+ *   ssim [B][P]    double = the SUM over the (H' - 10) x (W' - 10) valid positions of the SSIM value under the 11 x 11 Gaussian
+ *                           window (sigma 1.5, normalised, separable), C1 = 6.5025, C2 = 58.5225; filtered in float64
+ * One workgroup per ADM_RESTORATION_TILE^2 tile of valid positions and image: adm_restoration_blocks(H', W') of them per image
+ * (ADM_EINVAL below 11 x 11).  Each writes its sums to partial [B][blocks][P][2] int64, and the last one of an image to finish
+ * (ticket[b], an integer counter) adds them in index order: no float atomics, the same bits every run.  ticket: int32 [B], ZERO on
+ * entry and zero again on return.  Both outputs are overwritten whole.  Images need no alignment (image k starts at element
+ * k C H W); 4- and 16-byte loads are used where the addresses allow.  ADM_EINVAL, without launching: a null pointer, B outside
+ * 1 .. 65535, C not 1 or 3, crop_border < 0, H' or W' < 11, H W > ADM_RESTORATION_MAX_PIXELS, a float32 input off a 4-byte, an output
+ * or partial off an 8-byte or ticket off a 4-byte boundary. */
+#define ADM_RESTORATION_TILE 32
+#define ADM_RESTORATION_WINDOW 11
+#define ADM_RESTORATION_MAX_PIXELS (1L << 24)
+int adm_restoration_blocks(int Hs, int Ws);
+int adm_restoration_sums(const void* pred, int pred_is_f32, const void* target, int target_is_f32, int64_t* sse, double* ssim,
+                         int64_t* partial, int* ticket, int B, int C, int H, int W, int crop_border, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

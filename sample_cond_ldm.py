@@ -32,6 +32,13 @@ condition is the photo resized to the model's resolution and the windows run at 
 the resized map's bytes with adm_amd.metrics.saliency (MAE, F-, S- and E-measure): printed at the end and written to
 ``<save_folder>/saliency_metrics.json``; on any other data set the key raises.
 
+``sampler.cal_restoration: True`` (off by default) scores the super-resolution and the in-painting predictions -- the dataset entries
+with a PSNR line and a colour output -- with adm_amd.metrics.restoration: PSNR and SSIM on RGB and on the Y channel of the BYTES the
+png holds (the float prediction is quantised in the kernel as ``save_prediction`` quantises it) against the bytes of the part of
+'image' the prediction covers, with ``sampler.restoration_crop_border`` pixels shaved from every side (default 4 for x4
+super-resolution, 0 for in-painting, whose composite is scored whole).  Printed at the end and written to
+``<save_folder>/restoration_metrics.json``; on any other data set the key raises.  The PSNR line above is untouched.
+
 With ``data.class_name: ddm.data.SketchDataset`` and ``split: test`` (sketch-to-image,
 configs/sketch2img/sketchcoco_cond_ddm_const_ldm_sample.yaml) the condition is the ONE-channel sketch resized to ``image_size`` and the
 output a three-channel image, sampled in one window and written under the sketch's file name.  No PSNR is printed: a generated
@@ -306,6 +313,34 @@ def report_saliency(score, out_dir, world, rank):
     return res
 
 
+def restoration_scorer(data_cfg, s):
+    """The RestorationScore of ``sampler.cal_restoration: True`` (``sampler.restoration_crop_border``: default 4 for the x4
+    super-resolution form, else 0), or None without the key.  Scored are the entries that print a PSNR and write colour: the
+    super-resolution fall-through and in-painting; the key on any other data set raises."""
+    if not bool(s.get("cal_restoration", False)):
+        return None
+    key = sampling_dataset(data_cfg)
+    sm = SR_SAMPLING if key is None else DATASETS[key].sampling
+    if not sm.psnr or sm.gray:
+        raise ValueError(f"sampler.cal_restoration: True scores restored photographs, but data.class_name "
+                         f"{(data_cfg or {}).get('class_name')!r} has none: only super-resolution (ddm.data.SRDatasetTest, synthetic) and "
+                         "ddm.data.InpaintDataset are scored (drop the key)")
+    from adm_amd.metrics.restoration import RestorationScore
+    border = s.get("restoration_crop_border")
+    return RestorationScore((4 if sm.form == "slide_x4" else 0) if border is None else int(border))
+
+
+def report_restoration(score, out_dir, world, rank):
+    """Prints the values and writes <out_dir>/restoration_metrics.json (several ranks: restoration_metrics_rank{r}.json)."""
+    import json
+    res = score.result()
+    print(f"rank {rank}: restoration score over {res['images']} images (crop_border {score.crop_border}): "
+          + " ".join(f"{k}={res[k]:.4f}" for k in res if k != "images"))
+    with open(os.path.join(out_dir, "restoration_metrics.json" if world == 1 else f"restoration_metrics_rank{rank}.json"), "w") as f:
+        json.dump(res, f)
+    return res
+
+
 def window_sampler(ldm, scale):
     """c [B,C,h,w] -> the sample for the window c, `scale` times its size.  The encoder runs ONCE per window batch (the reference
     re-runs it inside every denoising step, cond_unet_sd.py:821)."""
@@ -367,6 +402,7 @@ def main():
     per_rank = n_total // world
     key = sampling_dataset(cfg.data)
     saliency_score = saliency_scorer(cfg.data, s)
+    restoration_score = restoration_scorer(cfg.data, s)
     if key is None:
         sm = SR_SAMPLING
         stream = CondStream(cfg.data, per_rank, device, seed=2000 + rank)
@@ -398,6 +434,9 @@ def main():
             depth_score.add(pred.to(torch.float32).contiguous(), ((batch["image"] + 1) * 0.5).contiguous())
         if saliency_score is not None:          # the bytes the png below holds against the resized map's bytes; tables stay on the device
             saliency_score.add(pred[:, :1].to(torch.float32).contiguous(), batch["image_u8"])
+        if restoration_score is not None:          # the bytes the png below holds against the target's; the sums stay on the device
+            target = (batch["image"] + 1) * 0.5
+            restoration_score.add(pred.to(torch.float32).contiguous(), target[:, :, :pred.shape[2], :pred.shape[3]].to(torch.float32).contiguous())
         if sm.depth and not bool(s.get("depth_png8", False)):
             name = save_depth_prediction(pred[0], out_dir, batch["img_name"], world, rank * per_rank + done)
         else:
@@ -418,6 +457,8 @@ def main():
             json.dump(res, f)
     if saliency_score is not None:
         report_saliency(saliency_score, out_dir, world, rank)
+    if restoration_score is not None:
+        report_restoration(restoration_score, out_dir, world, rank)
 
 
 if __name__ == "__main__":
